@@ -25,7 +25,9 @@ Protocol (what happens, in order; all of it is reported in the JSON line):
      shader clock before/after are emitted so the effect is visible.  `--precondition-s 0` disables it.
   2. W warm-up steps (untimed), barrier + synchronize.
   3. EXACTLY K timed steps between HIP events on the launch stream and a host timer, barrier +
-     synchronize, max over ranks -> `value`, `ms_per_step`, `roofline.achieved`.
+     synchronize, max over ranks -> `value`, `ms_per_step`, `roofline.achieved`.  With `--dump-outputs DIR`
+     rank 0 keeps what the last timed step computed (forward: out, lse; backward: dq, dk, dv) and writes it
+     as DIR/<name>.npy in float32 after the line's other measurements (see dump_outputs()).
   4. K more steps with one event pair per launch -> `per_launch_ms` {median, min, max, mean}.
   5. K steps in the reference's own harness style: host timer, synchronize after EVERY call
      (flash_attention_cutlass/test.py:30-40) -> `reference_harness_ms`.
@@ -261,6 +263,40 @@ def secondary_measurements(dev, budget_s=11.0):
     return res
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # all of --dump-outputs' files together stay below 64 MB
+
+
+def sample_outputs(named):
+    """--dump-outputs: [(name, device tensor)] -> [(file name, float32/float64 device tensor)], taken right behind the timed
+    region.  A tensor whose float32 copy fits its share of DUMP_BUDGET_BYTES is kept whole; a larger one keeps a fixed
+    sample of its rows (all dims but the last flattened; torch.randperm seeded with 0, sorted), and the row indices go
+    beside it as <name>_rows (float64, exact)."""
+    share = DUMP_BUDGET_BYTES // len(named)
+    res = []
+    for name, t in named:
+        rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        if rows.numel() * 4 <= share:
+            res.append((name, t.float().clone()))
+            continue
+        n = share // (4 * rows.shape[1])
+        idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+        res.append((name, rows.index_select(0, idx.to(t.device)).float()))
+        res.append((name + "_rows", idx.double()))
+    return res
+
+
+def dump_outputs(outdir, sampled):
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    files = {}
+    for name, t in sampled:
+        a = t.cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return files
+
+
 def workload_text(cfg_name, world, bwd=False, bwd_form="default"):
     B, H, N, D, dtype, causal = CONFIGS[cfg_name]
     what = ("backward (" + bwd_form + " form" + {"default": ": dQ launch, which forms delta, + fused dK/dV launch", "split": ": delta, dQ, dK, dV launches",
@@ -409,7 +445,12 @@ def main():
     ap.add_argument("--bwd-form", default="default", choices=["default", "split", "workspace"],
                     help="bwd mode: tfa_bwd's form — default (7 GEMM units), split (dK and dV as two launches: round 2's 8 units), "
                          "workspace (dS kept in scratch memory: 5 units)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (forward: out, lse; backward: dq, dk, dv) to DIR/<name>.npy in float32; "
+                         "outputs too large for the 48 MB budget are a fixed sample of rows, with the row indices in <name>_rows.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "RANK" not in os.environ and args.gpus > 1:
@@ -430,6 +471,8 @@ def main():
     bwd = args.mode == "bwd"
 
     if fake:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs needs the real hot path (not --fake-step-ms)")
         line = fake_run(args, world, rank, cfg_name, do_gather)
         if rank == 0:
             print(json.dumps(line), flush=True)
@@ -570,6 +613,9 @@ def main():
 
     # ---- 2. warm-up, 3. the timed region (kernel only: `value`) ----------------------------------------------
     wall, ev_ms = timed_region(step)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = sample_outputs([("dq", dq), ("dk", dk), ("dv", dv)] if bwd else [("out", out), ("lse", lse)])
 
     # ---- 4. per-launch durations (one event pair per launch) -------------------------------------------------
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -716,6 +762,9 @@ def main():
             except Exception as e:
                 line["cpu_baseline_python"] = {"value": None, "unit": "TFLOP/s", "cores": os.cpu_count(), "kind": "port",
                                                "sample": f"unavailable: {e!r}"}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, dumped),
+                                    "what": "the last timed step's outputs, float32; *_rows: row indices of a seeded sample (float64)"}
         print(json.dumps(line), flush=True)
 
     if dist is not None:

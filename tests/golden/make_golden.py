@@ -111,10 +111,33 @@ def golden_torch_only():
     )
 
 
+def golden_ref_kernels():
+    """The reference's compiled naive_attn and flash_attn on fp32 inputs from oracle.make_inputs (seed 5,
+    B=2 H=3 N=32 D=64, scale 0.2): the full square problem and Nq=12 queries against the first Nk=24 keys,
+    each causal and non-causal.  The inputs are not stored: tests/test_oracle.py makes them with the same call."""
+    from oracle import oracle as O
+
+    ref = O.ref_kernels()
+    assert ref is not None, "run `make -C oracle` first"
+    q, k, v = O.make_inputs(2, 3, 32, 64, torch.float32, seed=5)
+    res = {}
+    for causal in (0, 1):
+        for tag, (a, b, c) in (("full", (q, k, v)), ("nq12_nk24", (q[:, :, :12].contiguous(), k[:, :, :24].contiguous(), v[:, :, :24].contiguous()))):
+            res[f"naive_{tag}_c{causal}"] = ref.naive_attn(a, b, c, bool(causal), 0.2).numpy()
+            res[f"flash_{tag}_c{causal}"] = ref.flash_attn(a, b, c, bool(causal), 0.2).numpy()
+    np.savez_compressed(
+        os.path.join(HERE, "ref_kernels_seed5.npz"),
+        scale=np.float64(0.2),
+        source="flash_attention_c/csrc/attn.cpp naive_attn:206-234 flash_attn:237-262 (compiled unmodified)",
+        **res,
+    )
+
+
 if __name__ == "__main__":
     golden_tiny_py()
     golden_c_kernels()
     golden_torch_only()
+    golden_ref_kernels()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))
