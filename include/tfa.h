@@ -339,6 +339,99 @@ int tfa_debug_mfma_ceiling(const void* operands, unsigned long long bytes, doubl
  * convention) and bytes = Q+K+V read once + O written once (+LSE). */
 int tfa_fwd_work(const tfa_fwd_params* p, double* flops, double* bytes);
 
+/* ---- packed variable-length batches (the cu_seqlens form of FlashAttention-2's flash_attn_varlen_func) --------------------------------
+ * B sequences of different lengths packed along the rows: q is (total_q, H, D), k and v are (total_k, Hk, D), out is shaped like q; sequence b is
+ * rows [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q / out and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k / v.  cu_seqlens_q / _k are DEVICE int32
+ * arrays of B + 1 entries (cu[0] = 0, non-decreasing) that the library never reads on the host: no copy, no synchronisation — a call is asynchronous
+ * and can be captured in a graph.  Each work item of the kernels reads its sequence's four bounds itself (scalar loads) and clamps them into
+ * [0, total_q] / [0, total_k] and the lengths to max_seqlen_q / _k, so a bad cu_seqlens can misplace results but never address outside the tensors.
+ *   - every sequence has at most max_seqlen_q query rows and max_seqlen_k keys (host integers: they size the grids);
+ *   - causal masking per sequence, bottom-right aligned as in tfa_fwd: key j is visible to row i iff j <= i + (Nk_b - Nq_b); rows that see no key —
+ *     every row of a sequence with Nk_b = 0 — get out = 0, lse = +inf; sequences with Nq_b = 0 are allowed;
+ *   - lse: fp32 (H, total_q), contiguous, natural log (FlashAttention-2's varlen layout); delta (backward scratch) the same;
+ *   - GQA / MQA as in tfa_fwd (Hk divides H): dk / dv are summed over the query heads of each K/V head, within each sequence;
+ *   - rows outside every sequence (cu_q[B] <= r < total_q, and the same for keys) are never read into a result and never written.
+ * Strides are (head, row) pairs in elements, unit stride along D, every row 16-byte aligned; head dims = multiples of 8 up to 128; 16-bit q, k, v.
+ * Kernels: the forward runs the varlen form of the kernel tfa_fwd would pick for the fixed-length problem (B, H, Hk, max_seqlen_q, max_seqlen_k, D)
+ * — il8 (variant 30) or il4 (32); the key-split choices (36, 37) map to il4.  Only the MAIN instantiation of each exists in varlen form (full width,
+ * for bf16 the first-tile rule): with equal lengths and a head dim that reaches the kernel's last 32 columns (D = 40..64 or 104..128) the call runs
+ * the very kernel tfa_fwd runs, with the same bits.  Head dims that leave the kernel's last 32 columns empty (D <= 32, 72..96) run the full-width kernel with
+ * those columns read as zeros: tfa_fwd runs a narrow instantiation there (fewer MFMAs — a third fewer at D = 96 — and, for bf16, TFA_RULE_LAZY), so the two
+ * agree within the bounds of "Rounding points" but not in bits.  The backward's varlen launches are full-width too (tfa_bwd's dQ and dK/dV launches have
+ * narrow twins at those head dims).
+ * The backward runs its dQ launch (which also forms delta) and its fused dK/dV launch in varlen form.
+ * Out of scope (refused): head dims above 128 (TFA_ERR_HEAD_DIM), fp32 inputs (TFA_ERR_DTYPE), TFA_FWD_EXACT_MAX and any other flag (flags must be 0:
+ * TFA_ERR_SHAPE), split-KV, paged K/V, GQA decode row packing, the backward's dS-workspace form, sliding windows, dropout, and sequences whose
+ * max_seqlen rows would not fit one buffer descriptor (TFA_ERR_STRIDE: no windowed varlen form).  A NULL cu_seqlens is TFA_ERR_NULL;
+ * B, H, Hk, max_seqlen or total <= 0 or H % Hk != 0 is TFA_ERR_SHAPE.
+ * Measured: profiles/varlen_bench.txt (tools/bench_varlen.py; equal lengths at the speed of tfa_fwd / tfa_bwd, mixed lengths against padding and
+ * against one call per sequence), quoted in INTEGRATION.md. */
+typedef struct tfa_varlen_fwd_params {
+  const void* q;               /* (total_q, H,  D) */
+  const void* k;               /* (total_k, Hk, D) */
+  const void* v;               /* (total_k, Hk, D) */
+  void* out;                   /* (total_q, H,  D) of out_dtype */
+  float* lse;                  /* (H, total_q) fp32 contiguous, or NULL to skip */
+  const int32_t* cu_seqlens_q; /* device, B + 1 entries */
+  const int32_t* cu_seqlens_k; /* device, B + 1 entries */
+  int32_t B, H, Hk, D;
+  int32_t max_seqlen_q, max_seqlen_k;
+  int32_t total_q, total_k;    /* rows of q / out and of k / v */
+  int64_t q_stride[2];         /* head, row (elements) */
+  int64_t k_stride[2];
+  int64_t v_stride[2];
+  int64_t o_stride[2];         /* in elements of out_dtype */
+  float softmax_scale;
+  int32_t is_causal;
+  int32_t dtype;               /* TFA_F16 or TFA_BF16 */
+  int32_t out_dtype;           /* == dtype, or TFA_F32 */
+  int32_t flags;               /* must be 0 */
+  int32_t reserved_;           /* must be 0 */
+} tfa_varlen_fwd_params;
+
+typedef struct tfa_varlen_bwd_params {
+  const void* q;
+  const void* k;
+  const void* v;
+  const void* out;
+  const void* dout;            /* shaped like out, input dtype */
+  const float* lse;            /* (H, total_q), as written by tfa_fwd_varlen */
+  void* dq;                    /* shaped like q, grad_dtype */
+  void* dk;                    /* shaped like k */
+  void* dv;                    /* shaped like v */
+  float* delta;                /* scratch, H * total_q floats (4-byte aligned) */
+  const int32_t* cu_seqlens_q;
+  const int32_t* cu_seqlens_k;
+  int32_t B, H, Hk, D;
+  int32_t max_seqlen_q, max_seqlen_k;
+  int32_t total_q, total_k;
+  int64_t q_stride[2];         /* head, row (elements) */
+  int64_t k_stride[2];
+  int64_t v_stride[2];
+  int64_t o_stride[2];
+  int64_t do_stride[2];
+  int64_t dq_stride[2];        /* in elements of grad_dtype */
+  int64_t dk_stride[2];
+  int64_t dv_stride[2];
+  float softmax_scale;
+  int32_t is_causal;
+  int32_t dtype;               /* TFA_F16 / TFA_BF16 */
+  int32_t grad_dtype;          /* == dtype, or TFA_F32 */
+  int32_t flags;               /* must be 0 */
+  int32_t reserved_;           /* must be 0 */
+} tfa_varlen_bwd_params;
+
+/* Launch the packed forward on `stream` (asynchronous, never allocates, never reads cu_seqlens on the host). */
+int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream);
+/* Validate *p without launching (no GPU needed); on success optionally reports the launch geometry. */
+int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes);
+/* The kernel variant tfa_fwd_varlen runs for *p (30 or 32; the forced one if tfa_set_variant forces 30 or 32), or a negative TFA_ERR_* code. */
+int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p);
+/* The row reference P is rounded against (TFA_RULE_*, the header's "Rounding points"): TFA_RULE_FIRST_TILE for bf16, TFA_RULE_LAZY for fp16. */
+int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p);
+/* Launch the packed backward on `stream` (asynchronous): the dQ launch (it writes delta), then the fused dK/dV launch.  Deterministic. */
+int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@ from .ops import (  # noqa: F401
     flash_attn_bwd,
     flash_attn_fwd_splitkv,
     merge_partials,
+    flash_attn_varlen_func,
+    flash_attn_varlen_fwd,
+    flash_attn_varlen_bwd,
 )
 from . import _lib  # noqa: F401
 
@@ -38,4 +41,7 @@ __all__ = [
     "flash_attn_bwd",
     "flash_attn_fwd_splitkv",
     "merge_partials",
+    "flash_attn_varlen_func",
+    "flash_attn_varlen_fwd",
+    "flash_attn_varlen_bwd",
 ]

@@ -39,6 +39,11 @@ SYMBOLS = (
     "tfa_bwd_workspace_bytes",
     "tfa_bwd_work",
     "tfa_bwd_time",
+    "tfa_fwd_varlen",
+    "tfa_fwd_varlen_plan",
+    "tfa_fwd_varlen_variant",
+    "tfa_fwd_varlen_rounding_rule",
+    "tfa_bwd_varlen",
 )
 
 
@@ -109,6 +114,79 @@ class TfaBwdParams(C.Structure):
         ("grad_dtype", C.c_int32),
         ("workspace", C.c_void_p),
         ("workspace_bytes", C.c_int64),
+    ]
+
+
+class TfaVarlenFwdParams(C.Structure):
+    """struct tfa_varlen_fwd_params (include/tfa.h): packed variable-length batches, strides as (head, row) pairs."""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("k", C.c_void_p),
+        ("v", C.c_void_p),
+        ("out", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("cu_seqlens_q", C.c_void_p),
+        ("cu_seqlens_k", C.c_void_p),
+        ("B", C.c_int32),
+        ("H", C.c_int32),
+        ("Hk", C.c_int32),
+        ("D", C.c_int32),
+        ("max_seqlen_q", C.c_int32),
+        ("max_seqlen_k", C.c_int32),
+        ("total_q", C.c_int32),
+        ("total_k", C.c_int32),
+        ("q_stride", C.c_int64 * 2),
+        ("k_stride", C.c_int64 * 2),
+        ("v_stride", C.c_int64 * 2),
+        ("o_stride", C.c_int64 * 2),
+        ("softmax_scale", C.c_float),
+        ("is_causal", C.c_int32),
+        ("dtype", C.c_int32),
+        ("out_dtype", C.c_int32),
+        ("flags", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class TfaVarlenBwdParams(C.Structure):
+    """struct tfa_varlen_bwd_params (include/tfa.h)."""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("k", C.c_void_p),
+        ("v", C.c_void_p),
+        ("out", C.c_void_p),
+        ("dout", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("dq", C.c_void_p),
+        ("dk", C.c_void_p),
+        ("dv", C.c_void_p),
+        ("delta", C.c_void_p),
+        ("cu_seqlens_q", C.c_void_p),
+        ("cu_seqlens_k", C.c_void_p),
+        ("B", C.c_int32),
+        ("H", C.c_int32),
+        ("Hk", C.c_int32),
+        ("D", C.c_int32),
+        ("max_seqlen_q", C.c_int32),
+        ("max_seqlen_k", C.c_int32),
+        ("total_q", C.c_int32),
+        ("total_k", C.c_int32),
+        ("q_stride", C.c_int64 * 2),
+        ("k_stride", C.c_int64 * 2),
+        ("v_stride", C.c_int64 * 2),
+        ("o_stride", C.c_int64 * 2),
+        ("do_stride", C.c_int64 * 2),
+        ("dq_stride", C.c_int64 * 2),
+        ("dk_stride", C.c_int64 * 2),
+        ("dv_stride", C.c_int64 * 2),
+        ("softmax_scale", C.c_float),
+        ("is_causal", C.c_int32),
+        ("dtype", C.c_int32),
+        ("grad_dtype", C.c_int32),
+        ("flags", C.c_int32),
+        ("reserved_", C.c_int32),
     ]
 
 
@@ -184,6 +262,17 @@ def lib():
     L.tfa_bwd_time.argtypes = [PB, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     L.tfa_fwd_work.restype = C.c_int
     L.tfa_fwd_work.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    PV = C.POINTER(TfaVarlenFwdParams)
+    L.tfa_fwd_varlen.restype = C.c_int
+    L.tfa_fwd_varlen.argtypes = [PV, C.c_void_p]
+    L.tfa_fwd_varlen_plan.restype = C.c_int
+    L.tfa_fwd_varlen_plan.argtypes = [PV, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tfa_fwd_varlen_variant.restype = C.c_int
+    L.tfa_fwd_varlen_variant.argtypes = [PV]
+    L.tfa_fwd_varlen_rounding_rule.restype = C.c_int
+    L.tfa_fwd_varlen_rounding_rule.argtypes = [PV]
+    L.tfa_bwd_varlen.restype = C.c_int
+    L.tfa_bwd_varlen.argtypes = [C.POINTER(TfaVarlenBwdParams), C.c_void_p]
     _lib = L
     return L
 

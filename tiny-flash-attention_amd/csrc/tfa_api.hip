@@ -333,6 +333,55 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
   p->softmax_scale = scale; p->is_causal = causal; p->dtype = dtype; p->out_dtype = out_dtype;
 }
 
+// Packed variable-length batches (include/tfa.h: tfa_fwd_varlen).  The host knows the sequences' bounds only as max_seqlen_q / _k: it validates the
+// fixed-length problem of ONE sequence of max_seqlen_q x max_seqlen_k rows (batch stride 0 — validate() checks dtypes, scale, strides, alignment and that
+// such a slice fits one descriptor, and fills the kernel arguments), runs B of them as the grid's batch, and leaves the rest to the kernels: each work item
+// reads its sequence's bounds from cu_seqlens on the device (tfa_fwd_kernel.h: varlen_seq).  Kernel choice: what tfa_fwd picks for the fixed-length
+// problem (B, H, Hk, max_seqlen_q, max_seqlen_k, D), restricted to the two kernels with a varlen form — il8 (30) and il4 (32); the key-split ones map to il4.
+int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr) {
+  if (!p) return TFA_ERR_NULL;
+  if (!p->q || !p->k || !p->v || !p->out || !p->cu_seqlens_q || !p->cu_seqlens_k) return TFA_ERR_NULL;
+  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;             // (fp32 inputs: no varlen form)
+  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;           // (the 256-wide kernel has no varlen form)
+  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
+  if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
+  if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;                        // (TFA_FWD_EXACT_MAX: no varlen form)
+  tfa_fwd_params f;
+  memset(&f, 0, sizeof(f));
+  f.q = p->q; f.k = p->k; f.v = p->v; f.out = p->out; f.lse = p->lse;
+  f.B = 1; f.H = p->H; f.Hk = p->Hk; f.Nq = p->max_seqlen_q; f.Nk = p->max_seqlen_k; f.D = p->D;
+  const int64_t* src[4] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride};
+  int64_t* dst[4] = {f.q_stride, f.k_stride, f.v_stride, f.o_stride};
+  for (int t = 0; t < 4; ++t) { dst[t][0] = 0; dst[t][1] = src[t][0]; dst[t][2] = src[t][1]; }
+  f.softmax_scale = p->softmax_scale; f.is_causal = p->is_causal; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
+  tfa_fwd_params eq = f;
+  eq.B = p->B;
+  int variant = pick_variant(&eq);                   // (a variant forced by tfa_set_variant: taken when it is 30 or 32)
+  if (variant == tfa::kKSplitVariant || variant == tfa::kKSplitPairVariant) variant = tfa::kSmallGridVariant;
+  if (variant != tfa::kDefaultVariant && variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
+  tfa::KArgs a;
+  const int st = validate(&f, &a, variant);
+  if (st != TFA_OK) return st;
+  if (a.big) return TFA_ERR_STRIDE;                  // max_seqlen rows of a slice beyond one descriptor: no windowed varlen form
+  const int64_t nbh = (int64_t)p->B * p->H;
+  if (nbh * a.nwork >= (int64_t)0x7fffffff || (int64_t)p->H * p->total_q >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
+  a.B = p->B;
+  a.nbh = (int)nbh;
+  a.kv_stream = 0;
+  a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;   // (KArgs: in the bytes of the split-KV fields, which the il kernels never read)
+  a.total_q = p->total_q; a.total_k = p->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
+  if (variant_out) *variant_out = variant;
+  if (rule_out) *rule_out = (p->dtype == TFA_BF16 && TFA_IL_USE_MAXFREE) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;   // the main instantiations' rules (run() above)
+  const bool causal = p->is_causal != 0, f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (p->dtype == TFA_BF16)
+    e = wide ? tfa::launch_fwd_varlen<__bf16, 128>(a, causal, f32out, variant, s, geom, dry) : tfa::launch_fwd_varlen<__bf16, 64>(a, causal, f32out, variant, s, geom, dry);
+  else
+    e = wide ? tfa::launch_fwd_varlen<_Float16, 128>(a, causal, f32out, variant, s, geom, dry) : tfa::launch_fwd_varlen<_Float16, 64>(a, causal, f32out, variant, s, geom, dry);
+  return (int)e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -559,6 +608,27 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   // (tools/bench_decode_wide.py, profiles/r03_decode_wide.txt)
   if (!one_descriptor(p_in) && s > 4) s = 4;            // (the caller's strides, as tfa_fwd_splitkv tests them — not the packed ones)
   return s >= 2 ? (int)s : 1;
+}
+
+int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return run_varlen(p, stream, nullptr, false); }
+int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = run_varlen(p, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p) {
+  int v = -1;
+  const int st = run_varlen(p, nullptr, nullptr, true, &v);
+  return st != TFA_OK ? st : v;
+}
+int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p) {
+  int r = -1;
+  const int st = run_varlen(p, nullptr, nullptr, true, nullptr, &r);
+  return st != TFA_OK ? st : r;
 }
 
 int tfa_fwd_variant(const tfa_fwd_params* p) {

@@ -241,12 +241,81 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
   return (int)e;
 }
 
+// Packed variable-length batches (include/tfa.h: tfa_bwd_varlen): the dQ launch (which also forms delta) and the fused dK/dV launch, each in its VARLEN
+// instantiation.  As in the forward (tfa_api.hip: run_varlen) the host validates ONE sequence of max_seqlen_q x max_seqlen_k rows — every slice must fit one
+// descriptor, there is no windowed varlen form — sizes the grids from it and never reads cu_seqlens: each work item reads its sequence's bounds itself.
+int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry) {
+  if (!p) return TFA_ERR_NULL;
+  if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta || !p->cu_seqlens_q || !p->cu_seqlens_k)
+    return TFA_ERR_NULL;
+  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (p->grad_dtype != p->dtype && p->grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
+  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
+  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
+  if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
+  if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;
+  if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
+  const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
+  // (head, row) strides as the (batch, head, row) triples of one sequence: batch stride 0
+  int64_t st[8][3];
+  const int64_t* src[8] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride, p->dq_stride, p->dk_stride, p->dv_stride};
+  for (int i = 0; i < 8; ++i) {
+    st[i][0] = 0; st[i][1] = src[i][0]; st[i][2] = src[i][1];
+    const int c = check_strides(st[i], p->D, i < 5 ? esz : gsz);
+    if (c) return c;
+  }
+  const uintptr_t al = (uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out | (uintptr_t)p->dout | (uintptr_t)p->dq |
+                       (uintptr_t)p->dk | (uintptr_t)p->dv;
+  if (al & 15) return TFA_ERR_ALIGN;
+  if (((uintptr_t)p->lse | (uintptr_t)p->delta) & 3) return TFA_ERR_ALIGN;
+  if ((int64_t)p->H * p->total_q >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
+
+  tfa::BArgs a;
+  memset(&a, 0, sizeof(a));
+  const int nq = p->max_seqlen_q, nk = p->max_seqlen_k;
+  if (!fill(&a.q, p->q, st[0], nq, p->D, esz, nullptr) || !fill(&a.k, p->k, st[1], nk, p->D, esz, nullptr) || !fill(&a.v, p->v, st[2], nk, p->D, esz, nullptr) ||
+      !fill(&a.out, p->out, st[3], nq, p->D, esz, nullptr) || !fill(&a.dout, p->dout, st[4], nq, p->D, esz, nullptr))
+    return TFA_ERR_STRIDE;
+  a.lse = p->lse; a.delta = p->delta; a.delta_w = p->delta;
+  a.fuse_delta = 1;                                  // (the dQ launch forms delta; no separate delta launch in varlen form)
+  a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = nq; a.Nk = nk;
+  a.dv = p->D;
+  a.scale = p->softmax_scale;
+  a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
+  a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;
+  a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
+  const bool causal = p->is_causal != 0, f32 = p->grad_dtype == TFA_F32, wide = p->D > 64, bf16 = p->dtype == TFA_BF16;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  auto run = [&](const tfa::BArgs& m, bool keys, int64_t grid) -> int {
+    if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
+    const hipError_t e = bf16 ? (wide ? tfa::launch_bwd_varlen<__bf16, 128>(m, keys, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_varlen<__bf16, 64>(m, keys, (int)grid, causal, f32, s, dry))
+                              : (wide ? tfa::launch_bwd_varlen<_Float16, 128>(m, keys, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_varlen<_Float16, 64>(m, keys, (int)grid, causal, f32, s, dry));
+    return (int)e;
+  };
+  // dQ (and delta): 256-row resident blocks of each (sequence, query head)
+  tfa::BArgs d = a;
+  d.grad = p->dq; d.gs_b = 0; d.gs_h = st[5][1]; d.gs_n = st[5][2];
+  if (!slice_bytes(nq, d.gs_n, p->D, gsz, &d.g_bytes)) return TFA_ERR_STRIDE;   // (no g_full: its bytes hold cu_q / cu_k)
+  d.nrb = (nq + 255) / 256;
+  // dK and dV in one launch: 32 * KG resident keys of each (sequence, K/V head)
+  tfa::BArgs m = a;
+  m.grad = p->dk; m.gs_b = 0; m.gs_h = st[6][1]; m.gs_n = st[6][2];
+  m.grad2 = p->dv; m.g2s_b = 0; m.g2s_h = st[7][1]; m.g2s_n = st[7][2];
+  if (!slice_bytes(nk, m.gs_n, p->D, gsz, &m.g_bytes) || !slice_bytes(nk, m.g2s_n, p->D, gsz, &m.g2_bytes)) return TFA_ERR_STRIDE;
+  constexpr int kv_keys = 32 * TFA_BWD_KV_KG_OF(false);
+  m.nrb = (nk + kv_keys - 1) / kv_keys;
+  const int st_dq = run(d, false, (int64_t)p->B * p->H * d.nrb);
+  if (st_dq) return st_dq;
+  return run(m, true, (int64_t)p->B * p->Hk * m.nrb);
+}
+
 }  // namespace
 
 extern "C" {
 
 int tfa_bwd(const tfa_bwd_params* p, void* stream) { return run_bwd(p, stream, false); }
 int tfa_bwd_plan(const tfa_bwd_params* p) { return run_bwd(p, nullptr, true); }
+int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, stream, false); }
 int tfa_debug_bwd_split(int on) { g_bwd_split = on & 15; return TFA_OK; }
 long long tfa_bwd_workspace_bytes(const tfa_bwd_params* p) {
   tfa_bwd_params q;

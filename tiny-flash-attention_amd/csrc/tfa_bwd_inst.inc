@@ -8,8 +8,7 @@ template <typename T, int D, int MODE, bool CAUSAL, bool F32OUT, int DVB = D / 3
 static hipError_t launch_bwd_one(const BArgs& a, int grid, hipStream_t stream, bool dry) {
   constexpr bool WIDE256 = D > 128;                // one wave per SIMD, unified images (tfa_bwd_kernel.h)
   constexpr int NW = WIDE256 ? 4 : 8;
-  constexpr int NIMG = (WIDE256 || MODE == BWD_DV) ? 2 : 3;
-  constexpr int lds = 2 * NIMG * 64 * D * 2 + (MODE == BWD_DQ ? 0 : 2 * 512);   // two stages of tile images (+ the stages' row statistics, dK / dV)
+  constexpr int lds = bwd_lds_bytes<D, MODE, WIDE256>();   // two stages of tile images (+ the stages' row statistics, dK / dV): tfa_bwd_launch.h
   constexpr bool CAN_BIG = WIDE256 ? DVB == D / 32 : MODE == BWD_DQ;   // (256 wide: all three modes, in the unit of the full column count)
   if (a.big && !CAN_BIG) return hipErrorInvalidValue;       // (the host never asks: tfa_bwd_api.hip)
   auto kern = bwd_kernel<T, D, MODE, CAUSAL, F32OUT, WIDE256, NW, false, DVB>;
@@ -83,7 +82,7 @@ hipError_t launch_bwd<TFA_T, TFA_D>(const BArgs& a, int mode, int grid, bool cau
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool WS>
 static hipError_t launch_bwd_kv_one(const BArgs& a, int grid, hipStream_t stream, bool dry) {
   constexpr int KG = TFA_BWD_KV_KG_OF(WS);
-  constexpr int lds = 3 * 2 * 64 * D * 2 + (KG == 4 ? 3 : 2) * KG * (32 * 64 * 2) + 3 * 512;   // three stages of (Q, dO) tiles + the P exchange buffers (bwd_kv_kernel: NPX) + the stages' row statistics
+  constexpr int lds = bwd_kv_lds_bytes<D, KG>();   // three stages of (Q, dO) tiles + the P exchange buffers + the stages' row statistics: tfa_bwd_launch.h
   if constexpr (!WS) {
     if (!a.big && a.dv <= D - 32) {                  // the last 32-column block is empty: the instantiation that skips it
       if (dry) return hipSuccess;

@@ -17,6 +17,17 @@
 #define TFA_BWD_KV_KG_OF(WS) ((WS) ? 4 : TFA_BWD_KV_KG)
 
 namespace tfa {
+// dynamic LDS of the backward kernels — ONE formula per kernel for every launcher (fixed-length: tfa_bwd_inst.inc, packed variable-length:
+// tfa_bwd_varlen_inst.inc).  bwd_kernel: two stages of NIMG tile images, plus the stages' row statistics in the key-resident (dK / dV) modes.
+template <int D, int MODE, bool WIDE256>
+constexpr int bwd_lds_bytes() {
+  return 2 * ((WIDE256 || MODE == BWD_DV) ? 2 : 3) * 64 * D * 2 + (MODE == BWD_DQ ? 0 : 2 * 512);
+}
+// bwd_kv_kernel: three stages of (Q, dO) tiles, the P exchange buffers (bwd_kv_kernel: NPX), the stages' row statistics
+template <int D, int KG>
+constexpr int bwd_kv_lds_bytes() {
+  return 3 * 2 * 64 * D * 2 + (KG == 4 ? 3 : 2) * KG * (32 * 64 * 2) + 3 * 512;
+}
 template <typename T, int D>
 hipError_t launch_bwd(const BArgs& a, int mode, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
 // the 256-wide single-gradient kernels by the number of 32-column blocks that can hold valid head-dim columns (5..8)
@@ -28,6 +39,10 @@ hipError_t launch_bwd_kv(const BArgs& a, int grid, bool causal, bool f32out, hip
 // dQ = scale * dS . K from the workspace (tfa_bwd_dq_kernel.h): grid = B * H * ceil(Nq / 256)
 template <typename T, int D>
 hipError_t launch_bwd_dq_ws(const BArgs& a, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
+// packed variable-length batches (tfa_bwd_varlen): keys = false the dQ launch (grid = B * H * ceil(max_seqlen_q / 256)), keys = true the fused dK/dV
+// launch (grid = B * Hk * ceil(max_seqlen_k / 128)); tfa_bwd_inst_varlen_<dtype>_<D>.hip
+template <typename T, int D>
+hipError_t launch_bwd_varlen(const BArgs& a, bool keys, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
 template <typename T, int D>
 hipError_t launch_delta(const void* o, const void* dout, float* delta, const long long* os, const long long* ds, int H, int Nq, long long rows,
                         int dv, hipStream_t stream, bool dry);

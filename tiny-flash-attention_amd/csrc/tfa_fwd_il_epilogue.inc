@@ -16,6 +16,8 @@
     kargs_c* pe_ = (kargs_c*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(pe_));
     kargs_c& pe = *pe_;
+    VarSeq vse{};                                      // VARLEN: the sequence's rows re-read with the arguments; its LSE row is h * total_q + q0 + row
+    if constexpr (VARLEN) vse = varlen_seq(pe, b);
     const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int qi_e = lane_e & 31, hi_e = lane_e >> 5, my_row_e = wave_row0 + qi_e;
     float l_tot = pair_sum((l4[0] + l4[1]) + (l4[2] + l4[3]));
@@ -73,12 +75,14 @@
       // ONE store instruction per wave, always issued (the early requests of a pair's second pass are older than it: the counted vmcnt below relies on the
       // count): through a descriptor of this head's LSE row — rows beyond Nq, the second half-wave and a null pointer are out of its range and dropped
       const float lse = empty ? INFINITY : (mref + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-      auto lse_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(pe.lse + (long long)bh * pe.Nq), 0, pe.lse != nullptr ? (unsigned)pe.Nq * 4u : 0u, 0x00020000);
+      auto lse_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(VARLEN ? pe.lse + ((long long)h * pe.total_q + vse.q0) : pe.lse + (long long)bh * pe.Nq), 0,
+                                                      pe.lse != nullptr ? (unsigned)(VARLEN ? vse.nq : pe.Nq) * 4u : 0u, 0x00020000);
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lse), lse_rs, hi_e == 0 ? my_row_e * 4 : (int)TFA_OOB, 0, 0);
     } else
-    if (pe.lse != nullptr && hi_e == 0 && my_row_e < pe.Nq) {
+    if (pe.lse != nullptr && hi_e == 0 && my_row_e < (VARLEN ? vse.nq : pe.Nq)) {
       const float lse = empty ? INFINITY : (mref + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-      pe.lse[(long long)bh * pe.Nq + my_row_e] = lse;
+      if constexpr (VARLEN) pe.lse[(long long)h * pe.total_q + vse.q0 + my_row_e] = lse;
+      else pe.lse[(long long)bh * pe.Nq + my_row_e] = lse;
     }
     if (PREF2 && more_passes && !early_done) {
       // behind the LSE store, in front of the O stores: exactly NST_EPI vector-memory instructions follow these requests
@@ -87,8 +91,8 @@
       asm volatile("" ::: "memory");
     }
     if (F32OUT) {
-      float* obase = reinterpret_cast<float*>(pe.o) + b * pe.os_b + h * pe.os_h;
-      auto o_rs = slice_rsrc(obase, pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 4ull);
+      float* obase = reinterpret_cast<float*>(pe.o) + (VARLEN ? (long long)vse.q0 * pe.os_n : b * pe.os_b) + h * pe.os_h;
+      auto o_rs = slice_rsrc(obase, VARLEN ? varlen_bytes(vse.nq, pe.os_n, pe.dv, 4) : pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 4ull);
       const int ooff = (my_row_e - (WIN ? q0 : 0)) * (int)pe.os_n * 4 + hi_e * 16;
       // (PREF2's counted wait below relies on EXACTLY NST_EPI vector-memory instructions behind the next pass's requests: every store is issued —
       //  chunks beyond dv and rows beyond Nq go out of range, never skipped — and the trip counts are pinned to the constant here)
@@ -108,8 +112,8 @@
       // stores per lane, 32 different rows per instruction.  Instead the wave transposes its 32 x D tile through its own
       // slice of the epilogue region (16-byte chunk index XOR row, as for K) and writes whole rows: 1 KiB contiguous per
       // store instruction.  The region is separate from the tile buffers (which the next pass is already filling).
-      T* obase = reinterpret_cast<T*>(pe.o) + b * pe.os_b + h * pe.os_h;
-      auto o_rs = slice_rsrc(obase, pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 2ull);
+      T* obase = reinterpret_cast<T*>(pe.o) + (VARLEN ? (long long)vse.q0 * pe.os_n : b * pe.os_b) + h * pe.os_h;
+      auto o_rs = slice_rsrc(obase, VARLEN ? varlen_bytes(vse.nq, pe.os_n, pe.dv, 2) : pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 2ull);
       typedef __attribute__((ext_vector_type(4))) T t4;
       // (the lane ids go through an empty asm so that none of the 24 addresses below is loop-invariant: hoisted out of
       // the pass loop they would stay live across the main loop and spill)
@@ -148,8 +152,8 @@
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slice is rewritten by this wave's next epilogue only
       }
     } else {
-      T* obase = reinterpret_cast<T*>(pe.o) + b * pe.os_b + h * pe.os_h;
-      auto o_rs = slice_rsrc(obase, pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 2ull);
+      T* obase = reinterpret_cast<T*>(pe.o) + (VARLEN ? (long long)vse.q0 * pe.os_n : b * pe.os_b) + h * pe.os_h;
+      auto o_rs = slice_rsrc(obase, VARLEN ? varlen_bytes(vse.nq, pe.os_n, pe.dv, 2) : pe.o_bytes, (unsigned long long)q0 * (unsigned long long)pe.os_n * 2ull);
       const int ooff = (my_row_e - (WIN ? q0 : 0)) * (int)pe.os_n * 2 + hi_e * 8;
       typedef __attribute__((ext_vector_type(4))) T t4;
       static_assert(F32OUT || EPI || NST_EPI == DT * 4, "NST_EPI must equal the direct 16-bit epilogue's store count");

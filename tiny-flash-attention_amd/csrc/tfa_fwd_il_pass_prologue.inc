@@ -46,7 +46,7 @@
     int fm = nact;
     {
       int first_g = 0x3fffffff;                            // first tile OF THE HEAD that needs a mask for this wave
-      if (p.Nk % BN) first_g = p.Nk / BN;
+      if (IL_NK % BN) first_g = IL_NK / BN;
       if (CAUSAL) {
         const int c = pos_lo + shift + 1;                  // keys 0..c-1 are visible to every row of the wave
         const int full = c > 0 ? c / BN : 0;               // tiles 0..full-1 need no mask

@@ -135,7 +135,7 @@
     constexpr bool ASMLOOPX = ASMBASE && EXACT;        // the exact-running-max loop (variant 38): four bodies — parity x {plain, also re-basing O}
     // (the loop's LDS-DMA requests carry the tile's byte offset as their SCALAR offset, which the descriptor's bounds check does not see: it only asks for
     //  tiles that lie wholly inside the key sequence — K(j+2) with j + 2 < nt_full; a ragged last tile is requested by the compiler-scheduled bodies)
-    const int nt_full = own_tiles(p.Nk / BN) < nt ? own_tiles(p.Nk / BN) : nt;     // (key-split kernels: in the wave group's own tile numbering)
+    const int nt_full = own_tiles(IL_NK / BN) < nt ? own_tiles(IL_NK / BN) : nt;     // (key-split kernels: in the wave group's own tile numbering)
     // ---- the bodies BEHIND the loop by hand as well (round 6): per wave and pass hipcc still scheduled the tile in front of the masked one, the masked tile and the
     // last one — on the causal diagonal, where half of the block's waves have already stopped, those iterations ran SLOWER than a steady-state one
     // (3000-3160 cycles against 2600, profiles/r06_trace_diag.txt).  The lazy-reference statement now carries them (dispatch + pinned / masked / last-tile body

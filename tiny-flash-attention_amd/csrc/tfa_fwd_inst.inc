@@ -30,7 +30,7 @@ template <typename T, int D, int NW, int VF, bool CAUSAL, bool F32OUT, int DVB =
 static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* geom, bool dry) {
   // (+ 16 bytes + one float per query row: the max-free instantiations' "redo this pass" word and the seeds of a redone pass behind everything else,
   //  tfa_fwd_kernel_il.h: REDO_OFF, SEED_OFF)
-  constexpr int lds = ((VF & VF_IL_KSPLIT) ? 8 : 4) * 64 * D * 2 + (((VF & VF_IL_EPI) && !(VF & VF_IL_EPI_INPLACE)) ? NW * 32 * D * 2 : 0) + 16 + NW * 32 * 4;
+  constexpr int lds = il_lds_bytes<D, NW, VF>();
   auto kern = fwd_kernel_il<T, D, NW, CAUSAL, F32OUT, VF, AB, DVB>;
   static std::atomic<unsigned long long> attr_mask{0};
   return launch_common(kern, attr_mask, a.nbh * a.nwork, NW * 64, lds, a, stream, geom, dry);

@@ -1,0 +1,5 @@
+// one packed variable-length instantiation unit: dtype=bf16 head_dim=128 causal=0
+#define TFA_T __bf16
+#define TFA_D 128
+#define TFA_CAUSAL false
+#include "tfa_fwd_varlen_inst.inc"

@@ -62,9 +62,26 @@ struct KArgs {
   int B, H, Hk, Nq, Nk;
   int shift;        // causal: key j of THIS K/V tensor is visible to row i iff j <= i + shift
                     // (= Nk - Nq bottom-right aligned; less the chunk offset when K/V is a chunk of a longer sequence)
-  int nsplit;       // split-KV in one launch (tfa_fwd_splitkv; LDS-DMA kernel only): number of key chunks, 0/1 = none
-  int chunk;        // keys per chunk (multiple of 64)
-  long long o_part_stride, lse_part_stride;   // elements between the partial results of consecutive chunks
+  // (the split-KV fields share their bytes with those of packed variable-length batches — no launch is both — so that every existing kernel keeps its
+  //  argument layout: tfa_fwd_varlen, the VF_IL_VARLEN instantiations, read the second member of each union)
+  union {
+    struct {
+      int nsplit;   // split-KV in one launch (tfa_fwd_splitkv; LDS-DMA kernel only): number of key chunks, 0/1 = none
+      int chunk;    // keys per chunk (multiple of 64)
+    };
+    struct {
+      int total_q, total_k;   // varlen: rows of the packed tensors — every sequence bound read from cu_q / cu_k is clamped into them
+    };
+  };
+  union {
+    struct {
+      long long o_part_stride, lse_part_stride;   // elements between the partial results of consecutive chunks
+    };
+    struct {
+      const int* cu_q;   // varlen: sequence b is rows [cu_q[b], cu_q[b+1]) of q / out and [cu_k[b], cu_k[b+1]) of k / v (device int32, B + 1 entries);
+      const int* cu_k;   // B is then the sequence count and Nq / Nk = max_seqlen_q / _k: a sequence of that many rows sizes nmb, nwork and *_bytes (the grid)
+    };
+  };
   int nmb;          // number of query blocks per (b,h)
   int nwork;        // work items per (b,h): nmb, or ceil(nmb/2) when causal blocks are paired
   int nbh;          // B*H
@@ -97,6 +114,34 @@ struct KArgs {
   int kv_stream;    // K and V together reach 768 MiB — a cache the 256 MB memory-side cache cannot keep until the next call: decode
                     // kernels whose K/V tiles no other workgroup reads may stream them with the non-temporal hint (set by the host)
 };
+
+// One sequence of a packed variable-length batch, read on the device (scalar loads: b is uniform) — the host never reads cu_seqlens.  The bounds are clamped
+// into the packed tensors and the lengths to the host's max_seqlen (the arguments' Nq / Nk), so a bad cu_seqlens can misplace rows but never address outside
+// the tensors or a grid sized from max_seqlen.  A: KArgs or BArgs (same field names), in any address space.
+struct VarSeq {
+  int q0, nq, k0, nk;
+};
+template <typename A>
+static __device__ __forceinline__ VarSeq varlen_seq(const A& a, int b) {
+  typedef __attribute__((address_space(4))) const int cint4;
+  const cint4* cq = (const cint4*)(uintptr_t)a.cu_q;
+  const cint4* ck = (const cint4*)(uintptr_t)a.cu_k;
+  VarSeq s;
+  int q0 = cq[b], q1 = cq[b + 1], k0 = ck[b], k1 = ck[b + 1];
+  q0 = q0 < 0 ? 0 : (q0 > a.total_q ? a.total_q : q0);
+  q1 = q1 < q0 ? q0 : (q1 > a.total_q ? a.total_q : q1);
+  k0 = k0 < 0 ? 0 : (k0 > a.total_k ? a.total_k : k0);
+  k1 = k1 < k0 ? k0 : (k1 > a.total_k ? a.total_k : k1);
+  s.q0 = q0;
+  s.nq = q1 - q0 < a.Nq ? q1 - q0 : a.Nq;
+  s.k0 = k0;
+  s.nk = k1 - k0 < a.Nk ? k1 - k0 : a.Nk;
+  return s;
+}
+// extent in bytes of n rows at row stride `stride` elements, dv valid elements of esize bytes each (0 rows: an empty descriptor)
+static __device__ __forceinline__ unsigned long long varlen_bytes(int n, long long stride, int dv, int esize) {
+  return n > 0 ? (unsigned long long)(((long long)(n - 1) * stride + dv) * esize) : 0ull;
+}
 
 template <typename T> struct Elem;
 template <> struct Elem<__bf16> {

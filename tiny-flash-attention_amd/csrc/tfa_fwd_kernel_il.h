@@ -66,6 +66,9 @@ constexpr int VF_IL_EXACT = 1 << 30;     // the reference's rounding points (TFA
                                          // that also multiplies O by exp2(old - new): 64 v_mul, four behind each QK^T MFMA (round 5)
 constexpr int VF_IL_DMASTAGGER = 131072; // with DMASPREAD: the upper half of the waves issues its pieces behind the first PV MFMAs,
                                          // so the two waves of a SIMD never sit in an LDS-DMA issue stall at the same time
+constexpr int VF_IL_VARLEN = 1 << 23;    // packed variable-length batches (tfa_fwd_varlen): b indexes a sequence of KArgs::cu_q / cu_k, read by the work item itself
+                                         // (varlen_seq); its lengths, causal shift, block count, base rows and slice extents replace the launch's.  Nothing inside the
+                                         // tile loop changes.  (The bit is VF_X4_EPI of the x4 kernel: each kernel reads only its own flags)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -261,15 +264,28 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   }
   __builtin_assume(b >= 0 && h >= 0 && hk >= 0);     // (64-bit stride products without the sign terms)
   TP_STAMP(1, bh + wi + hk);                           // work item decoded
-  const int shift = p.shift;
+  // VARLEN: b is a sequence.  The grid was sized for max_seqlen_q: a work item beyond this sequence's query blocks leaves at once; the sequence's own
+  // lengths, shift and block count stand in for the launch's wherever the kernel reads them (the per-pass code re-reads the bounds, as it re-reads its kernargs)
+  constexpr bool VARLEN = (VF & VF_IL_VARLEN) != 0;
+  static_assert(!VARLEN || (!(VF & (VF_IL_KSPLIT | VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_EXACT | VF_IL_SEAM | VF_IL_PREF)) && !TFA_IL_USE_EARLY),
+                "varlen: the il8 / il4 main instantiations only");
+  VarSeq vsq{};
+  if constexpr (VARLEN) {
+    vsq = varlen_seq(p, b);
+    const int nmb_s = (vsq.nq + BM - 1) / BM;
+    if (wi >= (PAIR ? (nmb_s + 1) >> 1 : nmb_s)) return;
+  }
+  const int shift = VARLEN ? vsq.nk - vsq.nq : p.shift;
+  const int nmb_x = VARLEN ? (vsq.nq + BM - 1) / BM : p.nmb;
+#define IL_NK (VARLEN ? vsq.nk : p.Nk)
 
-  const T* qbase = reinterpret_cast<const T*>(p.q) + b * p.qs_b + h * p.qs_h;
-  const T* kbase = reinterpret_cast<const T*>(p.k) + b * p.ks_b + hk * p.ks_h;
-  const T* vbase = reinterpret_cast<const T*>(p.v) + b * p.vs_b + hk * p.vs_h;
+  const T* qbase = reinterpret_cast<const T*>(p.q) + (VARLEN ? (long long)vsq.q0 * p.qs_n : b * p.qs_b) + h * p.qs_h;
+  const T* kbase = reinterpret_cast<const T*>(p.k) + (VARLEN ? (long long)vsq.k0 * p.ks_n : b * p.ks_b) + hk * p.ks_h;
+  const T* vbase = reinterpret_cast<const T*>(p.v) + (VARLEN ? (long long)vsq.k0 * p.vs_n : b * p.vs_b) + hk * p.vs_h;
   // Q/O: one descriptor per query block (rsrc_at, once per pass).  K/V: one per slice, or — VF_IL_WINDOWED — one per tile.
   constexpr bool WIN = (VF & VF_IL_WINDOWED) != 0;
   // KSPLIT: group g sees the key sequence through a strided view — its tile j is tile 2j+g of the head
-  unsigned long long k_bytes = p.k_bytes, v_bytes = p.v_bytes;
+  unsigned long long k_bytes = VARLEN ? varlen_bytes(vsq.nk, p.ks_n, p.dv, 2) : p.k_bytes, v_bytes = VARLEN ? varlen_bytes(vsq.nk, p.vs_n, p.dv, 2) : p.v_bytes;
   if (KSPLIT) {
     const unsigned long long ko = (unsigned long long)grp * BN * p.ks_n * 2, vo = (unsigned long long)grp * BN * p.vs_n * 2;
     kbase += grp * BN * p.ks_n;
@@ -343,7 +359,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   asm volatile("" ::"v"(k_src[0]), "v"(v_src[PPW - 1]));
 #endif
   TP_STAMP(3, wi);                                     // lane offsets of the DMA pieces (in front of the first request)
-  const int npass = PAIR ? ((p.nmb - 1 - wi) != wi ? 2 : 1) : 1;
+  const int npass = PAIR ? ((nmb_x - 1 - wi) != wi ? 2 : 1) : 1;
   constexpr bool EPI = (VF & VF_IL_EPI) != 0;
   constexpr bool PREF2 = PAIR && (VF & VF_IL_PREF2) != 0;
   constexpr bool QLDS = (VF & VF_IL_QLDS) != 0;
@@ -379,8 +395,8 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   auto own_tiles = [&](int ntg) -> int { return KSPLIT ? (ntg - grp + 1) >> 1 : ntg; };   // this wave's share of ntg tiles of the head
   auto key0_of = [&](int t) -> int { return (KSTEP * t + grp) * BN; };                        // first key of the wave's tile t
   auto block_of = [&](int pass) -> int {
-    if (PAIR) return pass == 0 ? (p.nmb - 1 - wi) : wi;
-    return CAUSAL ? (p.nmb - 1 - wi) : wi;
+    if (PAIR) return pass == 0 ? (nmb_x - 1 - wi) : wi;
+    return CAUSAL ? (nmb_x - 1 - wi) : wi;
   };
   // requests for the start of query block mbx: K(0), V(0), K(1) by LDS-DMA and this lane's Q fragments
   // (round 6: what the per-pass code needs of the kernel arguments is read again from the kernarg segment through a laundered pointer — see the epilogue)
@@ -392,8 +408,10 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   };
   auto issue_prologue = [&](int mbx, bool with_dma) {
     kargs_c& p = *fresh_args();                        // (shadows the kernel's `p` inside this lambda on purpose)
+    VarSeq vx{};                                       // (VARLEN: the sequence's bounds re-read with the arguments)
+    if constexpr (VARLEN) vx = varlen_seq(p, b);
     const int q0x = mbx * BM;
-    int kve = p.Nk;
+    int kve = VARLEN ? vx.nk : p.Nk;
     if (CAUSAL) {
       const int lim = (((VF & VF_IL_IDLE) && p.row_mod > 0) ? p.row_mod : q0x + BM) + shift;
       kve = lim < kve ? lim : kve;
@@ -404,7 +422,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     int one = 1;                                       // (opaque: K(1)'s source offsets are otherwise shared with the first prologue's and live across the tile loop)
     asm volatile("" : "+s"(one));
     if (with_dma && ntx > 1) dma_k(one, 1);
-    auto q_rs = slice_rsrc(qbase, p.q_bytes, (unsigned long long)q0x * (unsigned long long)p.qs_n * 2ull);
+    auto q_rs = slice_rsrc(qbase, VARLEN ? varlen_bytes(vx.nq, p.qs_n, p.dv, 2) : p.q_bytes, (unsigned long long)q0x * (unsigned long long)p.qs_n * 2ull);
     // (the half-wave index goes through an empty asm: otherwise hipcc hoists the eight per-k-slot offsets out of the pass loop, where they stay live
     //  across the tile loop — eight registers the loop does not have, round 5 — and the lane id is re-derived with v_mbcnt instead of kept from the start)
     const int lane_p = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // (the lane id re-derived, like the epilogue does)
@@ -446,7 +464,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   const unsigned q_slice = lds_base + 4 * TILE_BYTES + wave * (32 * D * 2);
   auto issue_q_dma = [&](int mbx) {
     constexpr int RPP = 1024 / (D * 2);                // rows per 1 KiB piece
-    auto q_rs = slice_rsrc(qbase, p.q_bytes, 0ull);
+    auto q_rs = slice_rsrc(qbase, VARLEN ? varlen_bytes(vsq.nq, p.qs_n, p.dv, 2) : p.q_bytes, 0ull);
     const int r0 = __builtin_amdgcn_readfirstlane(mbx * BM + wave * 32);   // (uniform on purpose: hipcc otherwise carries it in a VGPR into the pass loop)
 #pragma unroll
     for (int i = 0; i < 32 / RPP; ++i) {
@@ -469,7 +487,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   int first_late = 0;                                  // 0: nothing issued behind Q, 1: V(0), 2: V(0) and K(1)
   auto issue_first = [&](int mbx) {
     const int q0x = mbx * BM;
-    int kve = p.Nk;
+    int kve = IL_NK;
     if (CAUSAL) { const int lim = q0x + BM + shift; kve = lim < kve ? lim : kve; }
     const int ntx = kve > 0 ? (kve + BN - 1) / BN : 0;
     if (ntx > 0) dma_k(0, 0);
@@ -523,7 +541,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     // query POSITIONS of the wave's rows (for the causal mask): rows themselves, or — packed GQA heads, decode instantiation
     // only — row % row_mod, in which case a wave's rows span every position 0 .. row_mod-1
     const int rmod = ((VF & VF_IL_IDLE) && CAUSAL) ? p.row_mod : 0;
-    int kv_end = p.Nk;
+    int kv_end = IL_NK;
     if (CAUSAL) {
       const int lim = (rmod > 0 ? rmod : q0 + BM) + shift;
       kv_end = lim < kv_end ? lim : kv_end;
@@ -562,12 +580,12 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     };
     auto needs_mask = [&](int t) -> bool {
       const int key0 = key0_of(t);
-      bool nm = (key0 + BN > p.Nk);
+      bool nm = (key0 + BN > IL_NK);
       if (CAUSAL) nm = nm || (key0 + BN - 1 > pos_lo + shift);
       return nm;
     };
     auto apply_mask = [&](int t, f32x16 (&s)[2]) {
-      int lim = p.Nk - 1;
+      int lim = IL_NK - 1;
       if (CAUSAL) { const int c = my_pos + shift; lim = c < lim ? c : lim; }
       lim -= key0_of(t) + 4 * hi;
 #pragma unroll
@@ -753,6 +771,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
 }
 
 #undef KT
+#undef IL_NK
 #undef P_TRACE
 #undef TP_STAMP
 #undef KS

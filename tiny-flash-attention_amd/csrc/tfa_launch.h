@@ -109,6 +109,14 @@ struct LaunchGeom {
   int grid, block, lds;
 };
 
+// dynamic LDS of an il kernel (fwd_kernel_il, tfa_fwd_kernel_il.h): the K / V tile buffers (KSPLIT: one ring per wave group), the separate epilogue region
+// (EPI without EPI_INPLACE), then the max-free instantiations' "redo this pass" word and one seed float per query row (REDO_OFF, SEED_OFF).  ONE formula
+// for every launcher of the kernel — fixed-length (tfa_fwd_inst.inc) and packed variable-length (tfa_fwd_varlen_inst.inc)
+template <int D, int NW, int VF>
+constexpr int il_lds_bytes() {
+  return ((VF & VF_IL_KSPLIT) ? 8 : 4) * 64 * D * 2 + (((VF & VF_IL_EPI) && !(VF & VF_IL_EPI_INPLACE)) ? NW * 32 * D * 2 : 0) + 16 + NW * 32 * 4;
+}
+
 // one translation unit per (dtype, width, causal): tfa_fwd_inst_<dtype>_<D>_c<0|1>.hip specialises launch_fwd_c
 template <typename T, int D, bool CAUSAL>
 hipError_t launch_fwd_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
@@ -120,6 +128,18 @@ TFA_FWD_UNITS(__bf16, 64) TFA_FWD_UNITS(__bf16, 128) TFA_FWD_UNITS(_Float16, 64)
 template <typename T, int D>
 static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
   return causal ? launch_fwd_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_c<T, D, false>(a, f32out, variant, stream, geom, dry);
+}
+// the packed variable-length form (VF_IL_VARLEN) of variants 30 and 32: one translation unit per (dtype, width, causal), tfa_fwd_inst_varlen_*.hip
+template <typename T, int D, bool CAUSAL>
+hipError_t launch_fwd_varlen_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_FWD_VARLEN_UNITS(T, D)                                                                             \
+  template <> hipError_t launch_fwd_varlen_c<T, D, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
+  template <> hipError_t launch_fwd_varlen_c<T, D, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
+TFA_FWD_VARLEN_UNITS(__bf16, 64) TFA_FWD_VARLEN_UNITS(__bf16, 128) TFA_FWD_VARLEN_UNITS(_Float16, 64) TFA_FWD_VARLEN_UNITS(_Float16, 128)
+#undef TFA_FWD_VARLEN_UNITS
+template <typename T, int D>
+static inline hipError_t launch_fwd_varlen(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
+  return causal ? launch_fwd_varlen_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_varlen_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
 
 // common tail of every launcher: report the geometry, opt in to the dynamic LDS size on this device, launch, and return

@@ -356,3 +356,158 @@ def flash_attn_func(q, k, v, causal=False, softmax_scale=None):
         return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale)
     out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# packed variable-length batches: the cu_seqlens form of FlashAttention-2's flash_attn_varlen_func (tfa_fwd_varlen / tfa_bwd_varlen)
+# ---------------------------------------------------------------------------------------------
+
+def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, extra=()):
+    """Host-side checks of a packed call — everything that needs no device read (cu_seqlens itself is only read by the kernels).
+    Returns B (the sequence count)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")) + tuple(extra):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise RuntimeError(f"{n} must be a 3-D tensor (total rows, heads, head dim)")
+        if t.stride(2) != 1:
+            raise RuntimeError(f"{n} must have unit stride along the head dimension")
+    if q.dtype == torch.float32:
+        raise TypeError("packed variable-length attention: float16 or bfloat16 only (no fp32 varlen path)")
+    if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"q,k,v must share dtype float16 or bfloat16 (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if k.shape != v.shape or k.shape[2] != q.shape[2]:
+        raise RuntimeError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    if q.shape[1] % k.shape[1] != 0:
+        raise RuntimeError(f"the query heads ({q.shape[1]}) must be a multiple of the K/V heads ({k.shape[1]})")
+    for t, n in ((cu_seqlens_q, "cu_seqlens_q"), (cu_seqlens_k, "cu_seqlens_k")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{n} must be a tensor")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{n} must be int32 (got {t.dtype})")
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() < 2:
+            raise RuntimeError(f"{n} must be a contiguous 1-D tensor of B + 1 >= 2 entries")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+        raise RuntimeError(f"cu_seqlens_q and cu_seqlens_k must both hold B + 1 entries ({cu_seqlens_q.numel()} vs {cu_seqlens_k.numel()})")
+    for m, n in ((max_seqlen_q, "max_seqlen_q"), (max_seqlen_k, "max_seqlen_k")):
+        if isinstance(m, torch.Tensor) or isinstance(m, bool) or int(m) != m or int(m) <= 0:
+            raise RuntimeError(f"{n} must be a positive host integer (got {m!r})")
+    for t, n in ((q, "q"), (k, "k"), (v, "v")) + tuple(extra) + ((cu_seqlens_q, "cu_seqlens_q"), (cu_seqlens_k, "cu_seqlens_k")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+        if t.device != q.device:
+            raise RuntimeError(f"{n} must be on q's device")
+    return cu_seqlens_q.numel() - 1
+
+
+def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
+                          out_f32=False, return_lse=True, out=None):
+    """Packed variable-length forward (tfa_fwd_varlen, include/tfa.h): q (total_q, H, D), k / v (total_k, Hk, D), sequence b is rows
+    [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v (device int32, B + 1 entries, never read on the host).
+    Causal masking per sequence, bottom-right aligned.  Returns ``(out, lse)``: ``out`` shaped like q (fp32 when ``out_f32``), ``lse`` fp32 (H, total_q).
+    Rows outside every sequence are not written (a caller-provided ``out`` keeps them)."""
+    _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    B = cu_seqlens_q.numel() - 1
+    total_q, H, D = q.shape
+    total_k, Hk, _ = k.shape
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.shape != q.shape or out.device != q.device:
+            raise RuntimeError(f"out must be a tensor shaped like q {tuple(q.shape)} on q's device")
+        if out.dtype not in (q.dtype, torch.float32):
+            raise RuntimeError(f"out must be {q.dtype} or float32 (got {out.dtype})")
+        if out.stride(2) != 1:
+            raise RuntimeError("out must have unit stride along the head dimension")
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    p = _lib.TfaVarlenFwdParams()
+    p.q, p.k, p.v, p.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.cu_seqlens_q, p.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
+    p.B, p.H, p.Hk, p.D = B, H, Hk, D
+    p.max_seqlen_q, p.max_seqlen_k, p.total_q, p.total_k = int(max_seqlen_q), int(max_seqlen_k), total_q, total_k
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
+        arr = getattr(p, name)
+        arr[0], arr[1] = t.stride(1), t.stride(0)
+    p.softmax_scale = float(softmax_scale)
+    p.is_causal = 1 if is_causal else 0
+    p.dtype = _DT[q.dtype]
+    p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().tfa_fwd_varlen(C.byref(p), C.c_void_p(stream)))
+    return out, lse
+
+
+def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
+                          grad_f32=False):
+    """Backward of ``flash_attn_varlen_fwd`` (tfa_bwd_varlen): returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``); for GQA dk / dv
+    are summed over the query heads of each K/V head within each sequence.  Rows outside every sequence get zero gradients: the kernels never write
+    them, so the three results are allocated zeroed (one memset of dq, dk and dv per call)."""
+    _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, extra=((out, "out"), (dout, "dout")))
+    if out.shape != q.shape or dout.shape != q.shape or out.dtype != q.dtype or dout.dtype != q.dtype:
+        raise RuntimeError("out and dout must be shaped like q, in q's dtype")
+    B = cu_seqlens_q.numel() - 1
+    total_q, H, D = q.shape
+    total_k, Hk, _ = k.shape
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    if not isinstance(lse, torch.Tensor) or not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or tuple(lse.shape) != (H, total_q):
+        raise RuntimeError(f"lse must be the forward's float32 {(H, total_q)} tensor on q's device")
+    lse = lse.contiguous()
+    gdt = torch.float32 if grad_f32 else q.dtype
+    dq = torch.zeros(q.shape, dtype=gdt, device=q.device)
+    dk = torch.zeros(k.shape, dtype=gdt, device=q.device)
+    dv = torch.zeros(v.shape, dtype=gdt, device=q.device)
+    delta = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
+    p = _lib.TfaVarlenBwdParams()
+    p.q, p.k, p.v, p.out, p.dout = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr()
+    p.lse, p.delta = lse.data_ptr(), delta.data_ptr()
+    p.dq, p.dk, p.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    p.cu_seqlens_q, p.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
+    p.B, p.H, p.Hk, p.D = B, H, Hk, D
+    p.max_seqlen_q, p.max_seqlen_k, p.total_q, p.total_k = int(max_seqlen_q), int(max_seqlen_k), total_q, total_k
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out), ("do_stride", dout),
+                    ("dq_stride", dq), ("dk_stride", dk), ("dv_stride", dv)):
+        arr = getattr(p, name)
+        arr[0], arr[1] = t.stride(1), t.stride(0)
+    p.softmax_scale = float(softmax_scale)
+    p.is_causal = 1 if is_causal else 0
+    p.dtype = _DT[q.dtype]
+    p.grad_dtype = _lib.TFA_F32 if grad_f32 else _DT[q.dtype]
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().tfa_bwd_varlen(C.byref(p), C.c_void_p(stream)))
+    return dq, dk, dv
+
+
+class _FlashAttnVarlen(torch.autograd.Function):
+    """autograd glue for ``flash_attn_varlen_func``: forward = tfa_fwd_varlen, backward = tfa_bwd_varlen."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale):
+        out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+        ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, causal, scale = ctx.args
+        if dout.stride(2) != 1:
+            dout = dout.contiguous()
+        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False):
+    """Packed variable-length attention with FlashAttention-2's positional signature (flash_attn_varlen_func): q (total_q, H, D), k / v
+    (total_k, Hk, D), cu_seqlens_q / _k device int32 (B + 1), max_seqlen_q / _k host integers.  Differentiable: when an input requires grad the
+    backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0)."""
+    if dropout_p != 0.0:
+        raise NotImplementedError("flash_attn_varlen_func: dropout is not supported (dropout_p must be 0)")
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale)
+    out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False)
+    return out
