@@ -361,7 +361,7 @@ int tfa_fwd_work(const tfa_fwd_params* p, double* flops, double* bytes);
  * narrow twins at those head dims).
  * The backward runs its dQ launch (which also forms delta) and its fused dK/dV launch in varlen form.
  * Out of scope (refused): head dims above 128 (TFA_ERR_HEAD_DIM), fp32 inputs (TFA_ERR_DTYPE), TFA_FWD_EXACT_MAX and any other flag (flags must be 0:
- * TFA_ERR_SHAPE), split-KV, paged K/V, GQA decode row packing, the backward's dS-workspace form, sliding windows, dropout, and sequences whose
+ * TFA_ERR_SHAPE), split-KV, paged K/V, GQA decode row packing, the backward's dS-workspace form, dropout (sliding windows: tfa_fwd_varlen_local below), and sequences whose
  * max_seqlen rows would not fit one buffer descriptor (TFA_ERR_STRIDE: no windowed varlen form).  A NULL cu_seqlens is TFA_ERR_NULL;
  * B, H, Hk, max_seqlen or total <= 0 or H % Hk != 0 is TFA_ERR_SHAPE.
  * Measured: profiles/varlen_bench.txt (tools/bench_varlen.py; equal lengths at the speed of tfa_fwd / tfa_bwd, mixed lengths against padding and
@@ -431,6 +431,37 @@ int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p);
 int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p);
 /* Launch the packed backward on `stream` (asynchronous): the dQ launch (it writes delta), then the fused dK/dV launch.  Deterministic. */
 int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream);
+
+/* ---- local (sliding-window) attention (FlashAttention-2's window_size = (left, right)) ---------------------------------------------------
+ * The same params structs as tfa_fwd / tfa_bwd / tfa_fwd_varlen / tfa_bwd_varlen plus the window: with shift = Nk - Nq per sequence (bottom-right
+ * aligned, as is_causal), key j is visible to query row i iff  i + shift - window_left <= j <= i + shift + window_right.  -1 = unbounded on that side;
+ * is_causal = 1 forces window_right = 0.  A side that reaches every key of every row is unbounded (left >= Nk - 1, right >= Nq - 1; max_seqlen for
+ * varlen).  (-1, -1) and (-1, 0) then run exactly what tfa_fwd / tfa_bwd (and the varlen forms) run with is_causal = 0 / 1: same kernels, same bits.
+ * Rows that see no key get out = 0 and lse = +inf; dk / dv of keys that no row sees are 0; GQA sums as in tfa_bwd.
+ * Any other window runs the LOCAL instantiations: the il8 (variant 30) or il4 (32) forward — il8 where tfa_fwd would pick it, il4 for everything else
+ * (split-KV, decode row packing and the key-split kernels have no local form) — without causal pairing, visiting only the key tiles that meet its rows'
+ * windows; rounding rule TFA_RULE_LAZY (bf16 included).  Full width only: head dims below the kernel's width read the missing columns as zeros.  The
+ * backward runs its dQ launch (which forms delta) and its fused dK/dV launch, each visiting only the tiles inside the window, deterministic; never the
+ * dS-workspace form (tfa_bwd_params::workspace is ignored).
+ * Refused for a true window: head dims above 128 (TFA_ERR_HEAD_DIM), fp32 inputs (TFA_ERR_DTYPE), any flag — TFA_FWD_EXACT_MAX included — (TFA_ERR_SHAPE),
+ * a side below -1 (TFA_ERR_SHAPE, for every window), kv_offset / nk_total != 0 (TFA_ERR_SHAPE), Nq + Nk >= 2^28 (TFA_ERR_SHAPE), slices that need
+ * per-tile descriptors (TFA_ERR_STRIDE), a forced variant other than 30 / 32 (TFA_ERR_VARIANT).
+ * Measured: profiles/window_bench.txt (tools/bench_window.py), quoted in README.md and INTEGRATION.md. */
+int tfa_fwd_local(const tfa_fwd_params* p, int window_left, int window_right, void* stream);
+int tfa_fwd_local_plan(const tfa_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes);
+/* The kernel variant tfa_fwd_local runs for *p (tfa_fwd_variant's answer for (-1, -1) / (-1, 0)), or a negative TFA_ERR_* code. */
+int tfa_fwd_local_variant(const tfa_fwd_params* p, int window_left, int window_right);
+/* The row reference P is rounded against (TFA_RULE_*): TFA_RULE_LAZY for a true window, tfa_fwd_rounding_rule's answer otherwise. */
+int tfa_fwd_local_rounding_rule(const tfa_fwd_params* p, int window_left, int window_right);
+int tfa_fwd_varlen_local(const tfa_varlen_fwd_params* p, int window_left, int window_right, void* stream);
+int tfa_fwd_varlen_local_plan(const tfa_varlen_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_varlen_local_variant(const tfa_varlen_fwd_params* p, int window_left, int window_right);
+int tfa_fwd_varlen_local_rounding_rule(const tfa_varlen_fwd_params* p, int window_left, int window_right);
+/* The backward of a local forward (same window, same params as tfa_bwd / tfa_bwd_varlen); _plan validates without launching. */
+int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, void* stream);
+int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right);
+int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int window_right, void* stream);
+int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right);
 
 #ifdef __cplusplus
 }

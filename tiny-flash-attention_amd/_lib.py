@@ -44,6 +44,18 @@ SYMBOLS = (
     "tfa_fwd_varlen_variant",
     "tfa_fwd_varlen_rounding_rule",
     "tfa_bwd_varlen",
+    "tfa_fwd_local",
+    "tfa_fwd_local_plan",
+    "tfa_fwd_local_variant",
+    "tfa_fwd_local_rounding_rule",
+    "tfa_fwd_varlen_local",
+    "tfa_fwd_varlen_local_plan",
+    "tfa_fwd_varlen_local_variant",
+    "tfa_fwd_varlen_local_rounding_rule",
+    "tfa_bwd_local",
+    "tfa_bwd_local_plan",
+    "tfa_bwd_varlen_local",
+    "tfa_bwd_varlen_local_plan",
 )
 
 
@@ -273,6 +285,18 @@ def lib():
     L.tfa_fwd_varlen_rounding_rule.argtypes = [PV]
     L.tfa_bwd_varlen.restype = C.c_int
     L.tfa_bwd_varlen.argtypes = [C.POINTER(TfaVarlenBwdParams), C.c_void_p]
+    IP = C.POINTER(C.c_int)
+    PF = C.POINTER(TfaFwdParams)
+    PB = C.POINTER(TfaBwdParams)
+    PVB = C.POINTER(TfaVarlenBwdParams)
+    for name, args in (("tfa_fwd_local", [PF, C.c_int, C.c_int, C.c_void_p]), ("tfa_fwd_local_plan", [PF, C.c_int, C.c_int, IP, IP, IP]),
+                       ("tfa_fwd_local_variant", [PF, C.c_int, C.c_int]), ("tfa_fwd_local_rounding_rule", [PF, C.c_int, C.c_int]),
+                       ("tfa_fwd_varlen_local", [PV, C.c_int, C.c_int, C.c_void_p]), ("tfa_fwd_varlen_local_plan", [PV, C.c_int, C.c_int, IP, IP, IP]),
+                       ("tfa_fwd_varlen_local_variant", [PV, C.c_int, C.c_int]), ("tfa_fwd_varlen_local_rounding_rule", [PV, C.c_int, C.c_int]),
+                       ("tfa_bwd_local", [PB, C.c_int, C.c_int, C.c_void_p]), ("tfa_bwd_local_plan", [PB, C.c_int, C.c_int]),
+                       ("tfa_bwd_varlen_local", [PVB, C.c_int, C.c_int, C.c_void_p]), ("tfa_bwd_varlen_local_plan", [PVB, C.c_int, C.c_int])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
     _lib = L
     return L
 

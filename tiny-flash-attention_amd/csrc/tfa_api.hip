@@ -338,7 +338,68 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
 // such a slice fits one descriptor, and fills the kernel arguments), runs B of them as the grid's batch, and leaves the rest to the kernels: each work item
 // reads its sequence's bounds from cu_seqlens on the device (tfa_fwd_kernel.h: varlen_seq).  Kernel choice: what tfa_fwd picks for the fixed-length
 // problem (B, H, Hk, max_seqlen_q, max_seqlen_k, D), restricted to the two kernels with a varlen form — il8 (30) and il4 (32); the key-split ones map to il4.
-int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr) {
+// Local (sliding-window) attention (include/tfa.h: tfa_fwd_local).  FlashAttention-2's window: key j is visible to row i iff i + shift - left <= j <= i + shift + right,
+// -1 = unbounded on that side, causal forces right = 0.  A side that reaches past every key of every row is unbounded: left >= Nk - 1, right >= Nq - 1 (max_seqlen
+// for varlen).  What is left is FULL (-1, -1), CAUSAL (-1, 0) — tfa_fwd's own kernels, same bits — or a true window, the VF_IL_LOCAL instantiations.
+enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
+int window_form(int* left, int* right, bool causal, int nq, int nk) {
+  if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
+  if (causal) *right = 0;
+  if (*left >= nk - 1) *left = -1;
+  if (*left < 0 && *right == 0) return WIN_CAUSAL;
+  if (*right >= nq - 1) *right = -1;
+  return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
+}
+// the checks every true window shares (fixed-length and varlen), then the kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else
+// (split-KV, decode row packing and the key-split kernels have no local form); a variant forced by tfa_set_variant must be one of the two
+int local_variant(const tfa_fwd_params* eq, int dtype, int D, int flags, int64_t nq, int64_t nk) {
+  if (dtype != TFA_F16 && dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (D < 8 || D > 128 || (D % 8) != 0) return TFA_ERR_HEAD_DIM;
+  if (flags != 0) return TFA_ERR_SHAPE;
+  if (nq + nk >= (1 << 28)) return TFA_ERR_SHAPE;      // (the kernels' window arithmetic in int32 with room to spare)
+  if (g_variant >= 0 && g_variant != tfa::kDefaultVariant && g_variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
+  return pick_variant(eq) == tfa::kDefaultVariant ? tfa::kDefaultVariant : tfa::kSmallGridVariant;
+}
+// the window as the kernels read it (KArgs::win_left / win_right, in the bytes of big / row_mod): both sides >= 0, an unbounded one as nq + nk
+void set_window(tfa::KArgs* a, int left, int right, int nq, int nk) {
+  a->win_left = left < 0 ? nq + nk : left;
+  a->win_right = right < 0 ? nq + nk : right;
+}
+
+int run_local(const tfa_fwd_params* p, int left, int right, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr) {
+  if (!p) return TFA_ERR_NULL;
+  const int form = window_form(&left, &right, p->is_causal != 0, p->Nq, p->Nk);
+  if (form < 0) return form;
+  if (form != WIN_LOCAL) {
+    tfa_fwd_params f = *p;
+    f.is_causal = form == WIN_CAUSAL;
+    return run(&f, stream, geom, dry, variant_out, rule_out);
+  }
+  if (p->kv_offset != 0 || p->nk_total != 0) return TFA_ERR_SHAPE;   // (a window over the whole key sequence only: no partial passes)
+  const int variant = local_variant(p, p->dtype, p->D, p->flags, p->Nq, p->Nk);
+  if (variant < 0) return variant;
+  tfa_fwd_params f = *p;
+  f.is_causal = 0;                                   // (validate: one query block per work item — no causal pairs)
+  tfa::KArgs a;
+  const int st = validate(&f, &a, variant);
+  if (st != TFA_OK) return st;
+  if (a.big) return TFA_ERR_STRIDE;                  // a slice beyond one descriptor: no windowed local form
+  set_window(&a, left, right, p->Nq, p->Nk);
+  if (variant_out) *variant_out = variant;
+  if (rule_out) *rule_out = TFA_RULE_LAZY;
+  const bool f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (p->dtype == TFA_BF16)
+    e = wide ? tfa::launch_fwd_local_c<__bf16, 128, false>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<__bf16, 64, false>(a, f32out, variant, s, geom, dry);
+  else
+    e = wide ? tfa::launch_fwd_local_c<_Float16, 128, false>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<_Float16, 64, false>(a, f32out, variant, s, geom, dry);
+  return (int)e;
+}
+
+// win: nullptr, or the local window {left, right} of tfa_fwd_varlen_local
+int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr,
+               const int* win = nullptr) {
   if (!p) return TFA_ERR_NULL;
   if (!p->q || !p->k || !p->v || !p->out || !p->cu_seqlens_q || !p->cu_seqlens_k) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;             // (fp32 inputs: no varlen form)
@@ -346,6 +407,13 @@ int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* ge
   if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
   if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
   if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;                        // (TFA_FWD_EXACT_MAX: no varlen form)
+  int left = -1, right = -1, form = p->is_causal ? WIN_CAUSAL : WIN_FULL;
+  if (win) {
+    left = win[0];
+    right = win[1];
+    form = window_form(&left, &right, p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
+    if (form < 0) return form;
+  }
   tfa_fwd_params f;
   memset(&f, 0, sizeof(f));
   f.q = p->q; f.k = p->k; f.v = p->v; f.out = p->out; f.lse = p->lse;
@@ -353,11 +421,16 @@ int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* ge
   const int64_t* src[4] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride};
   int64_t* dst[4] = {f.q_stride, f.k_stride, f.v_stride, f.o_stride};
   for (int t = 0; t < 4; ++t) { dst[t][0] = 0; dst[t][1] = src[t][0]; dst[t][2] = src[t][1]; }
-  f.softmax_scale = p->softmax_scale; f.is_causal = p->is_causal; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
+  f.softmax_scale = p->softmax_scale; f.is_causal = form == WIN_CAUSAL; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
   tfa_fwd_params eq = f;
   eq.B = p->B;
   int variant = pick_variant(&eq);                   // (a variant forced by tfa_set_variant: taken when it is 30 or 32)
   if (variant == tfa::kKSplitVariant || variant == tfa::kKSplitPairVariant) variant = tfa::kSmallGridVariant;
+  if (form == WIN_LOCAL) {
+    variant = local_variant(&eq, p->dtype, p->D, p->flags, p->max_seqlen_q, p->max_seqlen_k);
+    if (variant < 0) return variant;
+    f.is_causal = 0;                                 // (validate: one query block per work item — no causal pairs)
+  }
   if (variant != tfa::kDefaultVariant && variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
   tfa::KArgs a;
   const int st = validate(&f, &a, variant);
@@ -371,10 +444,18 @@ int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* ge
   a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;   // (KArgs: in the bytes of the split-KV fields, which the il kernels never read)
   a.total_q = p->total_q; a.total_k = p->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
   if (variant_out) *variant_out = variant;
-  if (rule_out) *rule_out = (p->dtype == TFA_BF16 && TFA_IL_USE_MAXFREE) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;   // the main instantiations' rules (run() above)
-  const bool causal = p->is_causal != 0, f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
+  if (rule_out) *rule_out = (p->dtype == TFA_BF16 && TFA_IL_USE_MAXFREE && form != WIN_LOCAL) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;   // the main instantiations' rules (run() above)
+  const bool causal = form == WIN_CAUSAL, f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipError_t e;
+  if (form == WIN_LOCAL) {
+    set_window(&a, left, right, p->max_seqlen_q, p->max_seqlen_k);   // (after the last read of a.big: the window shares its bytes)
+    if (p->dtype == TFA_BF16)
+      e = wide ? tfa::launch_fwd_local_c<__bf16, 128, true>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<__bf16, 64, true>(a, f32out, variant, s, geom, dry);
+    else
+      e = wide ? tfa::launch_fwd_local_c<_Float16, 128, true>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<_Float16, 64, true>(a, f32out, variant, s, geom, dry);
+    return (int)e;
+  }
   if (p->dtype == TFA_BF16)
     e = wide ? tfa::launch_fwd_varlen<__bf16, 128>(a, causal, f32out, variant, s, geom, dry) : tfa::launch_fwd_varlen<__bf16, 64>(a, causal, f32out, variant, s, geom, dry);
   else
@@ -628,6 +709,59 @@ int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p) {
 int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p) {
   int r = -1;
   const int st = run_varlen(p, nullptr, nullptr, true, nullptr, &r);
+  return st != TFA_OK ? st : r;
+}
+
+int tfa_fwd_local(const tfa_fwd_params* p, int window_left, int window_right, void* stream) {
+  return run_local(p, window_left, window_right, stream, nullptr, false);
+}
+int tfa_fwd_local_plan(const tfa_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = run_local(p, window_left, window_right, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+int tfa_fwd_local_variant(const tfa_fwd_params* p, int window_left, int window_right) {
+  tfa::LaunchGeom g{0, 0, 0};
+  int v = -1;
+  const int st = run_local(p, window_left, window_right, nullptr, &g, true, &v);
+  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
+  return v;
+}
+int tfa_fwd_local_rounding_rule(const tfa_fwd_params* p, int window_left, int window_right) {
+  tfa::LaunchGeom g{0, 0, 0};
+  int v = -1, r = -1;
+  const int st = run_local(p, window_left, window_right, nullptr, &g, true, &v, &r);
+  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
+  return r;
+}
+int tfa_fwd_varlen_local(const tfa_varlen_fwd_params* p, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  return run_varlen(p, stream, nullptr, false, nullptr, nullptr, w);
+}
+int tfa_fwd_varlen_local_plan(const tfa_varlen_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes) {
+  const int w[2] = {window_left, window_right};
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = run_varlen(p, nullptr, &g, true, nullptr, nullptr, w);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+int tfa_fwd_varlen_local_variant(const tfa_varlen_fwd_params* p, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  int v = -1;
+  const int st = run_varlen(p, nullptr, nullptr, true, &v, nullptr, w);
+  return st != TFA_OK ? st : v;
+}
+int tfa_fwd_varlen_local_rounding_rule(const tfa_varlen_fwd_params* p, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  int r = -1;
+  const int st = run_varlen(p, nullptr, nullptr, true, nullptr, &r, w);
   return st != TFA_OK ? st : r;
 }
 

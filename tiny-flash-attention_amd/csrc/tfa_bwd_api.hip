@@ -244,7 +244,100 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
 // Packed variable-length batches (include/tfa.h: tfa_bwd_varlen): the dQ launch (which also forms delta) and the fused dK/dV launch, each in its VARLEN
 // instantiation.  As in the forward (tfa_api.hip: run_varlen) the host validates ONE sequence of max_seqlen_q x max_seqlen_k rows — every slice must fit one
 // descriptor, there is no windowed varlen form — sizes the grids from it and never reads cu_seqlens: each work item reads its sequence's bounds itself.
-int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry) {
+// Local (sliding-window) attention: the window's form as the forward sees it (tfa_api.hip: window_form — the same normalisation, restated here because the two
+// translation units share no host code): FULL / CAUSAL run tfa_bwd's own launches, a true window the LOCAL instantiations
+enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
+int window_form(int* left, int* right, bool causal, int nq, int nk) {
+  if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
+  if (causal) *right = 0;
+  if (*left >= nk - 1) *left = -1;
+  if (*left < 0 && *right == 0) return WIN_CAUSAL;
+  if (*right >= nq - 1) *right = -1;
+  return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
+}
+void set_window(tfa::BArgs* a, int left, int right, int nq, int nk) {   // (both sides >= 0: an unbounded one as nq + nk)
+  a->win_left = left < 0 ? nq + nk : left;
+  a->win_right = right < 0 ? nq + nk : right;
+}
+
+// the dQ launch (it forms delta) and the fused dK/dV launch of a true window, fixed-length or varlen: a holds everything but the gradients
+int launch_local(const tfa::BArgs& a, bool varlen, int D, int dtype, bool f32, void* dq, const int64_t* dq_st, void* dk, const int64_t* dk_st, void* dv,
+                 const int64_t* dv_st, int nq, int nk, int nbatch, int H, int Hk, void* stream, bool dry) {
+  const int gsz = f32 ? 4 : 2;
+  const bool wide = D > 64, bf16 = dtype == TFA_BF16;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  auto run = [&](const tfa::BArgs& m, bool keys, int64_t grid) -> int {
+    if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
+    hipError_t e;
+    if (varlen)
+      e = bf16 ? (wide ? tfa::launch_bwd_local<__bf16, 128, true>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<__bf16, 64, true>(m, keys, (int)grid, f32, s, dry))
+               : (wide ? tfa::launch_bwd_local<_Float16, 128, true>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<_Float16, 64, true>(m, keys, (int)grid, f32, s, dry));
+    else
+      e = bf16 ? (wide ? tfa::launch_bwd_local<__bf16, 128, false>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<__bf16, 64, false>(m, keys, (int)grid, f32, s, dry))
+               : (wide ? tfa::launch_bwd_local<_Float16, 128, false>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<_Float16, 64, false>(m, keys, (int)grid, f32, s, dry));
+    return (int)e;
+  };
+  tfa::BArgs d = a;
+  d.grad = dq; d.gs_b = dq_st[0]; d.gs_h = dq_st[1]; d.gs_n = dq_st[2];
+  if (!slice_bytes(nq, d.gs_n, D, gsz, &d.g_bytes)) return TFA_ERR_STRIDE;
+  d.nrb = (nq + 255) / 256;
+  tfa::BArgs m = a;
+  m.grad = dk; m.gs_b = dk_st[0]; m.gs_h = dk_st[1]; m.gs_n = dk_st[2];
+  m.grad2 = dv; m.g2s_b = dv_st[0]; m.g2s_h = dv_st[1]; m.g2s_n = dv_st[2];
+  if (!slice_bytes(nk, m.gs_n, D, gsz, &m.g_bytes) || !slice_bytes(nk, m.g2s_n, D, gsz, &m.g2_bytes)) return TFA_ERR_STRIDE;
+  constexpr int kv_keys = 32 * TFA_BWD_KV_KG_OF(false);
+  m.nrb = (nk + kv_keys - 1) / kv_keys;
+  const int st_dq = run(d, false, (int64_t)nbatch * H * d.nrb);
+  if (st_dq) return st_dq;
+  return run(m, true, (int64_t)nbatch * Hk * m.nrb);
+}
+
+int run_bwd_local(const tfa_bwd_params* p, int left, int right, void* stream, bool dry) {
+  if (!p) return TFA_ERR_NULL;
+  const int form = window_form(&left, &right, p->is_causal != 0, p->Nq, p->Nk);
+  if (form < 0) return form;
+  if (form != WIN_LOCAL) {
+    tfa_bwd_params f = *p;
+    f.is_causal = form == WIN_CAUSAL;
+    return run_bwd(&f, stream, dry);
+  }
+  if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta) return TFA_ERR_NULL;
+  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (p->grad_dtype != p->dtype && p->grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
+  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
+  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->Nk <= 0 || p->H % p->Hk != 0) return TFA_ERR_SHAPE;
+  if ((int64_t)p->Nq + p->Nk >= (1 << 28)) return TFA_ERR_SHAPE;
+  if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
+  const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
+  const int64_t* in_st[5] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride};
+  for (int i = 0; i < 5; ++i) { const int st = check_strides(in_st[i], p->D, esz); if (st) return st; }
+  const int64_t* g_st[3] = {p->dq_stride, p->dk_stride, p->dv_stride};
+  for (int i = 0; i < 3; ++i) { const int st = check_strides(g_st[i], p->D, gsz); if (st) return st; }
+  const uintptr_t al = (uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out | (uintptr_t)p->dout | (uintptr_t)p->dq |
+                       (uintptr_t)p->dk | (uintptr_t)p->dv;
+  if (al & 15) return TFA_ERR_ALIGN;
+  if (((uintptr_t)p->lse | (uintptr_t)p->delta) & 15) return TFA_ERR_ALIGN;
+  if ((int64_t)p->B * p->H * p->Nq >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
+  tfa::BArgs a;
+  memset(&a, 0, sizeof(a));
+  // (no windowed local form: every slice must fit one descriptor — TFA_ERR_STRIDE otherwise)
+  if (!fill(&a.q, p->q, p->q_stride, p->Nq, p->D, esz, nullptr) || !fill(&a.k, p->k, p->k_stride, p->Nk, p->D, esz, nullptr) ||
+      !fill(&a.v, p->v, p->v_stride, p->Nk, p->D, esz, nullptr) || !fill(&a.out, p->out, p->o_stride, p->Nq, p->D, esz, nullptr) ||
+      !fill(&a.dout, p->dout, p->do_stride, p->Nq, p->D, esz, nullptr))
+    return TFA_ERR_STRIDE;
+  a.lse = p->lse; a.delta = p->delta; a.delta_w = p->delta;
+  a.fuse_delta = 1;                                  // (the dQ launch forms delta)
+  a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = p->Nq; a.Nk = p->Nk;
+  a.dv = p->D;
+  a.scale = p->softmax_scale;
+  a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
+  set_window(&a, left, right, p->Nq, p->Nk);
+  return launch_local(a, false, p->D, p->dtype, p->grad_dtype == TFA_F32, p->dq, p->dq_stride, p->dk, p->dk_stride, p->dv, p->dv_stride, p->Nq, p->Nk, p->B,
+                      p->H, p->Hk, stream, dry);
+}
+
+// win: nullptr, or the local window {left, right} of tfa_bwd_varlen_local
+int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry, const int* win = nullptr) {
   if (!p) return TFA_ERR_NULL;
   if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta || !p->cu_seqlens_q || !p->cu_seqlens_k)
     return TFA_ERR_NULL;
@@ -255,6 +348,14 @@ int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry) {
   if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
   if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;
   if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
+  int left = -1, right = -1, form = p->is_causal ? WIN_CAUSAL : WIN_FULL;
+  if (win) {
+    left = win[0];
+    right = win[1];
+    form = window_form(&left, &right, p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
+    if (form < 0) return form;
+    if (form == WIN_LOCAL && (int64_t)p->max_seqlen_q + p->max_seqlen_k >= (1 << 28)) return TFA_ERR_SHAPE;
+  }
   const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
   // (head, row) strides as the (batch, head, row) triples of one sequence: batch stride 0
   int64_t st[8][3];
@@ -284,7 +385,11 @@ int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry) {
   a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
   a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;
   a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
-  const bool causal = p->is_causal != 0, f32 = p->grad_dtype == TFA_F32, wide = p->D > 64, bf16 = p->dtype == TFA_BF16;
+  const bool causal = form == WIN_CAUSAL, f32 = p->grad_dtype == TFA_F32, wide = p->D > 64, bf16 = p->dtype == TFA_BF16;
+  if (form == WIN_LOCAL) {
+    set_window(&a, left, right, nq, nk);
+    return launch_local(a, true, p->D, p->dtype, f32, p->dq, st[5], p->dk, st[6], p->dv, st[7], nq, nk, p->B, p->H, p->Hk, stream, dry);
+  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   auto run = [&](const tfa::BArgs& m, bool keys, int64_t grid) -> int {
     if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
@@ -316,6 +421,16 @@ extern "C" {
 int tfa_bwd(const tfa_bwd_params* p, void* stream) { return run_bwd(p, stream, false); }
 int tfa_bwd_plan(const tfa_bwd_params* p) { return run_bwd(p, nullptr, true); }
 int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, stream, false); }
+int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, void* stream) { return run_bwd_local(p, window_left, window_right, stream, false); }
+int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right) { return run_bwd_local(p, window_left, window_right, nullptr, true); }
+int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  return run_bwd_varlen(p, stream, false, w);
+}
+int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  return run_bwd_varlen(p, nullptr, true, w);
+}
 int tfa_debug_bwd_split(int on) { g_bwd_split = on & 15; return TFA_OK; }
 long long tfa_bwd_workspace_bytes(const tfa_bwd_params* p) {
   tfa_bwd_params q;

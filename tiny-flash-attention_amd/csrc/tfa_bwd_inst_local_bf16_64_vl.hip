@@ -1,0 +1,5 @@
+// one local (sliding-window) backward instantiation unit: dtype=bf16 head_dim=64 varlen
+#define TFA_T __bf16
+#define TFA_D 64
+#define TFA_VARLEN true
+#include "tfa_bwd_local_inst.inc"

@@ -1,0 +1,5 @@
+// one local (sliding-window) backward instantiation unit: dtype=f16 head_dim=128 fixed-length
+#define TFA_T _Float16
+#define TFA_D 128
+#define TFA_VARLEN false
+#include "tfa_bwd_local_inst.inc"

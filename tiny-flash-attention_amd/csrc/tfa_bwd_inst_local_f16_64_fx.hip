@@ -1,0 +1,5 @@
+// one local (sliding-window) backward instantiation unit: dtype=f16 head_dim=64 fixed-length
+#define TFA_T _Float16
+#define TFA_D 64
+#define TFA_VARLEN false
+#include "tfa_bwd_local_inst.inc"

@@ -43,6 +43,9 @@ hipError_t launch_bwd_dq_ws(const BArgs& a, int grid, bool causal, bool f32out, 
 // launch (grid = B * Hk * ceil(max_seqlen_k / 128)); tfa_bwd_inst_varlen_<dtype>_<D>.hip
 template <typename T, int D>
 hipError_t launch_bwd_varlen(const BArgs& a, bool keys, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
+// local (sliding-window) attention (tfa_bwd_local / tfa_bwd_varlen_local): keys as above, the LOCAL instantiations; tfa_bwd_inst_local_<dtype>_<D>_<fx|vl>.hip
+template <typename T, int D, bool VARLEN>
+hipError_t launch_bwd_local(const BArgs& a, bool keys, int grid, bool f32out, hipStream_t stream, bool dry);
 template <typename T, int D>
 hipError_t launch_delta(const void* o, const void* dout, float* delta, const long long* os, const long long* ds, int H, int Nq, long long rows,
                         int dv, hipStream_t stream, bool dry);

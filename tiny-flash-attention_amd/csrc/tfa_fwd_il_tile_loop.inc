@@ -146,6 +146,10 @@
     constexpr bool ASMTAIL = (ASMLOOP || ASMLOOPX) && TFA_IL_USE_ASMTAIL;
     const bool tail_on = ASMTAIL && !seam && nt_full == nt;
     auto loop_ok = [&](int j) -> bool { return j + 1 < nact && j + 1 < fm && j + 2 < nt_full; };   // the loop proper takes tile j
+    // LOCAL: the statement masks only the right edge — it is entered at tile j only when S(j+1) on needs no left mask (tiles 0 .. nlm-1 hold keys left of
+    // the window of the wave's last row: the compiler-scheduled path computes their S through qk_burst's full mask)
+    int nlm = 0;
+    if (LOCAL) { const int e = pos_hi + shift - wlen; nlm = e > 0 ? (e + BN - 1) / BN : 0; }
     // EXACT: every tile with a successor takes the pinned body; the running maximum is advanced in front of it (exact_step) and the body that
     // also re-bases O runs when some row of the wave moved
     auto fast_exact = [&](auto par_c, bool masked, int j, f32x16 (&scur)[2], float mcur, f32x16 (&snext)[2], float& mnext) {
@@ -241,7 +245,7 @@
       } else {
       // (the statement makes progress from an even tile whenever no re-base is pending and either the loop proper takes the tile or the tails are on: then
       //  it runs to the wave's last tile and comes back early only for a re-base)
-      if (ASMLOOP && !trigger(mA) && (loop_ok(j) || tail_on)) {
+      if (ASMLOOP && !trigger(mA) && (loop_ok(j) || tail_on) && (!LOCAL || j + 1 >= nlm)) {
         int jj = j;
         asm_loop(jj, (early_ok && nact == nt) ? 1 : 0);   // tiles j .. jj-1 done, jj > j; S(jj) is in sA (jj even) / sB (odd)
 #if defined(TFA_IL_TRACEITER)

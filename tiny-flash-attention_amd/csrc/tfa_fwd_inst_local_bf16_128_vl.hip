@@ -1,0 +1,5 @@
+// one local (sliding-window) instantiation unit: dtype=bf16 head_dim=128 varlen
+#define TFA_T __bf16
+#define TFA_D 128
+#define TFA_VARLEN true
+#include "tfa_fwd_local_inst.inc"

@@ -92,9 +92,18 @@ struct KArgs {
   unsigned long long q_bytes, k_bytes, v_bytes, o_bytes;   // extent of one (b,h) slice in bytes.  Kernels use ONE descriptor per slice
                     // (< 2 GiB); the il kernels also exist in a WINDOWED instantiation (VF_IL_WINDOWED: rsrc_at, one query
                     // block / one K/V tile per descriptor) that tfa_api.hip launches when a slice is larger
-  int big;          // some slice does not fit one descriptor: launch the windowed instantiation
-  int row_mod;      // > 0: GQA query heads packed as rows (tfa_api.hip: pack_gqa_rows) in a CAUSAL problem — row r of the block is
+  // (the local-attention window shares its bytes with `big` and `row_mod` — the host reads `big` before it fills the window, and only the idle-wave
+  //  instantiations read `row_mod`, which have no local form — so that every existing kernel keeps its argument layout: tfa_fwd_local, VF_IL_LOCAL)
+  union {
+    struct {
+      int big;      // some slice does not fit one descriptor: launch the windowed instantiation
+      int row_mod;  // > 0: GQA query heads packed as rows (tfa_api.hip: pack_gqa_rows) in a CAUSAL problem — row r of the block is
                     // query position r % row_mod of one of the packed heads; 0: row r is position r
+    };
+    struct {
+      int win_left, win_right;   // local: key j is visible to row i iff i + shift - win_left <= j <= i + shift + win_right (both >= 0, clamped by the host)
+    };
+  };
   float scale;      // softmax_scale
   float scale_log2; // softmax_scale * log2(e)
   int grid;         // workgroups launched (persistent kernels walk work items with this stride)

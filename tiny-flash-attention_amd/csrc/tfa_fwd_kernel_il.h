@@ -69,6 +69,12 @@ constexpr int VF_IL_DMASTAGGER = 131072; // with DMASPREAD: the upper half of th
 constexpr int VF_IL_VARLEN = 1 << 23;    // packed variable-length batches (tfa_fwd_varlen): b indexes a sequence of KArgs::cu_q / cu_k, read by the work item itself
                                          // (varlen_seq); its lengths, causal shift, block count, base rows and slice extents replace the launch's.  Nothing inside the
                                          // tile loop changes.  (The bit is VF_X4_EPI of the x4 kernel: each kernel reads only its own flags)
+constexpr int VF_IL_LOCAL = 1 << 22;     // local (sliding-window) attention (tfa_fwd_local): key j is visible to row i iff i + shift - left <= j <= i + shift + right,
+                                         // left / right = KArgs::win_left / win_right (clamped by the host).  One pass per work item (no pairing: windowed blocks carry
+                                         // nearly equal work); the K / V slices start at the block's first visible tile, so the tile loop walks only the tiles that
+                                         // intersect the block's windows, the right edge is the causal limit moved by `right`, and the tiles on the left edge run the
+                                         // compiler-scheduled masked body.  Lazy row reference (TFA_RULE_LAZY): a row whose first visited tile is all masked re-bases
+                                         // from -1e30.  (The bit is VF_X4 of the x4 kernel: each kernel reads only its own flags)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -275,9 +281,24 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     const int nmb_s = (vsq.nq + BM - 1) / BM;
     if (wi >= (PAIR ? (nmb_s + 1) >> 1 : nmb_s)) return;
   }
-  const int shift = VARLEN ? vsq.nk - vsq.nq : p.shift;
   const int nmb_x = VARLEN ? (vsq.nq + BM - 1) / BM : p.nmb;
-#define IL_NK (VARLEN ? vsq.nk : p.Nk)
+  // LOCAL: one query block per work item (CAUSAL order, no pairs).  Its rows' windows start at key q0 + shift - left: K / V are addressed from the first
+  // 64-key tile that holds such a key on (kofs keys further on), and the block sees the keys through that view — shift and the key count lose kofs, the
+  // right edge is the causal limit plus `right`, and keys below my_pos + shift - wlen (wlen = left + right) are masked
+  constexpr bool LOCAL = (VF & VF_IL_LOCAL) != 0;
+  static_assert(!LOCAL || (CAUSAL && !PAIR && !(VF & (VF_IL_KSPLIT | VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_EXACT | VF_IL_SEAM | VF_IL_PREF | VF_IL_PREF2)) &&
+                           !TFA_IL_USE_EARLY), "local: the non-paired causal form of the il8 / il4 main instantiations");
+  int kofs = 0, wlen = 0;
+  if constexpr (LOCAL) {
+    const int nk_s = VARLEN ? vsq.nk : p.Nk;
+    const int lo = (nmb_x - 1 - wi) * BM + (VARLEN ? vsq.nk - vsq.nq : p.shift) - p.win_left;   // first key the block's first row sees
+    int t_lo = lo > 0 ? lo / BN : 0;
+    t_lo = t_lo < nk_s / BN ? t_lo : nk_s / BN;
+    kofs = __builtin_amdgcn_readfirstlane(t_lo * BN);
+    wlen = p.win_left + p.win_right;
+  }
+  const int shift = (VARLEN ? vsq.nk - vsq.nq : p.shift) + (LOCAL ? p.win_right - kofs : 0);
+#define IL_NK ((VARLEN ? vsq.nk : p.Nk) - (LOCAL ? kofs : 0))
 
   const T* qbase = reinterpret_cast<const T*>(p.q) + (VARLEN ? (long long)vsq.q0 * p.qs_n : b * p.qs_b) + h * p.qs_h;
   const T* kbase = reinterpret_cast<const T*>(p.k) + (VARLEN ? (long long)vsq.k0 * p.ks_n : b * p.ks_b) + hk * p.ks_h;
@@ -286,6 +307,13 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   constexpr bool WIN = (VF & VF_IL_WINDOWED) != 0;
   // KSPLIT: group g sees the key sequence through a strided view — its tile j is tile 2j+g of the head
   unsigned long long k_bytes = VARLEN ? varlen_bytes(vsq.nk, p.ks_n, p.dv, 2) : p.k_bytes, v_bytes = VARLEN ? varlen_bytes(vsq.nk, p.vs_n, p.dv, 2) : p.v_bytes;
+  if (LOCAL) {
+    const unsigned long long ko = (unsigned long long)kofs * p.ks_n * 2, vo = (unsigned long long)kofs * p.vs_n * 2;
+    kbase += kofs * p.ks_n;
+    vbase += kofs * p.vs_n;
+    k_bytes = k_bytes > ko ? k_bytes - ko : 0;
+    v_bytes = v_bytes > vo ? v_bytes - vo : 0;
+  }
   if (KSPLIT) {
     const unsigned long long ko = (unsigned long long)grp * BN * p.ks_n * 2, vo = (unsigned long long)grp * BN * p.vs_n * 2;
     kbase += grp * BN * p.ks_n;
@@ -373,7 +401,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   // maximum, nothing else), leaves them in LDS and runs the pass again with mref seeded by them (P <= 1: it cannot happen twice) — rare, 1.5 passes extra,
   // correct, and no second rule in the tile bodies (a max-tracking twin of every body beside the max-free one made hipcc spill 90 registers).
   // Stated domain: |v| * Nk < 2^63.  fp16 keeps the maximum (its P overflows at 2^16).  oracle/oracle.py: tiled_emulation_first_tile restates the rule.
-  constexpr bool MAXFREE_BASE = std::is_same<T, __bf16>::value && !EXACT && TFA_IL_USE_MAXFREE && TFA_IL_USE_ASMLOOP && (D == 128 || D == 64) && DVB == D / 32 &&
+  constexpr bool MAXFREE_BASE = std::is_same<T, __bf16>::value && !EXACT && !LOCAL && TFA_IL_USE_MAXFREE && TFA_IL_USE_ASMLOOP && (D == 128 || D == 64) && DVB == D / 32 &&
                                 (AB & ~ILAB_TRACE) == 0 && !(VF & (VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_DMASTAGGER | VF_IL_SEAM)) && (PPW == 1 || PPW == 2 || PPW == 4);
   constexpr bool MAXFREE = MAXFREE_BASE;
   static_assert(!MAXFREE || !((VF & VF_IL_PREF) && !(VF & VF_IL_PREF2)), "max-free: a redone pass re-issues its own first requests (PREF2 or no prefetch)");
@@ -411,7 +439,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     VarSeq vx{};                                       // (VARLEN: the sequence's bounds re-read with the arguments)
     if constexpr (VARLEN) vx = varlen_seq(p, b);
     const int q0x = mbx * BM;
-    int kve = VARLEN ? vx.nk : p.Nk;
+    int kve = (VARLEN ? vx.nk : p.Nk) - (LOCAL ? kofs : 0);
     if (CAUSAL) {
       const int lim = (((VF & VF_IL_IDLE) && p.row_mod > 0) ? p.row_mod : q0x + BM) + shift;
       kve = lim < kve ? lim : kve;
@@ -582,18 +610,20 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
       const int key0 = key0_of(t);
       bool nm = (key0 + BN > IL_NK);
       if (CAUSAL) nm = nm || (key0 + BN - 1 > pos_lo + shift);
+      if (LOCAL) nm = nm || (key0 < pos_hi + shift - wlen);     // the left edge: some row of the wave does not see the tile's first key
       return nm;
     };
     auto apply_mask = [&](int t, f32x16 (&s)[2]) {
       int lim = IL_NK - 1;
       if (CAUSAL) { const int c = my_pos + shift; lim = c < lim ? c : lim; }
       lim -= key0_of(t) + 4 * hi;
+      const int llo = LOCAL ? my_pos + shift - wlen - key0_of(t) - 4 * hi : 0;   // LOCAL: key offsets below this lie left of the lane's window
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int ko = 32 * tt + (r & 3) + 8 * (r >> 2);
-          if (ko > lim) s[tt][r] = -INFINITY;
+          if (ko > lim || (LOCAL && ko < llo)) s[tt][r] = -INFINITY;
         }
     };
     // Reference exponent of the row ("mref", log2 domain) instead of the exact running max: P = exp2(s*sc - mref)

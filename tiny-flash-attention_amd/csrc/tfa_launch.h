@@ -142,6 +142,16 @@ static inline hipError_t launch_fwd_varlen(const KArgs& a, bool causal, bool f32
   return causal ? launch_fwd_varlen_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_varlen_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
 
+// the local (sliding-window) form (VF_IL_LOCAL) of variants 30 and 32, fixed-length and packed variable-length: one translation unit per (dtype, width, form),
+// tfa_fwd_inst_local_*.hip
+template <typename T, int D, bool VARLEN>
+hipError_t launch_fwd_local_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_FWD_LOCAL_UNITS(T, D)                                                                             \
+  template <> hipError_t launch_fwd_local_c<T, D, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
+  template <> hipError_t launch_fwd_local_c<T, D, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
+TFA_FWD_LOCAL_UNITS(__bf16, 64) TFA_FWD_LOCAL_UNITS(__bf16, 128) TFA_FWD_LOCAL_UNITS(_Float16, 64) TFA_FWD_LOCAL_UNITS(_Float16, 128)
+#undef TFA_FWD_LOCAL_UNITS
+
 // common tail of every launcher: report the geometry, opt in to the dynamic LDS size on this device, launch, and return
 // THIS launch's status (a sticky error left behind by unrelated earlier HIP calls is cleared first).
 // the launch constants of the kernels' work-item decode (KArgs::wmode ..): every launch goes through launch_common, so no caller can forget them

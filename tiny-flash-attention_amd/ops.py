@@ -42,8 +42,38 @@ def _strides_bhnd(t, layout):
     raise ValueError(f"unknown layout {layout!r}")
 
 
+def _window(window_size, causal, nq, nk, dtype, D, extra=()):
+    """FlashAttention-2's ``window_size=(left, right)`` checked and normalised as the C ABI does it (include/tfa.h, local attention): returns
+    ``None`` for full / causal attention (the existing entry points run) or ``(left, right)`` for a true sliding window.  Unsupported combinations
+    raise ValueError naming the limit; ``extra``: (condition, message) pairs that rule a true window out."""
+    try:
+        left, right = (int(w) for w in window_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"window_size must be a pair of integers (left, right), got {window_size!r}") from None
+    if left < -1 or right < -1:
+        raise ValueError(f"window_size sides must be >= -1 (-1 = unbounded), got {(left, right)}")
+    if causal:
+        right = 0
+    if left >= nk - 1:
+        left = -1
+    if left < 0 and right == 0:
+        return None if causal else (-1, 0)
+    if right >= nq - 1:
+        right = -1
+    if left < 0 and right < 0:
+        return None
+    if dtype == torch.float32:
+        raise ValueError("window_size: sliding windows run on float16 / bfloat16 inputs only (no fp32 local path)")
+    if D > 128:
+        raise ValueError(f"window_size: sliding windows support head dims up to 128 (got {D})")
+    for cond, msg in extra:
+        if cond:
+            raise ValueError(f"window_size: {msg}")
+    return (left, right)
+
+
 def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd", out_f32=False,
-                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False):
+                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1)):
     """General forward: q (B,H,Nq,D) / k,v (B,Hk,Nk,D) for ``layout='bhnd'`` or
     (B,N,H,D) for ``layout='bnhd'``; any batch/head/row strides, unit stride along D.
     Returns ``(out, lse)``; ``out`` has q's shape (fp32 when ``out_f32``), ``lse`` is (B,H,Nq) fp32.
@@ -51,7 +81,9 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     flash_attention_cutlass/csrc/flash_attention.cu:536-630.  ``auto_split``: decode-like shapes (few query rows, long K/V)
     go through tfa_fwd_splitkv with the chunk count tfa_fwd_suggest_splits names (what the reference-named entry points do).
     ``exact_max``: TFA_FWD_EXACT_MAX — P is rounded to 16 bits at the reference's own points (exact running row maximum per
-    KV tile, main_torch_only.py:240-260); head dims up to 128."""
+    KV tile, main_torch_only.py:240-260); head dims up to 128.
+    ``window_size=(left, right)``: FlashAttention-2's local (sliding-window) attention — key j is visible to row i iff
+    i + (Nk - Nq) - left <= j <= i + (Nk - Nq) + right, -1 = unbounded, ``is_causal`` forces right = 0 (tfa_fwd_local)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -75,6 +107,10 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
         raise RuntimeError(f"shape mismatch: q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
+    win = _window(window_size, is_causal, Nq, Nk, q.dtype, D,
+                  extra=((exact_max, "no exact_max form of the local kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
+    if win == (-1, 0):                               # (the causal mask itself: tfa_fwd with is_causal)
+        win, is_causal = None, True
 
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
@@ -108,10 +144,12 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     # tfa_fwd_splitkv's merge writes a dense (B,H,Nq,D) result: gate on the exact strides it checks (is_contiguous() ignores the
     # strides of size-1 dims, and Nq == 1 is the very shape auto-split targets)
     dense_out = (out.stride(3) == 1 and out.stride(2) == D and out.stride(1) == Nq * D and out.stride(0) == H * Nq * D)
-    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out) else 1
+    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None) else 1
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if splits > 1:
+        if win is not None:
+            _lib.check(L.tfa_fwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
+        elif splits > 1:
             need = L.tfa_fwd_splitkv_workspace(C.byref(p), int(splits))
             if need < 0:
                 _lib.check(int(need))
@@ -225,13 +263,14 @@ def make_bwd_params(q, k, v, out, lse, dout, dq, dk, dv, delta, is_causal, softm
     return p
 
 
-def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None):
+def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None, window_size=(-1, -1)):
     """Backward of ``flash_attn_fwd``: returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``).
     ``out`` and ``lse`` are the forward's results for the same q, k, v; ``dout`` is the upstream gradient
     (shape/dtype of ``out``).  The reference has no backward — it only saves the LSE for one
     (flash_attention_cutlass/csrc/flash_attention.cu:353-354,614-623); maps onto tfa_bwd (include/tfa.h).
     ``workspace``: None (default: the O(N)-memory 7-GEMM form), True (allocate tfa_bwd_workspace_bytes of scratch for this call)
-    or a caller-owned uint8 / any-dtype CUDA tensor of at least that many bytes: tfa_bwd then keeps dS and executes 5 GEMMs."""
+    or a caller-owned uint8 / any-dtype CUDA tensor of at least that many bytes: tfa_bwd then keeps dS and executes 5 GEMMs.
+    ``window_size``: the forward's sliding window (tfa_bwd_local; no workspace form)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (dout, "dout")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -250,6 +289,10 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
                            f"(got {lse.dtype} {tuple(lse.shape)} on {lse.device})")
     if any(t.device != q.device for t in (k, v, out, dout)):
         raise RuntimeError("q,k,v,out,dout must be on the same device")
+    nq, nk = (q.shape[2], k.shape[2]) if layout == "bhnd" else (q.shape[1], k.shape[1])
+    win = _window(window_size, is_causal, nq, nk, q.dtype, D, extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
+    if win == (-1, 0):
+        win, is_causal = None, True
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.empty(q.shape, dtype=gdt, device=q.device)
@@ -267,7 +310,10 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         p.workspace_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().tfa_bwd(C.byref(p), C.c_void_p(stream)))
+        if win is not None:
+            _lib.check(_lib.lib().tfa_bwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().tfa_bwd(C.byref(p), C.c_void_p(stream)))
     return dq, dk, dv
 
 
@@ -332,10 +378,10 @@ class _FlashAttnBNHD(torch.autograd.Function):
     """autograd glue for ``flash_attn_func``: forward = tfa_fwd, backward = tfa_bwd, both on (B,N,H,D) views."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, softmax_scale):
-        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd")
+    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1)):
+        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.causal, ctx.scale = causal, softmax_scale
+        ctx.causal, ctx.scale, ctx.window = causal, softmax_scale, window_size
         return out
 
     @staticmethod
@@ -343,18 +389,20 @@ class _FlashAttnBNHD(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         if dout.stride(3) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd")
-        return dq, dk, dv, None, None
+        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window)
+        return dq, dk, dv, None, None, None
 
 
-def flash_attn_func(q, k, v, causal=False, softmax_scale=None):
+def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1)):
     """(B,N,H,D)-layout entry with the signature the reference's scripts use for comparison
     (flash_attention_cutlass/test.py:71-76, flash_attention_py/main_torch_only.py:304);
     supports GQA/MQA (fewer K/V heads).  Differentiable (like the official function the reference
-    compares against): when an input requires grad the backward runs tfa_bwd."""
+    compares against): when an input requires grad the backward runs tfa_bwd.  ``window_size=(left, right)``: FlashAttention-2's local
+    (sliding-window) attention, -1 = unbounded, ``causal`` forces right = 0 (tfa_fwd_local / tfa_bwd_local)."""
+    window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale)
-    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False)
+        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size)
+    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size)
     return out
 
 
@@ -399,17 +447,21 @@ def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
 
 
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          out_f32=False, return_lse=True, out=None):
+                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1)):
     """Packed variable-length forward (tfa_fwd_varlen, include/tfa.h): q (total_q, H, D), k / v (total_k, Hk, D), sequence b is rows
     [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v (device int32, B + 1 entries, never read on the host).
     Causal masking per sequence, bottom-right aligned.  Returns ``(out, lse)``: ``out`` shaped like q (fp32 when ``out_f32``), ``lse`` fp32 (H, total_q).
-    Rows outside every sequence are not written (a caller-provided ``out`` keeps them)."""
+    Rows outside every sequence are not written (a caller-provided ``out`` keeps them).  ``window_size``: FlashAttention-2's sliding window per
+    sequence (tfa_fwd_varlen_local)."""
     _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     B = cu_seqlens_q.numel() - 1
     total_q, H, D = q.shape
     total_k, Hk, _ = k.shape
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
+    win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
+    if win == (-1, 0):
+        win, is_causal = None, True
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
     else:
@@ -435,12 +487,15 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().tfa_fwd_varlen(C.byref(p), C.c_void_p(stream)))
+        if win is not None:
+            _lib.check(_lib.lib().tfa_fwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().tfa_fwd_varlen(C.byref(p), C.c_void_p(stream)))
     return out, lse
 
 
 def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          grad_f32=False):
+                          grad_f32=False, window_size=(-1, -1)):
     """Backward of ``flash_attn_varlen_fwd`` (tfa_bwd_varlen): returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``); for GQA dk / dv
     are summed over the query heads of each K/V head within each sequence.  Rows outside every sequence get zero gradients: the kernels never write
     them, so the three results are allocated zeroed (one memset of dq, dk and dv per call)."""
@@ -454,6 +509,9 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
         softmax_scale = 1.0 / math.sqrt(D)
     if not isinstance(lse, torch.Tensor) or not lse.is_cuda or lse.device != q.device or lse.dtype != torch.float32 or tuple(lse.shape) != (H, total_q):
         raise RuntimeError(f"lse must be the forward's float32 {(H, total_q)} tensor on q's device")
+    win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
+    if win == (-1, 0):
+        win, is_causal = None, True
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.zeros(q.shape, dtype=gdt, device=q.device)
@@ -477,7 +535,10 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     p.grad_dtype = _lib.TFA_F32 if grad_f32 else _DT[q.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().tfa_bwd_varlen(C.byref(p), C.c_void_p(stream)))
+        if win is not None:
+            _lib.check(_lib.lib().tfa_bwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().tfa_bwd_varlen(C.byref(p), C.c_void_p(stream)))
     return dq, dk, dv
 
 
@@ -485,29 +546,33 @@ class _FlashAttnVarlen(torch.autograd.Function):
     """autograd glue for ``flash_attn_varlen_func``: forward = tfa_fwd_varlen, backward = tfa_bwd_varlen."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale):
-        out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=(-1, -1)):
+        out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=window_size)
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
-        ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale)
+        ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
-        max_q, max_k, causal, scale = ctx.args
+        max_q, max_k, causal, scale, window = ctx.args
         if dout.stride(2) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale)
-        return dq, dk, dv, None, None, None, None, None, None
+        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
-def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False):
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
+                           window_size=(-1, -1)):
     """Packed variable-length attention with FlashAttention-2's positional signature (flash_attn_varlen_func): q (total_q, H, D), k / v
     (total_k, Hk, D), cu_seqlens_q / _k device int32 (B + 1), max_seqlen_q / _k host integers.  Differentiable: when an input requires grad the
-    backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0)."""
+    backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0).  ``window_size=(left, right)``: FlashAttention-2's sliding
+    window per sequence, -1 = unbounded, ``causal`` forces right = 0."""
     if dropout_p != 0.0:
         raise NotImplementedError("flash_attn_varlen_func: dropout is not supported (dropout_p must be 0)")
+    window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale)
-    out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False)
+        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale, window_size)
+    out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False,
+                                   window_size=window_size)
     return out
