@@ -228,6 +228,16 @@ bool pack_gqa_rows(const tfa_fwd_params* p, tfa_fwd_params* o, int* row_mod = nu
   return true;
 }
 
+// the row reference P is rounded against (include/tfa.h) for a 16-bit problem of head dim D that runs `variant`: the il kernels' lazily re-based reference,
+// except — bf16, the main instantiation (the one that carries the hand-scheduled statement: tfa_fwd_kernel_il.h MAXFREE) — the first key tile's maximum;
+// the 256-wide kernel re-bases lazily too; the LDS-DMA kernel and the exact-max il8 keep the exact running maximum
+int rounding_rule(int variant, int dtype, int D, bool main_inst) {
+  if (D > 128) return TFA_RULE_LAZY;
+  const tfa::Variant* vi = tfa::variant_info(variant);
+  if (!vi || !(vi->vf & tfa::VF_IL) || variant == tfa::kExactVariant) return TFA_RULE_EXACT_MAX;
+  return (dtype == TFA_BF16 && main_inst && TFA_IL_USE_MAXFREE) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;
+}
+
 // fp32 q, k, v (tfa_fwd_params::dtype == TFA_F32): the correctness path behind the reference's fp32 fixtures (tfa_fwd_f32.hip).  fp32 output
 // only; any strides with 16-byte aligned rows; head dims = multiples of 4 up to 256; GQA, Nq != Nk, kv_offset / nk_total as for the 16-bit types.
 int run_f32(const tfa_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool dry) {
@@ -296,30 +306,18 @@ int run(const tfa_fwd_params* p_in, void* stream, tfa::LaunchGeom* geom, bool dr
   if (st != TFA_OK) return st;
   if (variant_out) *variant_out = variant;
   if (rule_out) {
-    // the row reference P is rounded against (include/tfa.h): the il kernels' lazily re-based reference, except — bf16, the main instantiation (the one
-    // that carries the hand-scheduled statement: tfa_fwd_kernel_il.h MAXFREE) — the first key tile's maximum; the 256-wide kernel re-bases lazily too
-    const tfa::Variant* vi = tfa::variant_info(variant);
-    const bool il = vi && (vi->vf & tfa::VF_IL) != 0 && variant != tfa::kExactVariant;
-    const bool x4 = p->D > 128;
     const bool main_inst = tfa::is_il_variant(variant) && tfa::il_instantiation(variant, a.big != 0, a.Nq, a.row_mod, a.dv, p->D > 64 ? 128 : 64) == tfa::IL_MAIN;
-    *rule_out = x4 ? TFA_RULE_LAZY : !il ? TFA_RULE_EXACT_MAX : (p->dtype == TFA_BF16 && main_inst && TFA_IL_USE_MAXFREE) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;
+    *rule_out = rounding_rule(variant, p->dtype, p->D, main_inst);
   }
   const bool causal = p->is_causal != 0;
   const bool f32out = p->out_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  const bool wide = p->D > 64;   // kernel width: 64 serves D <= 64, 128 serves 64 < D <= 128, 256 the rest (KArgs::dv = the valid part)
-  if (p->D > 128) {
-    e = (p->dtype == TFA_BF16) ? tfa::launch_x4_unit<__bf16, 256>(a, causal, f32out, 0, s, geom, dry)
-                               : tfa::launch_x4_unit<_Float16, 256>(a, causal, f32out, 0, s, geom, dry);
-  } else if (p->dtype == TFA_BF16) {
-    e = wide ? tfa::launch_fwd<__bf16, 128>(a, causal, f32out, variant, s, geom, dry)
-             : tfa::launch_fwd<__bf16, 64>(a, causal, f32out, variant, s, geom, dry);
-  } else {
-    e = wide ? tfa::launch_fwd<_Float16, 128>(a, causal, f32out, variant, s, geom, dry)
-             : tfa::launch_fwd<_Float16, 64>(a, causal, f32out, variant, s, geom, dry);
-  }
-  return (int)e;
+  // kernel width: 64 serves D <= 64, 128 serves 64 < D <= 128, 256 (the x4 kernel) the rest (KArgs::dv = the valid part)
+  return (int)tfa::by_dtype_width<64, 128, 256>(p->dtype, p->D, [&](auto k) {
+    using T = typename decltype(k)::T;
+    if constexpr (decltype(k)::W == 256) return tfa::launch_x4_unit<T, 256>(a, causal, f32out, 0, s, geom, dry);
+    else return tfa::launch_fwd<T, decltype(k)::W>(a, causal, f32out, variant, s, geom, dry);
+  });
 }
 
 void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, void* out, float* lse,
@@ -333,73 +331,78 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
   p->softmax_scale = scale; p->is_causal = causal; p->dtype = dtype; p->out_dtype = out_dtype;
 }
 
-// Packed variable-length batches (include/tfa.h: tfa_fwd_varlen).  The host knows the sequences' bounds only as max_seqlen_q / _k: it validates the
-// fixed-length problem of ONE sequence of max_seqlen_q x max_seqlen_k rows (batch stride 0 — validate() checks dtypes, scale, strides, alignment and that
-// such a slice fits one descriptor, and fills the kernel arguments), runs B of them as the grid's batch, and leaves the rest to the kernels: each work item
-// reads its sequence's bounds from cu_seqlens on the device (tfa_fwd_kernel.h: varlen_seq).  Kernel choice: what tfa_fwd picks for the fixed-length
-// problem (B, H, Hk, max_seqlen_q, max_seqlen_k, D), restricted to the two kernels with a varlen form — il8 (30) and il4 (32); the key-split ones map to il4.
-// Local (sliding-window) attention (include/tfa.h: tfa_fwd_local).  FlashAttention-2's window: key j is visible to row i iff i + shift - left <= j <= i + shift + right,
-// -1 = unbounded on that side, causal forces right = 0.  A side that reaches past every key of every row is unbounded: left >= Nk - 1, right >= Nq - 1 (max_seqlen
-// for varlen).  What is left is FULL (-1, -1), CAUSAL (-1, 0) — tfa_fwd's own kernels, same bits — or a true window, the VF_IL_LOCAL instantiations.
-enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
-int window_form(int* left, int* right, bool causal, int nq, int nk) {
-  if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
-  if (causal) *right = 0;
-  if (*left >= nk - 1) *left = -1;
-  if (*left < 0 && *right == 0) return WIN_CAUSAL;
-  if (*right >= nq - 1) *right = -1;
-  return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
-}
-// the checks every true window shares (fixed-length and varlen), then the kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else
-// (split-KV, decode row packing and the key-split kernels have no local form); a variant forced by tfa_set_variant must be one of the two
-int local_variant(const tfa_fwd_params* eq, int dtype, int D, int flags, int64_t nq, int64_t nk) {
-  if (dtype != TFA_F16 && dtype != TFA_BF16) return TFA_ERR_DTYPE;
-  if (D < 8 || D > 128 || (D % 8) != 0) return TFA_ERR_HEAD_DIM;
-  if (flags != 0) return TFA_ERR_SHAPE;
-  if (nq + nk >= (1 << 28)) return TFA_ERR_SHAPE;      // (the kernels' window arithmetic in int32 with room to spare)
-  if (g_variant >= 0 && g_variant != tfa::kDefaultVariant && g_variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
-  return pick_variant(eq) == tfa::kDefaultVariant ? tfa::kDefaultVariant : tfa::kSmallGridVariant;
-}
-// the window as the kernels read it (KArgs::win_left / win_right, in the bytes of big / row_mod): both sides >= 0, an unbounded one as nq + nk
-void set_window(tfa::KArgs* a, int left, int right, int nq, int nk) {
-  a->win_left = left < 0 ? nq + nk : left;
-  a->win_right = right < 0 ? nq + nk : right;
-}
-
-int run_local(const tfa_fwd_params* p, int left, int right, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr) {
-  if (!p) return TFA_ERR_NULL;
-  const int form = window_form(&left, &right, p->is_causal != 0, p->Nq, p->Nk);
-  if (form < 0) return form;
-  if (form != WIN_LOCAL) {
-    tfa_fwd_params f = *p;
-    f.is_causal = form == WIN_CAUSAL;
-    return run(&f, stream, geom, dry, variant_out, rule_out);
+// The varlen and local forms (VF_IL_VARLEN / VF_IL_LOCAL instantiations of il8 and il4: tfa_fwd_form_inst.inc) of a problem that passed its form's own checks.
+//   f:   the fixed-length problem the kernels see — varlen: ONE sequence of max_seqlen_q x max_seqlen_k rows (batch stride 0); validate() checks dtypes, scale,
+//        strides, alignment and that such a slice fits one descriptor, and fills the kernel arguments;
+//   eq:  the problem whose kernel choice the form takes over (pick_variant) — the caller's for fixed-length windows, (B, H, Hk, max_seqlen_q, max_seqlen_k, D)
+//        for varlen;
+//   vl:  the varlen call, or nullptr: B sequences run as the grid's batch and each work item reads its bounds from cu_seqlens on the device
+//        (tfa_fwd_kernel.h: varlen_seq) — the host never reads them;
+//   win: the normalised {left, right} of a true window (window_form: WIN_LOCAL), or nullptr.
+// Kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else (the key-split kernels, split-KV and decode row packing have no such form); a
+// variant forced by tfa_set_variant must be one of the two.
+int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_varlen_fwd_params* vl, const int* win, void* stream, tfa::LaunchGeom* geom,
+             bool dry, int* variant_out, int* rule_out) {
+  tfa_fwd_params f = f_in;
+  int variant;
+  if (win) {
+    if ((int64_t)f.Nq + f.Nk >= (1 << 28)) return TFA_ERR_SHAPE;   // (the kernels' window arithmetic in int32 with room to spare)
+    if (g_variant >= 0 && g_variant != tfa::kDefaultVariant && g_variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
+    variant = pick_variant(&eq) == tfa::kDefaultVariant ? tfa::kDefaultVariant : tfa::kSmallGridVariant;
+    f.is_causal = 0;                                 // (validate: one query block per work item — no causal pairs)
+  } else {
+    variant = pick_variant(&eq);                     // (a variant forced by tfa_set_variant: taken when it is 30 or 32)
+    if (variant == tfa::kKSplitVariant || variant == tfa::kKSplitPairVariant) variant = tfa::kSmallGridVariant;
+    if (variant != tfa::kDefaultVariant && variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
   }
-  if (p->kv_offset != 0 || p->nk_total != 0) return TFA_ERR_SHAPE;   // (a window over the whole key sequence only: no partial passes)
-  const int variant = local_variant(p, p->dtype, p->D, p->flags, p->Nq, p->Nk);
-  if (variant < 0) return variant;
-  tfa_fwd_params f = *p;
-  f.is_causal = 0;                                   // (validate: one query block per work item — no causal pairs)
   tfa::KArgs a;
   const int st = validate(&f, &a, variant);
   if (st != TFA_OK) return st;
-  if (a.big) return TFA_ERR_STRIDE;                  // a slice beyond one descriptor: no windowed local form
-  set_window(&a, left, right, p->Nq, p->Nk);
+  if (a.big) return TFA_ERR_STRIDE;                  // a slice beyond one descriptor: no windowed varlen / local form
+  if (vl) {
+    const int64_t nbh = (int64_t)vl->B * vl->H;
+    if (nbh * a.nwork >= (int64_t)0x7fffffff || (int64_t)vl->H * vl->total_q >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
+    a.B = vl->B;
+    a.nbh = (int)nbh;
+    a.kv_stream = 0;
+    a.cu_q = vl->cu_seqlens_q; a.cu_k = vl->cu_seqlens_k;   // (KArgs: in the bytes of the split-KV fields, which the il kernels never read)
+    a.total_q = vl->total_q; a.total_k = vl->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
+  }
+  if (win) tfa::set_window(&a, win[0], win[1], f.Nq, f.Nk);   // (after the last read of a.big: the window shares its bytes)
   if (variant_out) *variant_out = variant;
-  if (rule_out) *rule_out = TFA_RULE_LAZY;
-  const bool f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
+  if (rule_out) *rule_out = rounding_rule(variant, f.dtype, f.D, !win);   // (the local form is not the main instantiation)
+  const bool causal = f.is_causal != 0, f32out = f.out_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (p->dtype == TFA_BF16)
-    e = wide ? tfa::launch_fwd_local_c<__bf16, 128, false>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<__bf16, 64, false>(a, f32out, variant, s, geom, dry);
-  else
-    e = wide ? tfa::launch_fwd_local_c<_Float16, 128, false>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<_Float16, 64, false>(a, f32out, variant, s, geom, dry);
-  return (int)e;
+  return (int)tfa::by_dtype_width<64, 128>(f.dtype, f.D, [&](auto k) {
+    using T = typename decltype(k)::T;
+    constexpr int W = decltype(k)::W;
+    if (!win) return tfa::launch_fwd_form<T, W, true, false>(a, causal, f32out, variant, s, geom, dry);   // (no window: always varlen here)
+    return vl ? tfa::launch_fwd_form<T, W, true, true>(a, causal, f32out, variant, s, geom, dry)
+              : tfa::launch_fwd_form<T, W, false, true>(a, causal, f32out, variant, s, geom, dry);
+  });
 }
 
-// win: nullptr, or the local window {left, right} of tfa_fwd_varlen_local
-int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out = nullptr, int* rule_out = nullptr,
-               const int* win = nullptr) {
+// tfa_fwd_local: FULL and CAUSAL windows are tfa_fwd's own problems; a true window covers the whole key sequence (no partial passes)
+int run_local(const tfa_fwd_params* p, const int* w, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
+  if (!p) return TFA_ERR_NULL;
+  int win[2] = {w[0], w[1]};
+  const int form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->Nq, p->Nk);
+  if (form < 0) return form;
+  if (form != tfa::WIN_LOCAL) {
+    tfa_fwd_params f = *p;
+    f.is_causal = form == tfa::WIN_CAUSAL;
+    return run(&f, stream, geom, dry, variant_out, rule_out);
+  }
+  if (p->kv_offset != 0 || p->nk_total != 0) return TFA_ERR_SHAPE;
+  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
+  if (p->flags != 0) return TFA_ERR_SHAPE;
+  return run_form(*p, *p, nullptr, win, stream, geom, dry, variant_out, rule_out);
+}
+
+// Packed variable-length batches (include/tfa.h: tfa_fwd_varlen, tfa_fwd_varlen_local — w: the window, or nullptr).  The host knows the sequences' bounds only
+// as max_seqlen_q / _k; run_form runs the fixed-length problem of one sequence of that size B times.
+int run_varlen(const tfa_varlen_fwd_params* p, const int* w, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
   if (!p) return TFA_ERR_NULL;
   if (!p->q || !p->k || !p->v || !p->out || !p->cu_seqlens_q || !p->cu_seqlens_k) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;             // (fp32 inputs: no varlen form)
@@ -407,11 +410,11 @@ int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* ge
   if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
   if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
   if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;                        // (TFA_FWD_EXACT_MAX: no varlen form)
-  int left = -1, right = -1, form = p->is_causal ? WIN_CAUSAL : WIN_FULL;
-  if (win) {
-    left = win[0];
-    right = win[1];
-    form = window_form(&left, &right, p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
+  int win[2] = {-1, -1}, form = p->is_causal ? tfa::WIN_CAUSAL : tfa::WIN_FULL;
+  if (w) {
+    win[0] = w[0];
+    win[1] = w[1];
+    form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
     if (form < 0) return form;
   }
   tfa_fwd_params f;
@@ -421,46 +424,42 @@ int run_varlen(const tfa_varlen_fwd_params* p, void* stream, tfa::LaunchGeom* ge
   const int64_t* src[4] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride};
   int64_t* dst[4] = {f.q_stride, f.k_stride, f.v_stride, f.o_stride};
   for (int t = 0; t < 4; ++t) { dst[t][0] = 0; dst[t][1] = src[t][0]; dst[t][2] = src[t][1]; }
-  f.softmax_scale = p->softmax_scale; f.is_causal = form == WIN_CAUSAL; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
+  f.softmax_scale = p->softmax_scale; f.is_causal = form == tfa::WIN_CAUSAL; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
   tfa_fwd_params eq = f;
   eq.B = p->B;
-  int variant = pick_variant(&eq);                   // (a variant forced by tfa_set_variant: taken when it is 30 or 32)
-  if (variant == tfa::kKSplitVariant || variant == tfa::kKSplitPairVariant) variant = tfa::kSmallGridVariant;
-  if (form == WIN_LOCAL) {
-    variant = local_variant(&eq, p->dtype, p->D, p->flags, p->max_seqlen_q, p->max_seqlen_k);
-    if (variant < 0) return variant;
-    f.is_causal = 0;                                 // (validate: one query block per work item — no causal pairs)
-  }
-  if (variant != tfa::kDefaultVariant && variant != tfa::kSmallGridVariant) return TFA_ERR_VARIANT;
-  tfa::KArgs a;
-  const int st = validate(&f, &a, variant);
+  return run_form(f, eq, p, form == tfa::WIN_LOCAL ? win : nullptr, stream, geom, dry, variant_out, rule_out);
+}
+
+// One forward call as an entry point names it: fixed-length (p) or packed variable-length (vp), with the {left, right} window of the _local entry points or
+// without (win == nullptr) — and the route that runs it.  The _plan, _variant and _rounding_rule entry points are dry runs of that route (no GPU needed).
+struct FwdCall {
+  const tfa_fwd_params* p;
+  const tfa_varlen_fwd_params* vp;
+  const int* win;
+};
+int route(const FwdCall& c, void* stream, tfa::LaunchGeom* geom = nullptr, bool dry = false, int* variant_out = nullptr, int* rule_out = nullptr) {
+  if (c.vp) return run_varlen(c.vp, c.win, stream, geom, dry, variant_out, rule_out);
+  if (c.win) return run_local(c.p, c.win, stream, geom, dry, variant_out, rule_out);
+  return run(c.p, stream, geom, dry, variant_out, rule_out);
+}
+int plan(const FwdCall& c, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = route(c, nullptr, &g, true);
   if (st != TFA_OK) return st;
-  if (a.big) return TFA_ERR_STRIDE;                  // max_seqlen rows of a slice beyond one descriptor: no windowed varlen form
-  const int64_t nbh = (int64_t)p->B * p->H;
-  if (nbh * a.nwork >= (int64_t)0x7fffffff || (int64_t)p->H * p->total_q >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-  a.B = p->B;
-  a.nbh = (int)nbh;
-  a.kv_stream = 0;
-  a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;   // (KArgs: in the bytes of the split-KV fields, which the il kernels never read)
-  a.total_q = p->total_q; a.total_k = p->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
-  if (variant_out) *variant_out = variant;
-  if (rule_out) *rule_out = (p->dtype == TFA_BF16 && TFA_IL_USE_MAXFREE && form != WIN_LOCAL) ? TFA_RULE_FIRST_TILE : TFA_RULE_LAZY;   // the main instantiations' rules (run() above)
-  const bool causal = form == WIN_CAUSAL, f32out = p->out_dtype == TFA_F32, wide = p->D > 64;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (form == WIN_LOCAL) {
-    set_window(&a, left, right, p->max_seqlen_q, p->max_seqlen_k);   // (after the last read of a.big: the window shares its bytes)
-    if (p->dtype == TFA_BF16)
-      e = wide ? tfa::launch_fwd_local_c<__bf16, 128, true>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<__bf16, 64, true>(a, f32out, variant, s, geom, dry);
-    else
-      e = wide ? tfa::launch_fwd_local_c<_Float16, 128, true>(a, f32out, variant, s, geom, dry) : tfa::launch_fwd_local_c<_Float16, 64, true>(a, f32out, variant, s, geom, dry);
-    return (int)e;
-  }
-  if (p->dtype == TFA_BF16)
-    e = wide ? tfa::launch_fwd_varlen<__bf16, 128>(a, causal, f32out, variant, s, geom, dry) : tfa::launch_fwd_varlen<__bf16, 64>(a, causal, f32out, variant, s, geom, dry);
-  else
-    e = wide ? tfa::launch_fwd_varlen<_Float16, 128>(a, causal, f32out, variant, s, geom, dry) : tfa::launch_fwd_varlen<_Float16, 64>(a, causal, f32out, variant, s, geom, dry);
-  return (int)e;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+// the kernel variant (rule == false) or rounding rule (true) of a call, or its TFA_ERR_*.  A dry run reports a HIP error (a positive status) only where a
+// launcher refuses a variant: tfa_set_variant's timing-only ablation numbers, which a product build accepts but carries no kernel for; they read as TFA_ERR_SHAPE
+// here.  (The varlen routes never get there: they refuse every variant but 30 and 32 first.)
+int variant_or_rule(const FwdCall& c, bool rule) {
+  tfa::LaunchGeom g{0, 0, 0};
+  int v = -1, r = -1;
+  const int st = route(c, nullptr, &g, true, &v, &r);
+  if (st != TFA_OK) return st > 0 ? TFA_ERR_SHAPE : st;
+  return rule ? r : v;
 }
 
 }  // namespace
@@ -502,15 +501,7 @@ int tfa_fwd_bhnd_f32out(const void* q, const void* k, const void* v, float* out,
   return run(&p, stream, nullptr, false);
 }
 
-int tfa_fwd_plan(const tfa_fwd_params* p, int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g = {0, 0, 0};
-  const int st = run(p, nullptr, &g, true);
-  if (st != 0) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
-}
+int tfa_fwd_plan(const tfa_fwd_params* p, int* grid, int* block, int* lds_bytes) { return plan({p, nullptr, nullptr}, grid, block, lds_bytes); }
 
 // ---- side streams for the one-launch-per-chunk route of tfa_fwd_splitkv ----------------------------------------------------
 // The chunk launches of one call are independent; on ONE stream they run one after the other and a decode-like problem (few
@@ -653,14 +644,13 @@ int tfa_fwd_splitkv(const tfa_fwd_params* p, int splits, float* workspace, void*
   a.lse_part_stride = rows;
   if ((long long)a.nbh * a.nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e;
   const bool causal = q.is_causal != 0;                   // (the packed one-row problem is non-causal)
-  if (p->D > 128)                                          // head dims 136..256: the same kernel 256 wide (one wave per SIMD, hand-owned accumulators)
-    e = (p->dtype == TFA_BF16) ? tfa::launch_splitkv_wide<__bf16>(a, causal, s, nullptr, false) : tfa::launch_splitkv_wide<_Float16>(a, causal, s, nullptr, false);
-  else if (p->dtype == TFA_BF16)
-    e = (p->D > 64) ? tfa::launch_fwd<__bf16, 128>(a, causal, true, variant, s, nullptr, false) : tfa::launch_fwd<__bf16, 64>(a, causal, true, variant, s, nullptr, false);
-  else
-    e = (p->D > 64) ? tfa::launch_fwd<_Float16, 128>(a, causal, true, variant, s, nullptr, false) : tfa::launch_fwd<_Float16, 64>(a, causal, true, variant, s, nullptr, false);
+  // head dims 136..256: the same kernel 256 wide (one wave per SIMD, hand-owned accumulators)
+  const hipError_t e = tfa::by_dtype_width<64, 128, 256>(p->dtype, p->D, [&](auto k) {
+    using T = typename decltype(k)::T;
+    if constexpr (decltype(k)::W == 256) return tfa::launch_splitkv_wide<T>(a, causal, s, nullptr, false);
+    else return tfa::launch_fwd<T, decltype(k)::W>(a, causal, true, variant, s, nullptr, false);
+  });
   if (e != hipSuccess) return (int)e;
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->out_dtype, p->lse, stream);
 }
@@ -691,95 +681,46 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   return s >= 2 ? (int)s : 1;
 }
 
-int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return run_varlen(p, stream, nullptr, false); }
-int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = run_varlen(p, nullptr, &g, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
-}
-int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p) {
-  int v = -1;
-  const int st = run_varlen(p, nullptr, nullptr, true, &v);
-  return st != TFA_OK ? st : v;
-}
-int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p) {
-  int r = -1;
-  const int st = run_varlen(p, nullptr, nullptr, true, nullptr, &r);
-  return st != TFA_OK ? st : r;
-}
+int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return route({nullptr, p, nullptr}, stream); }
+int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes) { return plan({nullptr, p, nullptr}, grid, block, lds_bytes); }
+int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p) { return variant_or_rule({nullptr, p, nullptr}, false); }
+int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p) { return variant_or_rule({nullptr, p, nullptr}, true); }
 
 int tfa_fwd_local(const tfa_fwd_params* p, int window_left, int window_right, void* stream) {
-  return run_local(p, window_left, window_right, stream, nullptr, false);
+  const int w[2] = {window_left, window_right};
+  return route({p, nullptr, w}, stream);
 }
 int tfa_fwd_local_plan(const tfa_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = run_local(p, window_left, window_right, nullptr, &g, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
+  const int w[2] = {window_left, window_right};
+  return plan({p, nullptr, w}, grid, block, lds_bytes);
 }
 int tfa_fwd_local_variant(const tfa_fwd_params* p, int window_left, int window_right) {
-  tfa::LaunchGeom g{0, 0, 0};
-  int v = -1;
-  const int st = run_local(p, window_left, window_right, nullptr, &g, true, &v);
-  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
-  return v;
+  const int w[2] = {window_left, window_right};
+  return variant_or_rule({p, nullptr, w}, false);
 }
 int tfa_fwd_local_rounding_rule(const tfa_fwd_params* p, int window_left, int window_right) {
-  tfa::LaunchGeom g{0, 0, 0};
-  int v = -1, r = -1;
-  const int st = run_local(p, window_left, window_right, nullptr, &g, true, &v, &r);
-  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
-  return r;
+  const int w[2] = {window_left, window_right};
+  return variant_or_rule({p, nullptr, w}, true);
 }
 int tfa_fwd_varlen_local(const tfa_varlen_fwd_params* p, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};
-  return run_varlen(p, stream, nullptr, false, nullptr, nullptr, w);
+  return route({nullptr, p, w}, stream);
 }
 int tfa_fwd_varlen_local_plan(const tfa_varlen_fwd_params* p, int window_left, int window_right, int* grid, int* block, int* lds_bytes) {
   const int w[2] = {window_left, window_right};
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = run_varlen(p, nullptr, &g, true, nullptr, nullptr, w);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
+  return plan({nullptr, p, w}, grid, block, lds_bytes);
 }
 int tfa_fwd_varlen_local_variant(const tfa_varlen_fwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
-  int v = -1;
-  const int st = run_varlen(p, nullptr, nullptr, true, &v, nullptr, w);
-  return st != TFA_OK ? st : v;
+  return variant_or_rule({nullptr, p, w}, false);
 }
 int tfa_fwd_varlen_local_rounding_rule(const tfa_varlen_fwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
-  int r = -1;
-  const int st = run_varlen(p, nullptr, nullptr, true, nullptr, &r, w);
-  return st != TFA_OK ? st : r;
+  return variant_or_rule({nullptr, p, w}, true);
 }
 
-int tfa_fwd_variant(const tfa_fwd_params* p) {
-  tfa::LaunchGeom g = {0, 0, 0};
-  int variant = -1;                                       // run()'s final choice (after GQA packing and its fall-back)
-  const int st = run(p, nullptr, &g, true, &variant);
-  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
-  return variant;
-}
-
-int tfa_fwd_rounding_rule(const tfa_fwd_params* p) {
-  tfa::LaunchGeom g = {0, 0, 0};
-  int variant = -1, rule = -1;
-  const int st = run(p, nullptr, &g, true, &variant, &rule);
-  if (st != 0) return st > 0 ? TFA_ERR_SHAPE : st;
-  return rule;
-}
+int tfa_fwd_variant(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, false); }   // (run()'s final choice, after GQA packing and its fall-back)
+int tfa_fwd_rounding_rule(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, true); }
 
 int tfa_fwd_time(const tfa_fwd_params* p, int warmup, int iters, void* stream, float* avg_ms) {
   if (!avg_ms || iters <= 0 || warmup < 0) return TFA_ERR_NULL;

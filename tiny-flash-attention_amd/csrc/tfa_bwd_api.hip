@@ -70,6 +70,59 @@ int check_strides(const int64_t* st, int d, int esize) {
   return TFA_OK;
 }
 
+// The preconditions every backward form shares, in tfa_bwd's order (an input with several faults gets the status of the first).  v is the problem as the
+// kernels see it — varlen: ONE sequence of max_seqlen_q x max_seqlen_k rows, batch stride 0 (run_bwd_varlen).  What differs between the forms:
+//   form_ptrs:  the form's own pointers are set (varlen: cu_seqlens);
+//   form_shape: the form's own shape conditions hold (a fixed-length window: Nq + Nk < 2^28; varlen: totals > 0, flags and reserved_ 0);
+//   max_d:      the widest head dim (256 tfa_bwd, 128 the varlen and local forms);
+//   window_st:  the varlen window's status (window_form and its 2^28 limit), reported behind the scale;
+//   stat_align: bytes of alignment of lse and delta (16 fixed-length: read as 16-byte vectors; 4 varlen);
+//   rows:       rows of lse and delta (B*H*Nq, varlen H*total_q).
+int check_bwd(const tfa_bwd_params& v, bool form_ptrs, bool form_shape, int max_d, int window_st, int stat_align, int64_t rows) {
+  if (!v.q || !v.k || !v.v || !v.out || !v.dout || !v.lse || !v.dq || !v.dk || !v.dv || !v.delta || !form_ptrs) return TFA_ERR_NULL;
+  if (v.dtype != TFA_F16 && v.dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (v.grad_dtype != v.dtype && v.grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
+  if (v.D < 8 || v.D > max_d || (v.D % 8) != 0) return TFA_ERR_HEAD_DIM;   // kernels are 64, 128 and 256 wide; BArgs::dv = the valid part
+  if (v.B <= 0 || v.H <= 0 || v.Hk <= 0 || v.Nq <= 0 || v.Nk <= 0 || v.H % v.Hk != 0 || !form_shape) return TFA_ERR_SHAPE;
+  if (!(v.softmax_scale > 0.f) || !isfinite(v.softmax_scale)) return TFA_ERR_SCALE;
+  if (window_st != TFA_OK) return window_st;
+  const int gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
+  const int64_t* st[8] = {v.q_stride, v.k_stride, v.v_stride, v.o_stride, v.do_stride, v.dq_stride, v.dk_stride, v.dv_stride};
+  for (int i = 0; i < 8; ++i) {
+    const int c = check_strides(st[i], v.D, i < 5 ? 2 : gsz);
+    if (c) return c;
+  }
+  const uintptr_t al = (uintptr_t)v.q | (uintptr_t)v.k | (uintptr_t)v.v | (uintptr_t)v.out | (uintptr_t)v.dout | (uintptr_t)v.dq |
+                       (uintptr_t)v.dk | (uintptr_t)v.dv;
+  if (al & 15) return TFA_ERR_ALIGN;
+  if (((uintptr_t)v.lse | (uintptr_t)v.delta) & (stat_align - 1)) return TFA_ERR_ALIGN;
+  if (rows >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
+  return TFA_OK;
+}
+
+// The kernel arguments every launch of v shares — everything but the gradients — after the gradients' slices pass the same size rule as the inputs.
+// bigp: slice_bytes's (nullptr: the form has no windowed instantiation).
+int fill_args(const tfa_bwd_params& v, int* bigp, tfa::BArgs* a) {
+  memset(a, 0, sizeof(*a));
+  const int esz = 2, gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
+  // (out: read by the dQ launch when it forms delta and by the delta kernel; fill() is also what validates its strides and slice size for every form)
+  if (!fill(&a->q, v.q, v.q_stride, v.Nq, v.D, esz, bigp) || !fill(&a->k, v.k, v.k_stride, v.Nk, v.D, esz, bigp) ||
+      !fill(&a->v, v.v, v.v_stride, v.Nk, v.D, esz, bigp) || !fill(&a->out, v.out, v.o_stride, v.Nq, v.D, esz, bigp) ||
+      !fill(&a->dout, v.dout, v.do_stride, v.Nq, v.D, esz, bigp))
+    return TFA_ERR_STRIDE;
+  unsigned tmp;
+  unsigned long long tmpf;
+  if (!slice_bytes(v.Nq, v.dq_stride[2], v.D, gsz, &tmp, &tmpf, bigp) || !slice_bytes(v.Nk, v.dk_stride[2], v.D, gsz, &tmp, &tmpf, bigp) ||
+      !slice_bytes(v.Nk, v.dv_stride[2], v.D, gsz, &tmp, &tmpf, bigp))
+    return TFA_ERR_STRIDE;
+  a->lse = v.lse; a->delta = v.delta; a->delta_w = v.delta;
+  a->B = v.B; a->H = v.H; a->Hk = v.Hk; a->Nq = v.Nq; a->Nk = v.Nk;
+  a->dv = v.D;
+  a->scale = v.softmax_scale;
+  a->scale_log2 = v.softmax_scale * 1.4426950408889634f;
+  return TFA_OK;
+}
+
 // bytes of the dS workspace for *p, 0 when a head's slab (roundup(Nk,128) x roundup(Nq,256) x 2 bytes) would not fit one descriptor
 long long ws_bytes(const tfa_bwd_params* p, int* nk_pad, int* nq_pad) {
   const long long nk = ((long long)p->Nk + 127) / 128 * 128, nq = ((long long)p->Nq + 255) / 256 * 256;
@@ -83,49 +136,20 @@ long long ws_bytes(const tfa_bwd_params* p, int* nk_pad, int* nq_pad) {
 int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need = nullptr) {
   if (ws_need) *ws_need = 0;
   if (!p) return TFA_ERR_NULL;
-  if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta) return TFA_ERR_NULL;
-  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
-  if (p->grad_dtype != p->dtype && p->grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
-  if (p->D < 8 || p->D > 256 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;   // kernels are 64, 128 and 256 wide; BArgs::dv = the valid part
-  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->Nk <= 0 || p->H % p->Hk != 0) return TFA_ERR_SHAPE;
-  if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
-  const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
-  const int64_t* in_st[5] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride};
-  for (int i = 0; i < 5; ++i) { const int st = check_strides(in_st[i], p->D, esz); if (st) return st; }
-  const int64_t* g_st[3] = {p->dq_stride, p->dk_stride, p->dv_stride};
-  for (int i = 0; i < 3; ++i) { const int st = check_strides(g_st[i], p->D, gsz); if (st) return st; }
-  const uintptr_t al = (uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out | (uintptr_t)p->dout | (uintptr_t)p->dq |
-                       (uintptr_t)p->dk | (uintptr_t)p->dv;
-  if (al & 15) return TFA_ERR_ALIGN;
-  if (((uintptr_t)p->lse | (uintptr_t)p->delta) & 15) return TFA_ERR_ALIGN;   // read as 16-byte vectors
-  if ((int64_t)p->B * p->H * p->Nq >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
-
+  int st = check_bwd(*p, true, true, 256, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
+  if (st) return st;
+  const int gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
   tfa::BArgs a;
-  memset(&a, 0, sizeof(a));
   // slices of 2 GiB and more (long (B,N,H,D) tensors): the windowed instantiations of the dQ launch and of the fused dK/dV launch —
   // not with the two-launch debug form at head dims up to 128 (its dK / dV launches have no windowed instantiation; the 256-wide kernel has one for each of its three launches)
   const bool can_big = p->D > 128 || !(g_bwd_split & 1);
   int big = (g_bwd_split & 2) ? 1 : 0;        // tests: the windowed instantiations on a small problem
   int* bigp = can_big ? &big : nullptr;
-  if (!fill(&a.q, p->q, p->q_stride, p->Nq, p->D, esz, bigp)) return TFA_ERR_STRIDE;
-  if (!fill(&a.k, p->k, p->k_stride, p->Nk, p->D, esz, bigp)) return TFA_ERR_STRIDE;
-  if (!fill(&a.v, p->v, p->v_stride, p->Nk, p->D, esz, bigp)) return TFA_ERR_STRIDE;
-  if (!fill(&a.dout, p->dout, p->do_stride, p->Nq, p->D, esz, bigp)) return TFA_ERR_STRIDE;
-  {   // out (read by the delta kernel through plain 64-bit pointers) and the gradients: same rule
-    unsigned tmp; unsigned long long tmpf;
-    if (!slice_bytes(p->Nq, p->o_stride[2], p->D, esz, &tmp, &tmpf, bigp) || !slice_bytes(p->Nq, p->dq_stride[2], p->D, gsz, &tmp, &tmpf, bigp) ||
-        !slice_bytes(p->Nk, p->dk_stride[2], p->D, gsz, &tmp, &tmpf, bigp) || !slice_bytes(p->Nk, p->dv_stride[2], p->D, gsz, &tmp, &tmpf, bigp))
-      return TFA_ERR_STRIDE;
-  }
+  st = fill_args(*p, bigp, &a);
+  if (st) return st;
   if (big && !can_big) return TFA_ERR_STRIDE;
   a.big = big;
-  a.lse = p->lse; a.delta = p->delta;
-  a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = p->Nq; a.Nk = p->Nk;
-  a.dv = p->D;
-  const bool wide = p->D > 64;
   const bool wide256 = p->D > 128;          // head dims 136..256: one wave per SIMD, 128-row resident blocks, three single-gradient launches
-  a.scale = p->softmax_scale;
-  a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
   const bool causal = p->is_causal != 0, f32 = p->grad_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
@@ -137,14 +161,16 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
     m.nrb = (n_res + res_rows - 1) / res_rows;
     const int64_t grid = (int64_t)p->B * h_res * m.nrb;
     if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-    hipError_t e;
-    if (p->dtype == TFA_BF16)
-      e = wide256 ? tfa::launch_bwd<__bf16, 256>(m, mode, (int)grid, causal, f32, s, dry)
-          : wide  ? tfa::launch_bwd<__bf16, 128>(m, mode, (int)grid, causal, f32, s, dry) : tfa::launch_bwd<__bf16, 64>(m, mode, (int)grid, causal, f32, s, dry);
-    else
-      e = wide256 ? tfa::launch_bwd<_Float16, 256>(m, mode, (int)grid, causal, f32, s, dry)
-          : wide  ? tfa::launch_bwd<_Float16, 128>(m, mode, (int)grid, causal, f32, s, dry) : tfa::launch_bwd<_Float16, 64>(m, mode, (int)grid, causal, f32, s, dry);
-    return (int)e;
+    return (int)tfa::by_dtype_width<64, 128, 256>(p->dtype, p->D, [&](auto k) {
+      return tfa::launch_bwd<typename decltype(k)::T, decltype(k)::W>(m, mode, (int)grid, causal, f32, s, dry);
+    });
+  };
+
+  // the fused dK/dV launch (head dims up to 128; a.ws: the form that also writes dS)
+  auto launch_kv = [&](const tfa::BArgs& m, int grid) {
+    return tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
+      return tfa::launch_bwd_kv<typename decltype(k)::T, decltype(k)::W>(m, grid, causal, f32, s, dry);
+    });
   };
 
   // ---- with a workspace: dK/dV launch that also writes dS, then dQ = scale * dS . K (5 GEMM units) -----------------------------
@@ -168,24 +194,15 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
   // (BArgs::fuse_delta; 51 us and one pass over dO less at config 3) — unless the fused dK/dV launch runs FIRST (the workspace form), or
   // tfa_debug_bwd_split value 8 (bit 3) asks for the launch of its own (A/B, tests)
   const bool fuse_delta = !use_ws && !(g_bwd_split & 8);
-  // (always: the dQ launch reads O only when it forms delta, but fill() is also what validates out's strides and slice size for every form)
-  if (!fill(&a.out, p->out, p->o_stride, p->Nq, p->D, esz, bigp)) return TFA_ERR_STRIDE;
-  a.delta_w = p->delta;
   a.fuse_delta = fuse_delta ? 1 : 0;
   if (!fuse_delta)
   {
     const long long os[3] = {p->o_stride[0], p->o_stride[1], p->o_stride[2]};
     const long long ds[3] = {p->do_stride[0], p->do_stride[1], p->do_stride[2]};
     const long long rows = (long long)p->B * p->H * p->Nq;
-    hipError_t e;
-    if (p->dtype == TFA_BF16)
-      e = wide256 ? tfa::launch_delta<__bf16, 256>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry)
-          : wide  ? tfa::launch_delta<__bf16, 128>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry)
-                  : tfa::launch_delta<__bf16, 64>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry);
-    else
-      e = wide256 ? tfa::launch_delta<_Float16, 256>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry)
-          : wide  ? tfa::launch_delta<_Float16, 128>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry)
-                  : tfa::launch_delta<_Float16, 64>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry);
+    const hipError_t e = tfa::by_dtype_width<64, 128, 256>(p->dtype, p->D, [&](auto k) {
+      return tfa::launch_delta<typename decltype(k)::T, decltype(k)::W>(p->out, p->dout, p->delta, os, ds, p->H, p->Nq, rows, p->D, s, dry);
+    });
     if (e != hipSuccess) return (int)e;
   }
   if (use_ws) {
@@ -197,11 +214,7 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
     m.nrb = (p->Nk + 127) / 128;
     int64_t grid = (int64_t)p->B * p->Hk * m.nrb;
     if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-    hipError_t e;
-    if (p->dtype == TFA_BF16)
-      e = wide ? tfa::launch_bwd_kv<__bf16, 128>(m, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_kv<__bf16, 64>(m, (int)grid, causal, f32, s, dry);
-    else
-      e = wide ? tfa::launch_bwd_kv<_Float16, 128>(m, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_kv<_Float16, 64>(m, (int)grid, causal, f32, s, dry);
+    hipError_t e = launch_kv(m, (int)grid);
     if (e != hipSuccess) return (int)e;
     tfa::BArgs d = a;
     d.ws = p->workspace; d.ws_nk = nk_pad; d.ws_nq = nq_pad;
@@ -210,13 +223,12 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
     d.nrb = (p->Nq + 255) / 256;
     grid = (int64_t)p->B * p->H * d.nrb;
     if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-    if (p->dtype == TFA_BF16)
-      e = wide ? tfa::launch_bwd_dq_ws<__bf16, 128>(d, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_dq_ws<__bf16, 64>(d, (int)grid, causal, f32, s, dry);
-    else
-      e = wide ? tfa::launch_bwd_dq_ws<_Float16, 128>(d, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_dq_ws<_Float16, 64>(d, (int)grid, causal, f32, s, dry);
+    e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
+      return tfa::launch_bwd_dq_ws<typename decltype(k)::T, decltype(k)::W>(d, (int)grid, causal, f32, s, dry);
+    });
     return (int)e;
   }
-  int st = launch(tfa::BWD_DQ, p->dq, p->dq_stride, p->Nq, p->H);
+  st = launch(tfa::BWD_DQ, p->dq, p->dq_stride, p->Nq, p->H);
   if (st) return st;
   if ((g_bwd_split & 1) || wide256) {                            // head dims above 128, and debug / A-B: the two single-gradient launches (S computed twice)
     st = launch(tfa::BWD_DK, p->dk, p->dk_stride, p->Nk, p->Hk);
@@ -233,185 +245,96 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
   m.nrb = (p->Nk + kv_keys - 1) / kv_keys;
   const int64_t grid = (int64_t)p->B * p->Hk * m.nrb;
   if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-  hipError_t e;
-  if (p->dtype == TFA_BF16)
-    e = wide ? tfa::launch_bwd_kv<__bf16, 128>(m, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_kv<__bf16, 64>(m, (int)grid, causal, f32, s, dry);
-  else
-    e = wide ? tfa::launch_bwd_kv<_Float16, 128>(m, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_kv<_Float16, 64>(m, (int)grid, causal, f32, s, dry);
-  return (int)e;
+  return (int)launch_kv(m, (int)grid);
 }
 
-// Packed variable-length batches (include/tfa.h: tfa_bwd_varlen): the dQ launch (which also forms delta) and the fused dK/dV launch, each in its VARLEN
-// instantiation.  As in the forward (tfa_api.hip: run_varlen) the host validates ONE sequence of max_seqlen_q x max_seqlen_k rows — every slice must fit one
-// descriptor, there is no windowed varlen form — sizes the grids from it and never reads cu_seqlens: each work item reads its sequence's bounds itself.
-// Local (sliding-window) attention: the window's form as the forward sees it (tfa_api.hip: window_form — the same normalisation, restated here because the two
-// translation units share no host code): FULL / CAUSAL run tfa_bwd's own launches, a true window the LOCAL instantiations
-enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
-int window_form(int* left, int* right, bool causal, int nq, int nk) {
-  if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
-  if (causal) *right = 0;
-  if (*left >= nk - 1) *left = -1;
-  if (*left < 0 && *right == 0) return WIN_CAUSAL;
-  if (*right >= nq - 1) *right = -1;
-  return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
-}
-void set_window(tfa::BArgs* a, int left, int right, int nq, int nk) {   // (both sides >= 0: an unbounded one as nq + nk)
-  a->win_left = left < 0 ? nq + nk : left;
-  a->win_right = right < 0 ? nq + nk : right;
-}
-
-// the dQ launch (it forms delta) and the fused dK/dV launch of a true window, fixed-length or varlen: a holds everything but the gradients
-int launch_local(const tfa::BArgs& a, bool varlen, int D, int dtype, bool f32, void* dq, const int64_t* dq_st, void* dk, const int64_t* dk_st, void* dv,
-                 const int64_t* dv_st, int nq, int nk, int nbatch, int H, int Hk, void* stream, bool dry) {
-  const int gsz = f32 ? 4 : 2;
-  const bool wide = D > 64, bf16 = dtype == TFA_BF16;
+// The varlen and local forms: the dQ launch (which forms delta) and then the fused dK/dV launch of the form kernels (VARLEN / LOCAL instantiations:
+// tfa_bwd_form_inst.inc).  a holds everything but the gradients; v is the problem as the kernels see it (run_bwd_varlen: one sequence, batch stride 0).
+int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, void* stream, bool dry) {
+  const int gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
+  const bool causal = v.is_causal != 0, f32 = v.grad_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   auto run = [&](const tfa::BArgs& m, bool keys, int64_t grid) -> int {
     if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-    hipError_t e;
-    if (varlen)
-      e = bf16 ? (wide ? tfa::launch_bwd_local<__bf16, 128, true>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<__bf16, 64, true>(m, keys, (int)grid, f32, s, dry))
-               : (wide ? tfa::launch_bwd_local<_Float16, 128, true>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<_Float16, 64, true>(m, keys, (int)grid, f32, s, dry));
-    else
-      e = bf16 ? (wide ? tfa::launch_bwd_local<__bf16, 128, false>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<__bf16, 64, false>(m, keys, (int)grid, f32, s, dry))
-               : (wide ? tfa::launch_bwd_local<_Float16, 128, false>(m, keys, (int)grid, f32, s, dry) : tfa::launch_bwd_local<_Float16, 64, false>(m, keys, (int)grid, f32, s, dry));
-    return (int)e;
-  };
-  tfa::BArgs d = a;
-  d.grad = dq; d.gs_b = dq_st[0]; d.gs_h = dq_st[1]; d.gs_n = dq_st[2];
-  if (!slice_bytes(nq, d.gs_n, D, gsz, &d.g_bytes)) return TFA_ERR_STRIDE;
-  d.nrb = (nq + 255) / 256;
-  tfa::BArgs m = a;
-  m.grad = dk; m.gs_b = dk_st[0]; m.gs_h = dk_st[1]; m.gs_n = dk_st[2];
-  m.grad2 = dv; m.g2s_b = dv_st[0]; m.g2s_h = dv_st[1]; m.g2s_n = dv_st[2];
-  if (!slice_bytes(nk, m.gs_n, D, gsz, &m.g_bytes) || !slice_bytes(nk, m.g2s_n, D, gsz, &m.g2_bytes)) return TFA_ERR_STRIDE;
-  constexpr int kv_keys = 32 * TFA_BWD_KV_KG_OF(false);
-  m.nrb = (nk + kv_keys - 1) / kv_keys;
-  const int st_dq = run(d, false, (int64_t)nbatch * H * d.nrb);
-  if (st_dq) return st_dq;
-  return run(m, true, (int64_t)nbatch * Hk * m.nrb);
-}
-
-int run_bwd_local(const tfa_bwd_params* p, int left, int right, void* stream, bool dry) {
-  if (!p) return TFA_ERR_NULL;
-  const int form = window_form(&left, &right, p->is_causal != 0, p->Nq, p->Nk);
-  if (form < 0) return form;
-  if (form != WIN_LOCAL) {
-    tfa_bwd_params f = *p;
-    f.is_causal = form == WIN_CAUSAL;
-    return run_bwd(&f, stream, dry);
-  }
-  if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta) return TFA_ERR_NULL;
-  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
-  if (p->grad_dtype != p->dtype && p->grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
-  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
-  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->Nk <= 0 || p->H % p->Hk != 0) return TFA_ERR_SHAPE;
-  if ((int64_t)p->Nq + p->Nk >= (1 << 28)) return TFA_ERR_SHAPE;
-  if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
-  const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
-  const int64_t* in_st[5] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride};
-  for (int i = 0; i < 5; ++i) { const int st = check_strides(in_st[i], p->D, esz); if (st) return st; }
-  const int64_t* g_st[3] = {p->dq_stride, p->dk_stride, p->dv_stride};
-  for (int i = 0; i < 3; ++i) { const int st = check_strides(g_st[i], p->D, gsz); if (st) return st; }
-  const uintptr_t al = (uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out | (uintptr_t)p->dout | (uintptr_t)p->dq |
-                       (uintptr_t)p->dk | (uintptr_t)p->dv;
-  if (al & 15) return TFA_ERR_ALIGN;
-  if (((uintptr_t)p->lse | (uintptr_t)p->delta) & 15) return TFA_ERR_ALIGN;
-  if ((int64_t)p->B * p->H * p->Nq >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
-  tfa::BArgs a;
-  memset(&a, 0, sizeof(a));
-  // (no windowed local form: every slice must fit one descriptor — TFA_ERR_STRIDE otherwise)
-  if (!fill(&a.q, p->q, p->q_stride, p->Nq, p->D, esz, nullptr) || !fill(&a.k, p->k, p->k_stride, p->Nk, p->D, esz, nullptr) ||
-      !fill(&a.v, p->v, p->v_stride, p->Nk, p->D, esz, nullptr) || !fill(&a.out, p->out, p->o_stride, p->Nq, p->D, esz, nullptr) ||
-      !fill(&a.dout, p->dout, p->do_stride, p->Nq, p->D, esz, nullptr))
-    return TFA_ERR_STRIDE;
-  a.lse = p->lse; a.delta = p->delta; a.delta_w = p->delta;
-  a.fuse_delta = 1;                                  // (the dQ launch forms delta)
-  a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = p->Nq; a.Nk = p->Nk;
-  a.dv = p->D;
-  a.scale = p->softmax_scale;
-  a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
-  set_window(&a, left, right, p->Nq, p->Nk);
-  return launch_local(a, false, p->D, p->dtype, p->grad_dtype == TFA_F32, p->dq, p->dq_stride, p->dk, p->dk_stride, p->dv, p->dv_stride, p->Nq, p->Nk, p->B,
-                      p->H, p->Hk, stream, dry);
-}
-
-// win: nullptr, or the local window {left, right} of tfa_bwd_varlen_local
-int run_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream, bool dry, const int* win = nullptr) {
-  if (!p) return TFA_ERR_NULL;
-  if (!p->q || !p->k || !p->v || !p->out || !p->dout || !p->lse || !p->dq || !p->dk || !p->dv || !p->delta || !p->cu_seqlens_q || !p->cu_seqlens_k)
-    return TFA_ERR_NULL;
-  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
-  if (p->grad_dtype != p->dtype && p->grad_dtype != TFA_F32) return TFA_ERR_DTYPE;
-  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
-  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
-  if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
-  if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;
-  if (!(p->softmax_scale > 0.f) || !isfinite(p->softmax_scale)) return TFA_ERR_SCALE;
-  int left = -1, right = -1, form = p->is_causal ? WIN_CAUSAL : WIN_FULL;
-  if (win) {
-    left = win[0];
-    right = win[1];
-    form = window_form(&left, &right, p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
-    if (form < 0) return form;
-    if (form == WIN_LOCAL && (int64_t)p->max_seqlen_q + p->max_seqlen_k >= (1 << 28)) return TFA_ERR_SHAPE;
-  }
-  const int esz = 2, gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
-  // (head, row) strides as the (batch, head, row) triples of one sequence: batch stride 0
-  int64_t st[8][3];
-  const int64_t* src[8] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride, p->dq_stride, p->dk_stride, p->dv_stride};
-  for (int i = 0; i < 8; ++i) {
-    st[i][0] = 0; st[i][1] = src[i][0]; st[i][2] = src[i][1];
-    const int c = check_strides(st[i], p->D, i < 5 ? esz : gsz);
-    if (c) return c;
-  }
-  const uintptr_t al = (uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->out | (uintptr_t)p->dout | (uintptr_t)p->dq |
-                       (uintptr_t)p->dk | (uintptr_t)p->dv;
-  if (al & 15) return TFA_ERR_ALIGN;
-  if (((uintptr_t)p->lse | (uintptr_t)p->delta) & 3) return TFA_ERR_ALIGN;
-  if ((int64_t)p->H * p->total_q >= (int64_t)0x1fffffff) return TFA_ERR_SHAPE;
-
-  tfa::BArgs a;
-  memset(&a, 0, sizeof(a));
-  const int nq = p->max_seqlen_q, nk = p->max_seqlen_k;
-  if (!fill(&a.q, p->q, st[0], nq, p->D, esz, nullptr) || !fill(&a.k, p->k, st[1], nk, p->D, esz, nullptr) || !fill(&a.v, p->v, st[2], nk, p->D, esz, nullptr) ||
-      !fill(&a.out, p->out, st[3], nq, p->D, esz, nullptr) || !fill(&a.dout, p->dout, st[4], nq, p->D, esz, nullptr))
-    return TFA_ERR_STRIDE;
-  a.lse = p->lse; a.delta = p->delta; a.delta_w = p->delta;
-  a.fuse_delta = 1;                                  // (the dQ launch forms delta; no separate delta launch in varlen form)
-  a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = nq; a.Nk = nk;
-  a.dv = p->D;
-  a.scale = p->softmax_scale;
-  a.scale_log2 = p->softmax_scale * 1.4426950408889634f;
-  a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;
-  a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
-  const bool causal = form == WIN_CAUSAL, f32 = p->grad_dtype == TFA_F32, wide = p->D > 64, bf16 = p->dtype == TFA_BF16;
-  if (form == WIN_LOCAL) {
-    set_window(&a, left, right, nq, nk);
-    return launch_local(a, true, p->D, p->dtype, f32, p->dq, st[5], p->dk, st[6], p->dv, st[7], nq, nk, p->B, p->H, p->Hk, stream, dry);
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  auto run = [&](const tfa::BArgs& m, bool keys, int64_t grid) -> int {
-    if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
-    const hipError_t e = bf16 ? (wide ? tfa::launch_bwd_varlen<__bf16, 128>(m, keys, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_varlen<__bf16, 64>(m, keys, (int)grid, causal, f32, s, dry))
-                              : (wide ? tfa::launch_bwd_varlen<_Float16, 128>(m, keys, (int)grid, causal, f32, s, dry) : tfa::launch_bwd_varlen<_Float16, 64>(m, keys, (int)grid, causal, f32, s, dry));
-    return (int)e;
+    return (int)tfa::by_dtype_width<64, 128>(v.dtype, v.D, [&](auto k) {
+      using T = typename decltype(k)::T;
+      constexpr int W = decltype(k)::W;
+      if (!local) return tfa::launch_bwd_form<T, W, true, false>(m, keys, (int)grid, causal, f32, s, dry);   // (no window: always varlen here)
+      return varlen ? tfa::launch_bwd_form<T, W, true, true>(m, keys, (int)grid, causal, f32, s, dry)
+                    : tfa::launch_bwd_form<T, W, false, true>(m, keys, (int)grid, causal, f32, s, dry);
+    });
   };
   // dQ (and delta): 256-row resident blocks of each (sequence, query head)
   tfa::BArgs d = a;
-  d.grad = p->dq; d.gs_b = 0; d.gs_h = st[5][1]; d.gs_n = st[5][2];
-  if (!slice_bytes(nq, d.gs_n, p->D, gsz, &d.g_bytes)) return TFA_ERR_STRIDE;   // (no g_full: its bytes hold cu_q / cu_k)
-  d.nrb = (nq + 255) / 256;
+  d.grad = v.dq; d.gs_b = v.dq_stride[0]; d.gs_h = v.dq_stride[1]; d.gs_n = v.dq_stride[2];
+  if (!slice_bytes(v.Nq, d.gs_n, v.D, gsz, &d.g_bytes)) return TFA_ERR_STRIDE;   // (no g_full: varlen keeps cu_q / cu_k in its bytes)
+  d.nrb = (v.Nq + 255) / 256;
   // dK and dV in one launch: 32 * KG resident keys of each (sequence, K/V head)
   tfa::BArgs m = a;
-  m.grad = p->dk; m.gs_b = 0; m.gs_h = st[6][1]; m.gs_n = st[6][2];
-  m.grad2 = p->dv; m.g2s_b = 0; m.g2s_h = st[7][1]; m.g2s_n = st[7][2];
-  if (!slice_bytes(nk, m.gs_n, p->D, gsz, &m.g_bytes) || !slice_bytes(nk, m.g2s_n, p->D, gsz, &m.g2_bytes)) return TFA_ERR_STRIDE;
+  m.grad = v.dk; m.gs_b = v.dk_stride[0]; m.gs_h = v.dk_stride[1]; m.gs_n = v.dk_stride[2];
+  m.grad2 = v.dv; m.g2s_b = v.dv_stride[0]; m.g2s_h = v.dv_stride[1]; m.g2s_n = v.dv_stride[2];
+  if (!slice_bytes(v.Nk, m.gs_n, v.D, gsz, &m.g_bytes) || !slice_bytes(v.Nk, m.g2s_n, v.D, gsz, &m.g2_bytes)) return TFA_ERR_STRIDE;
   constexpr int kv_keys = 32 * TFA_BWD_KV_KG_OF(false);
-  m.nrb = (nk + kv_keys - 1) / kv_keys;
-  const int st_dq = run(d, false, (int64_t)p->B * p->H * d.nrb);
+  m.nrb = (v.Nk + kv_keys - 1) / kv_keys;
+  const int st_dq = run(d, false, (int64_t)v.B * v.H * d.nrb);
   if (st_dq) return st_dq;
-  return run(m, true, (int64_t)p->B * p->Hk * m.nrb);
+  return run(m, true, (int64_t)v.B * v.Hk * m.nrb);
+}
+
+// Local (sliding-window) attention, tfa_bwd_local: the window's form as the forward sees it (tfa_host_util.h: window_form) — FULL / CAUSAL run tfa_bwd's own
+// launches, a true window the LOCAL instantiations (every slice within one descriptor: no windowed local form)
+int run_bwd_local(const tfa_bwd_params* p, const int* w, void* stream, bool dry) {
+  if (!p) return TFA_ERR_NULL;
+  int win[2] = {w[0], w[1]};
+  const int form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->Nq, p->Nk);
+  if (form < 0) return form;
+  if (form != tfa::WIN_LOCAL) {
+    tfa_bwd_params f = *p;
+    f.is_causal = form == tfa::WIN_CAUSAL;
+    return run_bwd(&f, stream, dry);
+  }
+  int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
+  if (st) return st;
+  tfa::BArgs a;
+  st = fill_args(*p, nullptr, &a);
+  if (st) return st;
+  a.fuse_delta = 1;                                  // (the dQ launch forms delta)
+  tfa::set_window(&a, win[0], win[1], p->Nq, p->Nk);
+  return launch_form_pair(a, *p, false, true, stream, dry);
+}
+
+// Packed variable-length batches (include/tfa.h: tfa_bwd_varlen, tfa_bwd_varlen_local — w: the window, or nullptr): as in the forward (tfa_api.hip: run_varlen)
+// the host checks ONE sequence of max_seqlen_q x max_seqlen_k rows — every slice must fit one descriptor, there is no windowed varlen form — sizes the grids
+// from it and never reads cu_seqlens: each work item reads its sequence's bounds itself.
+int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, void* stream, bool dry) {
+  if (!p) return TFA_ERR_NULL;
+  tfa_bwd_params v;                                  // the fixed-length view: (head, row) strides as (batch, head, row) triples, batch stride 0
+  memset(&v, 0, sizeof(v));
+  v.q = p->q; v.k = p->k; v.v = p->v; v.out = p->out; v.dout = p->dout; v.lse = p->lse; v.dq = p->dq; v.dk = p->dk; v.dv = p->dv; v.delta = p->delta;
+  v.B = p->B; v.H = p->H; v.Hk = p->Hk; v.Nq = p->max_seqlen_q; v.Nk = p->max_seqlen_k; v.D = p->D;
+  const int64_t* src[8] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->do_stride, p->dq_stride, p->dk_stride, p->dv_stride};
+  int64_t* dst[8] = {v.q_stride, v.k_stride, v.v_stride, v.o_stride, v.do_stride, v.dq_stride, v.dk_stride, v.dv_stride};
+  for (int i = 0; i < 8; ++i) { dst[i][0] = 0; dst[i][1] = src[i][0]; dst[i][2] = src[i][1]; }
+  v.softmax_scale = p->softmax_scale; v.dtype = p->dtype; v.grad_dtype = p->grad_dtype;
+  int win[2] = {-1, -1}, form = p->is_causal ? tfa::WIN_CAUSAL : tfa::WIN_FULL, window_st = TFA_OK;
+  if (w) {
+    win[0] = w[0];
+    win[1] = w[1];
+    form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
+    window_st = form < 0 ? form : (form == tfa::WIN_LOCAL && (int64_t)p->max_seqlen_q + p->max_seqlen_k >= (1 << 28)) ? TFA_ERR_SHAPE : TFA_OK;
+  }
+  v.is_causal = form == tfa::WIN_CAUSAL;
+  const bool shape = p->total_q > 0 && p->total_k > 0 && p->flags == 0 && p->reserved_ == 0;
+  int st = check_bwd(v, p->cu_seqlens_q && p->cu_seqlens_k, shape, 128, window_st, 4, (int64_t)p->H * p->total_q);
+  if (st) return st;
+  tfa::BArgs a;
+  st = fill_args(v, nullptr, &a);
+  if (st) return st;
+  a.fuse_delta = 1;                                  // (the dQ launch forms delta; no separate delta launch in varlen form)
+  a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;
+  a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
+  if (form == tfa::WIN_LOCAL) tfa::set_window(&a, win[0], win[1], v.Nq, v.Nk);
+  return launch_form_pair(a, v, true, form == tfa::WIN_LOCAL, stream, dry);
 }
 
 }  // namespace
@@ -420,16 +343,22 @@ extern "C" {
 
 int tfa_bwd(const tfa_bwd_params* p, void* stream) { return run_bwd(p, stream, false); }
 int tfa_bwd_plan(const tfa_bwd_params* p) { return run_bwd(p, nullptr, true); }
-int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, stream, false); }
-int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, void* stream) { return run_bwd_local(p, window_left, window_right, stream, false); }
-int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right) { return run_bwd_local(p, window_left, window_right, nullptr, true); }
+int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, nullptr, stream, false); }
+int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  return run_bwd_local(p, w, stream, false);
+}
+int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  return run_bwd_local(p, w, nullptr, true);
+}
 int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_varlen(p, stream, false, w);
+  return run_bwd_varlen(p, w, stream, false);
 }
 int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_varlen(p, nullptr, true, w);
+  return run_bwd_varlen(p, w, nullptr, true);
 }
 int tfa_debug_bwd_split(int on) { g_bwd_split = on & 15; return TFA_OK; }
 long long tfa_bwd_workspace_bytes(const tfa_bwd_params* p) {

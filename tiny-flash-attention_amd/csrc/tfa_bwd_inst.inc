@@ -12,24 +12,14 @@ static hipError_t launch_bwd_one(const BArgs& a, int grid, hipStream_t stream, b
   constexpr bool CAN_BIG = WIDE256 ? DVB == D / 32 : MODE == BWD_DQ;   // (256 wide: all three modes, in the unit of the full column count)
   if (a.big && !CAN_BIG) return hipErrorInvalidValue;       // (the host never asks: tfa_bwd_api.hip)
   auto kern = bwd_kernel<T, D, MODE, CAUSAL, F32OUT, WIDE256, NW, false, DVB>;
-  if (dry) return hipSuccess;
   if constexpr (CAN_BIG) {                                   // (only the forms that can be asked for are instantiated)
     if (a.big) {
-      auto kern_big = bwd_kernel<T, D, MODE, CAUSAL, F32OUT, WIDE256, NW, true>;
       static std::atomic<unsigned long long> attr_mask_big{0};
-      hipError_t eb = set_dyn_lds_once(attr_mask_big, reinterpret_cast<const void*>(kern_big), lds);
-      if (eb != hipSuccess) return eb;
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(kern_big, dim3(grid), dim3(NW * 64), lds, stream, a);
-      return hipGetLastError();
+      return launch_bwd_kernel(bwd_kernel<T, D, MODE, CAUSAL, F32OUT, WIDE256, NW, true>, attr_mask_big, grid, NW * 64, lds, a, stream, dry);
     }
   }
   static std::atomic<unsigned long long> attr_mask{0};   // one per instantiation, one bit per device (tfa_launch.h)
-  hipError_t e = set_dyn_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, a);
-  return hipGetLastError();
+  return launch_bwd_kernel(kern, attr_mask, grid, NW * 64, lds, a, stream, dry);
 }
 
 template <typename T, int D, int MODE, int DVB = D / 32>
@@ -85,34 +75,19 @@ static hipError_t launch_bwd_kv_one(const BArgs& a, int grid, hipStream_t stream
   constexpr int lds = bwd_kv_lds_bytes<D, KG>();   // three stages of (Q, dO) tiles + the P exchange buffers + the stages' row statistics: tfa_bwd_launch.h
   if constexpr (!WS) {
     if (!a.big && a.dv <= D - 32) {                  // the last 32-column block is empty: the instantiation that skips it
-      if (dry) return hipSuccess;
-      auto kern_n = bwd_kv_kernel<T, D, CAUSAL, F32OUT, false, KG, false, D / 32 - 1>;
       static std::atomic<unsigned long long> attr_mask_n{0};
-      hipError_t en = set_dyn_lds_once(attr_mask_n, reinterpret_cast<const void*>(kern_n), lds);
-      if (en != hipSuccess) return en;
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(kern_n, dim3(grid), dim3(KG * 128), lds, stream, a);
-      return hipGetLastError();
+      return launch_bwd_kernel(bwd_kv_kernel<T, D, CAUSAL, F32OUT, false, KG, false, D / 32 - 1>, attr_mask_n, grid, KG * 128, lds, a, stream, dry);
     }
   }
   auto kern = bwd_kv_kernel<T, D, CAUSAL, F32OUT, WS, KG>;
   auto kern_big = bwd_kv_kernel<T, D, CAUSAL, F32OUT, false, TFA_BWD_KV_KG_OF(false), true>;
   if (a.big && WS) return hipErrorInvalidValue;
-  if (dry) return hipSuccess;
   if (a.big) {
     static std::atomic<unsigned long long> attr_mask_big{0};
-    hipError_t eb = set_dyn_lds_once(attr_mask_big, reinterpret_cast<const void*>(kern_big), lds);
-    if (eb != hipSuccess) return eb;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern_big, dim3(grid), dim3(KG * 128), lds, stream, a);
-    return hipGetLastError();
+    return launch_bwd_kernel(kern_big, attr_mask_big, grid, KG * 128, lds, a, stream, dry);
   }
   static std::atomic<unsigned long long> attr_mask{0};
-  hipError_t e = set_dyn_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(KG * 128), lds, stream, a);
-  return hipGetLastError();
+  return launch_bwd_kernel(kern, attr_mask, grid, KG * 128, lds, a, stream, dry);
 }
 
 template <>
@@ -128,14 +103,8 @@ hipError_t launch_bwd_kv<TFA_T, TFA_D>(const BArgs& a, int grid, bool causal, bo
 template <typename T, int D, bool CAUSAL, bool F32OUT>
 static hipError_t launch_bwd_dq_ws_one(const BArgs& a, int grid, hipStream_t stream, bool dry) {
   constexpr int lds = 3 * (64 * 256 * 2 + 64 * D * 2);               // three stages of (dS^T tile, K tile)
-  auto kern = bwd_dq_ws_kernel<T, D, CAUSAL, F32OUT>;
-  if (dry) return hipSuccess;
   static std::atomic<unsigned long long> attr_mask{0};
-  hipError_t e = set_dyn_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
-  if (e != hipSuccess) return e;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a);
-  return hipGetLastError();
+  return launch_bwd_kernel(bwd_dq_ws_kernel<T, D, CAUSAL, F32OUT>, attr_mask, grid, 512, lds, a, stream, dry);
 }
 
 template <>

@@ -2,4 +2,5 @@
 #define TFA_T _Float16
 #define TFA_D 64
 #define TFA_VARLEN false
-#include "tfa_bwd_local_inst.inc"
+#define TFA_LOCAL true
+#include "tfa_bwd_form_inst.inc"

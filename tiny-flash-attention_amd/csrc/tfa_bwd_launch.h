@@ -17,8 +17,8 @@
 #define TFA_BWD_KV_KG_OF(WS) ((WS) ? 4 : TFA_BWD_KV_KG)
 
 namespace tfa {
-// dynamic LDS of the backward kernels — ONE formula per kernel for every launcher (fixed-length: tfa_bwd_inst.inc, packed variable-length:
-// tfa_bwd_varlen_inst.inc).  bwd_kernel: two stages of NIMG tile images, plus the stages' row statistics in the key-resident (dK / dV) modes.
+// dynamic LDS of the backward kernels — ONE formula per kernel for every launcher (fixed-length: tfa_bwd_inst.inc, the varlen and local forms:
+// tfa_bwd_form_inst.inc).  bwd_kernel: two stages of NIMG tile images, plus the stages' row statistics in the key-resident (dK / dV) modes.
 template <int D, int MODE, bool WIDE256>
 constexpr int bwd_lds_bytes() {
   return 2 * ((WIDE256 || MODE == BWD_DV) ? 2 : 3) * 64 * D * 2 + (MODE == BWD_DQ ? 0 : 2 * 512);
@@ -28,6 +28,19 @@ template <int D, int KG>
 constexpr int bwd_kv_lds_bytes() {
   return 3 * 2 * 64 * D * 2 + (KG == 4 ? 3 : 2) * KG * (32 * 64 * 2) + 3 * 512;
 }
+// the common tail of every launcher of a BArgs kernel (the counterpart of tfa_launch.h: launch_common): nothing on a dry run; else opt in to the dynamic
+// LDS size on this device, launch, and return THIS launch's status (a sticky error left behind by unrelated earlier HIP calls is cleared first)
+template <typename Kern>
+static inline hipError_t launch_bwd_kernel(Kern kern, std::atomic<unsigned long long>& mask, int grid, int block, int lds, const BArgs& a, hipStream_t stream,
+                                           bool dry) {
+  if (dry) return hipSuccess;
+  hipError_t e = set_dyn_lds_once(mask, reinterpret_cast<const void*>(kern), lds);
+  if (e != hipSuccess) return e;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a);
+  return hipGetLastError();
+}
+
 template <typename T, int D>
 hipError_t launch_bwd(const BArgs& a, int mode, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
 // the 256-wide single-gradient kernels by the number of 32-column blocks that can hold valid head-dim columns (5..8)
@@ -39,13 +52,12 @@ hipError_t launch_bwd_kv(const BArgs& a, int grid, bool causal, bool f32out, hip
 // dQ = scale * dS . K from the workspace (tfa_bwd_dq_kernel.h): grid = B * H * ceil(Nq / 256)
 template <typename T, int D>
 hipError_t launch_bwd_dq_ws(const BArgs& a, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
-// packed variable-length batches (tfa_bwd_varlen): keys = false the dQ launch (grid = B * H * ceil(max_seqlen_q / 256)), keys = true the fused dK/dV
-// launch (grid = B * Hk * ceil(max_seqlen_k / 128)); tfa_bwd_inst_varlen_<dtype>_<D>.hip
-template <typename T, int D>
-hipError_t launch_bwd_varlen(const BArgs& a, bool keys, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
-// local (sliding-window) attention (tfa_bwd_local / tfa_bwd_varlen_local): keys as above, the LOCAL instantiations; tfa_bwd_inst_local_<dtype>_<D>_<fx|vl>.hip
-template <typename T, int D, bool VARLEN>
-hipError_t launch_bwd_local(const BArgs& a, bool keys, int grid, bool f32out, hipStream_t stream, bool dry);
+// the packed variable-length (VARLEN: tfa_bwd_varlen) and local (LOCAL: tfa_bwd_local, tfa_bwd_varlen_local) forms: keys = false the dQ launch
+// (grid = B * H * ceil(Nq / 256)), keys = true the fused dK/dV launch (grid = B * Hk * ceil(Nk / 128)) — Nq / Nk = max_seqlen_q / _k for varlen.  The local
+// kernels are the causal template only (`causal` is ignored).  One unit per (dtype, width, form): tfa_bwd_inst_varlen_<dtype>_<D>.hip (VARLEN) and
+// tfa_bwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN)
+template <typename T, int D, bool VARLEN, bool LOCAL>
+hipError_t launch_bwd_form(const BArgs& a, bool keys, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
 template <typename T, int D>
 hipError_t launch_delta(const void* o, const void* dout, float* delta, const long long* os, const long long* ds, int H, int Nq, long long rows,
                         int dv, hipStream_t stream, bool dry);

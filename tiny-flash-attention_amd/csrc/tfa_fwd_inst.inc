@@ -26,15 +26,6 @@ static hipError_t launch_dma(const KArgs& a, bool causal, bool f32out, hipStream
   TFA_CF_DISPATCH(launch_one_dma, T, D, NW, VF)
 }
 
-template <typename T, int D, int NW, int VF, bool CAUSAL, bool F32OUT, int DVB = D / 32, int AB = 0>
-static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* geom, bool dry) {
-  // (+ 16 bytes + one float per query row: the max-free instantiations' "redo this pass" word and the seeds of a redone pass behind everything else,
-  //  tfa_fwd_kernel_il.h: REDO_OFF, SEED_OFF)
-  constexpr int lds = il_lds_bytes<D, NW, VF>();
-  auto kern = fwd_kernel_il<T, D, NW, CAUSAL, F32OUT, VF, AB, DVB>;
-  static std::atomic<unsigned long long> attr_mask{0};
-  return launch_common(kern, attr_mask, a.nbh * a.nwork, NW * 64, lds, a, stream, geom, dry);
-}
 template <typename T, int D, int NW, int VF>
 static hipError_t launch_il(const KArgs& a, bool causal, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
   TFA_CF_DISPATCH(launch_one_il, T, D, NW, VF)

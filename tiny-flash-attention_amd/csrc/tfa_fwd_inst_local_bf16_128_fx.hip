@@ -2,4 +2,6 @@
 #define TFA_T __bf16
 #define TFA_D 128
 #define TFA_VARLEN false
-#include "tfa_fwd_local_inst.inc"
+#define TFA_LOCAL true
+#define TFA_CAUSAL true
+#include "tfa_fwd_form_inst.inc"

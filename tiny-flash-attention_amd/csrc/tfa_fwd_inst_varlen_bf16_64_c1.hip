@@ -2,4 +2,6 @@
 #define TFA_T __bf16
 #define TFA_D 64
 #define TFA_CAUSAL true
-#include "tfa_fwd_varlen_inst.inc"
+#define TFA_VARLEN true
+#define TFA_LOCAL false
+#include "tfa_fwd_form_inst.inc"

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 
+#include "tfa.h"
+
 namespace tfa {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE: one bit per device ordinal in the launcher's mask, so a
@@ -32,6 +34,41 @@ static inline int num_cus_current_device() {
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
   if (cacheable) cache[dev].store(n, std::memory_order_relaxed);
   return n;
+}
+
+// The kernel shape a launch instantiates: element type T, compiled head-dim width W.
+template <typename T_, int W_>
+struct Shape {
+  using T = T_;
+  static constexpr int W = W_;
+};
+// The one dtype x width switch of the API units: calls f(Shape<T, W>{}) with T = __bf16 for TFA_BF16 and _Float16 otherwise, and W the narrowest
+// of the caller's widths (ascending) that holds D — the last one when none does.  Every call site shares f's return type.
+template <int W, int... Ws, typename F>
+static inline auto by_dtype_width(int dtype, int D, F&& f) {
+  if constexpr (sizeof...(Ws) > 0)
+    if (D > W) return by_dtype_width<Ws...>(dtype, D, f);
+  return dtype == TFA_BF16 ? f(Shape<__bf16, W>{}) : f(Shape<_Float16, W>{});
+}
+
+// Local (sliding-window) attention, FlashAttention-2's window: key j is visible to row i iff i + shift - left <= j <= i + shift + right, -1 = unbounded on
+// that side, causal forces right = 0.  A side that reaches past every key of every row is unbounded: left >= nk - 1, right >= nq - 1 (max_seqlen for
+// varlen).  What is left is FULL (-1, -1), CAUSAL (-1, 0) — the fixed-length and varlen kernels, same bits — or a true window, the LOCAL instantiations.
+// Returns the form, or TFA_ERR_SHAPE for a side below -1.
+enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
+static inline int window_form(int* left, int* right, bool causal, int nq, int nk) {
+  if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
+  if (causal) *right = 0;
+  if (*left >= nk - 1) *left = -1;
+  if (*left < 0 && *right == 0) return WIN_CAUSAL;
+  if (*right >= nq - 1) *right = -1;
+  return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
+}
+// the window as the kernels read it (KArgs / BArgs::win_left, win_right): both sides >= 0, an unbounded one as nq + nk
+template <typename Args>
+static inline void set_window(Args* a, int left, int right, int nq, int nk) {
+  a->win_left = left < 0 ? nq + nk : left;
+  a->win_right = right < 0 ? nq + nk : right;
 }
 
 }  // namespace tfa

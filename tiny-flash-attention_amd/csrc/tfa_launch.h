@@ -111,7 +111,7 @@ struct LaunchGeom {
 
 // dynamic LDS of an il kernel (fwd_kernel_il, tfa_fwd_kernel_il.h): the K / V tile buffers (KSPLIT: one ring per wave group), the separate epilogue region
 // (EPI without EPI_INPLACE), then the max-free instantiations' "redo this pass" word and one seed float per query row (REDO_OFF, SEED_OFF).  ONE formula
-// for every launcher of the kernel — fixed-length (tfa_fwd_inst.inc) and packed variable-length (tfa_fwd_varlen_inst.inc)
+// for every launcher of the kernel: launch_one_il below
 template <int D, int NW, int VF>
 constexpr int il_lds_bytes() {
   return ((VF & VF_IL_KSPLIT) ? 8 : 4) * 64 * D * 2 + (((VF & VF_IL_EPI) && !(VF & VF_IL_EPI_INPLACE)) ? NW * 32 * D * 2 : 0) + 16 + NW * 32 * 4;
@@ -129,28 +129,23 @@ template <typename T, int D>
 static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
   return causal ? launch_fwd_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
-// the packed variable-length form (VF_IL_VARLEN) of variants 30 and 32: one translation unit per (dtype, width, causal), tfa_fwd_inst_varlen_*.hip
-template <typename T, int D, bool CAUSAL>
-hipError_t launch_fwd_varlen_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_FWD_VARLEN_UNITS(T, D)                                                                             \
-  template <> hipError_t launch_fwd_varlen_c<T, D, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
-  template <> hipError_t launch_fwd_varlen_c<T, D, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
-TFA_FWD_VARLEN_UNITS(__bf16, 64) TFA_FWD_VARLEN_UNITS(__bf16, 128) TFA_FWD_VARLEN_UNITS(_Float16, 64) TFA_FWD_VARLEN_UNITS(_Float16, 128)
-#undef TFA_FWD_VARLEN_UNITS
-template <typename T, int D>
-static inline hipError_t launch_fwd_varlen(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
-  return causal ? launch_fwd_varlen_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_varlen_c<T, D, false>(a, f32out, variant, stream, geom, dry);
+// the packed variable-length (VF_IL_VARLEN) and local (sliding-window, VF_IL_LOCAL) forms of variants 30 and 32: one translation unit per (dtype, width, form,
+// causal) — tfa_fwd_inst_varlen_<dtype>_<D>_c<0|1>.hip (VARLEN) and tfa_fwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN: the CAUSAL template
+// only, tfa_fwd_form_inst.inc)
+template <typename T, int D, bool VARLEN, bool LOCAL, bool CAUSAL>
+hipError_t launch_fwd_form_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_FWD_FORM_UNITS(T, D)                                                                                         \
+  template <> hipError_t launch_fwd_form_c<T, D, true, false, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
+  template <> hipError_t launch_fwd_form_c<T, D, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
+  template <> hipError_t launch_fwd_form_c<T, D, false, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
+  template <> hipError_t launch_fwd_form_c<T, D, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
+TFA_FWD_FORM_UNITS(__bf16, 64) TFA_FWD_FORM_UNITS(__bf16, 128) TFA_FWD_FORM_UNITS(_Float16, 64) TFA_FWD_FORM_UNITS(_Float16, 128)
+#undef TFA_FWD_FORM_UNITS
+template <typename T, int D, bool VARLEN, bool LOCAL>
+static inline hipError_t launch_fwd_form(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
+  if constexpr (LOCAL) return launch_fwd_form_c<T, D, VARLEN, true, true>(a, f32out, variant, stream, geom, dry);   // (the window carries the right edge)
+  else return causal ? launch_fwd_form_c<T, D, VARLEN, false, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_form_c<T, D, VARLEN, false, false>(a, f32out, variant, stream, geom, dry);
 }
-
-// the local (sliding-window) form (VF_IL_LOCAL) of variants 30 and 32, fixed-length and packed variable-length: one translation unit per (dtype, width, form),
-// tfa_fwd_inst_local_*.hip
-template <typename T, int D, bool VARLEN>
-hipError_t launch_fwd_local_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_FWD_LOCAL_UNITS(T, D)                                                                             \
-  template <> hipError_t launch_fwd_local_c<T, D, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
-  template <> hipError_t launch_fwd_local_c<T, D, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
-TFA_FWD_LOCAL_UNITS(__bf16, 64) TFA_FWD_LOCAL_UNITS(__bf16, 128) TFA_FWD_LOCAL_UNITS(_Float16, 64) TFA_FWD_LOCAL_UNITS(_Float16, 128)
-#undef TFA_FWD_LOCAL_UNITS
 
 // common tail of every launcher: report the geometry, opt in to the dynamic LDS size on this device, launch, and return
 // THIS launch's status (a sticky error left behind by unrelated earlier HIP calls is cleared first).
@@ -183,6 +178,16 @@ static inline hipError_t launch_common(Kern kern, std::atomic<unsigned long long
   (void)hipGetLastError();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a);
   return hipGetLastError();
+}
+
+// one il kernel instantiation (fwd_kernel_il, tfa_fwd_kernel_il.h), launched for every (b,h) slice's work items: every launcher of the il kernels, fixed-length
+// (tfa_fwd_inst.inc) and the varlen / local forms (tfa_fwd_form_inst.inc)
+template <typename T, int D, int NW, int VF, bool CAUSAL, bool F32OUT, int DVB = D / 32, int AB = 0>
+static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* geom, bool dry) {
+  constexpr int lds = il_lds_bytes<D, NW, VF>();
+  auto kern = fwd_kernel_il<T, D, NW, CAUSAL, F32OUT, VF, AB, DVB>;
+  static std::atomic<unsigned long long> attr_mask{0};   // one per instantiation, one bit per device
+  return launch_common(kern, attr_mask, a.nbh * a.nwork, NW * 64, lds, a, stream, geom, dry);
 }
 
 // The LDS-DMA kernel 256 wide, fp32 partial output: tfa_fwd_splitkv's one-launch form for head dims above 128 (tfa_dma_inst_<dtype>_256.hip)
