@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -462,6 +462,54 @@ int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, vo
 int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right);
 int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int window_right, void* stream);
 int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right);
+
+/* ---- ALiBi (FlashAttention-2's alibi_slopes) -----------------------------------------------------------------------------------------------
+ * The same params structs as tfa_fwd / tfa_bwd / tfa_fwd_varlen / tfa_bwd_varlen plus the slopes and a window.  With shift = Nk - Nq per sequence
+ * (bottom-right aligned, as is_causal and the window):
+ *     S[i,j] = softmax_scale * q_i . k_j  -  alibi_slopes[b * slopes_batch_stride + h] * | i + shift - j |
+ * then the mask (is_causal / the window, exactly as the _local entry points read them; (-1, -1) = none), the softmax and P V.  Everything downstream is
+ * defined on these biased scores: lse is the true logsumexp_j S[i,j] INCLUDING the bias, causal or not (tfa_bwd_alibi and tfa_merge consume it); rows that
+ * see no key get out = 0 and lse = +inf; the backward recomputes P from the biased scores and returns dq, dk, dv — the slopes get no gradient.
+ * alibi_slopes: fp32 in DEVICE memory, one slope per QUERY head h (GQA: the H / Hk query heads of a K/V head have their own) of batch entry / sequence b;
+ * slopes_batch_stride = 0: one row of H slopes shared by the batch, = H: a (B, H) array.  The library never reads the array on the host — no copy, no
+ * synchronisation, a call can be captured in a graph and replayed after the values were changed in place.  Any finite value is legal (zero and negative
+ * included); non-finite slopes give unspecified results; nothing is validated on the host.  (Without slopes call the existing entry points: there is no
+ * "NULL = no bias" here.)
+ * Every call runs the ALiBi form of the LOCAL instantiations, whatever the window — full and causal attention carry unbounded sides: the il8 (variant 30)
+ * or il4 (32) forward as tfa_fwd_local chooses, one query block per work item, every tile through the compiler-scheduled bodies (the bias is added to the
+ * raw scores in front of the row maximum); rounding rule TFA_RULE_LAZY for both dtypes.  The backward runs the dQ launch (which forms delta) and the fused
+ * dK/dV launch of that form, deterministic; never the dS-workspace form (tfa_bwd_params::workspace is ignored).
+ * Refused, nothing launched: alibi_slopes NULL (TFA_ERR_NULL) or not 4-byte aligned (TFA_ERR_ALIGN), slopes_batch_stride other than 0 or H
+ * (TFA_ERR_STRIDE), and what the local form refuses, with its codes: head dims above 128 (TFA_ERR_HEAD_DIM), fp32 inputs (TFA_ERR_DTYPE), any flag —
+ * TFA_FWD_EXACT_MAX included — (TFA_ERR_SHAPE), a window side below -1 (TFA_ERR_SHAPE), kv_offset / nk_total != 0 (TFA_ERR_SHAPE), Nq + Nk >= 2^28
+ * (TFA_ERR_SHAPE), slices that need per-tile descriptors (TFA_ERR_STRIDE), a forced variant other than 30 / 32 (TFA_ERR_VARIANT).
+ * The kernels form the distance i + shift - j exactly in int32 and convert it to fp32 in front of |.|: beyond 2^24 positions (Nq + Nk < 2^28 is admitted) it
+ * carries fp32's relative rounding, the same order as the rounding of slope * |distance| itself.
+ * Tolerances: the header's "which tolerance each path guarantees", with the LSE bar relative to its size — |d| <= 1e-4 * max(1, |lse|): with Nq > Nk and no
+ * causal mask every key of the first rows is Nq - Nk positions away and the LSE itself is of the order of slope * (Nq - Nk).
+ * Measured: profiles/alibi_bench.txt (tools/bench_alibi.py), quoted in README.md. */
+int tfa_fwd_alibi(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream);
+/* Validate and report the launch geometry of tfa_fwd_alibi without launching (no GPU needed). */
+int tfa_fwd_alibi_plan(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, int* grid,
+                       int* block, int* lds_bytes);
+/* The kernel variant tfa_fwd_alibi runs for *p (30 or 32), or a negative TFA_ERR_* code. */
+int tfa_fwd_alibi_variant(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+/* The row reference P is rounded against: TFA_RULE_LAZY (bf16 and fp16), or a negative TFA_ERR_* code. */
+int tfa_fwd_alibi_rounding_rule(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+/* Packed variable-length batches: b indexes the sequence (slopes_batch_stride = H: one row of slopes per sequence), the distance is taken per sequence. */
+int tfa_fwd_varlen_alibi(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                         void* stream);
+int tfa_fwd_varlen_alibi_plan(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                              int* grid, int* block, int* lds_bytes);
+int tfa_fwd_varlen_alibi_variant(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+int tfa_fwd_varlen_alibi_rounding_rule(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                       int window_right);
+/* The backward of an ALiBi forward (same slopes, same window, same params as tfa_bwd / tfa_bwd_varlen); _plan validates without launching. */
+int tfa_bwd_alibi(const tfa_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream);
+int tfa_bwd_alibi_plan(const tfa_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+int tfa_bwd_varlen_alibi(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                         void* stream);
+int tfa_bwd_varlen_alibi_plan(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,18 @@ SYMBOLS = (
     "tfa_bwd_local_plan",
     "tfa_bwd_varlen_local",
     "tfa_bwd_varlen_local_plan",
+    "tfa_fwd_alibi",
+    "tfa_fwd_alibi_plan",
+    "tfa_fwd_alibi_variant",
+    "tfa_fwd_alibi_rounding_rule",
+    "tfa_fwd_varlen_alibi",
+    "tfa_fwd_varlen_alibi_plan",
+    "tfa_fwd_varlen_alibi_variant",
+    "tfa_fwd_varlen_alibi_rounding_rule",
+    "tfa_bwd_alibi",
+    "tfa_bwd_alibi_plan",
+    "tfa_bwd_varlen_alibi",
+    "tfa_bwd_varlen_alibi_plan",
 )
 
 
@@ -295,6 +307,16 @@ def lib():
                        ("tfa_fwd_varlen_local_variant", [PV, C.c_int, C.c_int]), ("tfa_fwd_varlen_local_rounding_rule", [PV, C.c_int, C.c_int]),
                        ("tfa_bwd_local", [PB, C.c_int, C.c_int, C.c_void_p]), ("tfa_bwd_local_plan", [PB, C.c_int, C.c_int]),
                        ("tfa_bwd_varlen_local", [PVB, C.c_int, C.c_int, C.c_void_p]), ("tfa_bwd_varlen_local_plan", [PVB, C.c_int, C.c_int])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
+    # ALiBi: the local entry points' arguments with (const float* alibi_slopes, int64_t slopes_batch_stride) in front of the window
+    AL = [C.c_void_p, C.c_int64, C.c_int, C.c_int]
+    for name, args in (("tfa_fwd_alibi", [PF] + AL + [C.c_void_p]), ("tfa_fwd_alibi_plan", [PF] + AL + [IP, IP, IP]),
+                       ("tfa_fwd_alibi_variant", [PF] + AL), ("tfa_fwd_alibi_rounding_rule", [PF] + AL),
+                       ("tfa_fwd_varlen_alibi", [PV] + AL + [C.c_void_p]), ("tfa_fwd_varlen_alibi_plan", [PV] + AL + [IP, IP, IP]),
+                       ("tfa_fwd_varlen_alibi_variant", [PV] + AL), ("tfa_fwd_varlen_alibi_rounding_rule", [PV] + AL),
+                       ("tfa_bwd_alibi", [PB] + AL + [C.c_void_p]), ("tfa_bwd_alibi_plan", [PB] + AL),
+                       ("tfa_bwd_varlen_alibi", [PVB] + AL + [C.c_void_p]), ("tfa_bwd_varlen_alibi_plan", [PVB] + AL)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     _lib = L

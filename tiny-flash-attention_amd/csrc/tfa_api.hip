@@ -172,6 +172,7 @@ int validate(const tfa_fwd_params* p, tfa::KArgs* a, int variant, int row_mod = 
   if (!slice_bytes(p->Nq, a->os_n, p->D, osz, win, &a->o_bytes, &a->big)) return TFA_ERR_STRIDE;
   if ((g_dbg_flags & 256) && win) a->big = 1;   // tests: run the windowed instantiation on a small problem
   a->scale = p->softmax_scale;
+  // (trace and grid share their bytes with the ALiBi slopes: run_form calls set_alibi AFTER validate(), and it must stay the last writer of them)
   a->trace = g_trace;
   a->grid = num_cus();
   if (g_dbg_flags & 512) a->grid = 8;            // tests: persistent kernels with 8 workgroups, so that small problems walk several work items each
@@ -338,11 +339,13 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
 //        for varlen;
 //   vl:  the varlen call, or nullptr: B sequences run as the grid's batch and each work item reads its bounds from cu_seqlens on the device
 //        (tfa_fwd_kernel.h: varlen_seq) — the host never reads them;
-//   win: the normalised {left, right} of a true window (window_form: WIN_LOCAL), or nullptr.
+//   win: the normalised {left, right} of a true window (window_form: WIN_LOCAL), or nullptr;
+//   al:  the ALiBi slopes (checked by the caller), or nullptr: with them the ALiBi form of the local kernels runs whatever the window is — win is then always given,
+//        its unbounded sides as -1 (set_window).
 // Kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else (the key-split kernels, split-KV and decode row packing have no such form); a
 // variant forced by tfa_set_variant must be one of the two.
-int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_varlen_fwd_params* vl, const int* win, void* stream, tfa::LaunchGeom* geom,
-             bool dry, int* variant_out, int* rule_out) {
+int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_varlen_fwd_params* vl, const int* win, const tfa::AlibiArg* al, void* stream,
+             tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
   tfa_fwd_params f = f_in;
   int variant;
   if (win) {
@@ -369,6 +372,7 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     a.total_q = vl->total_q; a.total_k = vl->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
   }
   if (win) tfa::set_window(&a, win[0], win[1], f.Nq, f.Nk);   // (after the last read of a.big: the window shares its bytes)
+  if (al) tfa::set_alibi(&a, *al);
   if (variant_out) *variant_out = variant;
   if (rule_out) *rule_out = rounding_rule(variant, f.dtype, f.D, !win);   // (the local form is not the main instantiation)
   const bool causal = f.is_causal != 0, f32out = f.out_dtype == TFA_F32;
@@ -377,18 +381,21 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     using T = typename decltype(k)::T;
     constexpr int W = decltype(k)::W;
     if (!win) return tfa::launch_fwd_form<T, W, true, false>(a, causal, f32out, variant, s, geom, dry);   // (no window: always varlen here)
+    if (al) return vl ? tfa::launch_fwd_form<T, W, true, true, true>(a, causal, f32out, variant, s, geom, dry)
+                      : tfa::launch_fwd_form<T, W, false, true, true>(a, causal, f32out, variant, s, geom, dry);
     return vl ? tfa::launch_fwd_form<T, W, true, true>(a, causal, f32out, variant, s, geom, dry)
               : tfa::launch_fwd_form<T, W, false, true>(a, causal, f32out, variant, s, geom, dry);
   });
 }
 
 // tfa_fwd_local: FULL and CAUSAL windows are tfa_fwd's own problems; a true window covers the whole key sequence (no partial passes)
-int run_local(const tfa_fwd_params* p, const int* w, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
+// tfa_fwd_alibi (al): every window, FULL and CAUSAL included, is the local form's problem — the ALiBi kernels are instantiations of it
+int run_local(const tfa_fwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
   if (!p) return TFA_ERR_NULL;
   int win[2] = {w[0], w[1]};
   const int form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->Nq, p->Nk);
   if (form < 0) return form;
-  if (form != tfa::WIN_LOCAL) {
+  if (form != tfa::WIN_LOCAL && !al) {
     tfa_fwd_params f = *p;
     f.is_causal = form == tfa::WIN_CAUSAL;
     return run(&f, stream, geom, dry, variant_out, rule_out);
@@ -397,12 +404,18 @@ int run_local(const tfa_fwd_params* p, const int* w, void* stream, tfa::LaunchGe
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
   if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
   if (p->flags != 0) return TFA_ERR_SHAPE;
-  return run_form(*p, *p, nullptr, win, stream, geom, dry, variant_out, rule_out);
+  if (al) {
+    if (p->H <= 0) return TFA_ERR_SHAPE;
+    const int st = tfa::check_alibi(*al, p->H);
+    if (st != TFA_OK) return st;
+  }
+  return run_form(*p, *p, nullptr, win, al, stream, geom, dry, variant_out, rule_out);
 }
 
 // Packed variable-length batches (include/tfa.h: tfa_fwd_varlen, tfa_fwd_varlen_local — w: the window, or nullptr).  The host knows the sequences' bounds only
 // as max_seqlen_q / _k; run_form runs the fixed-length problem of one sequence of that size B times.
-int run_varlen(const tfa_varlen_fwd_params* p, const int* w, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
+int run_varlen(const tfa_varlen_fwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out,
+               int* rule_out) {
   if (!p) return TFA_ERR_NULL;
   if (!p->q || !p->k || !p->v || !p->out || !p->cu_seqlens_q || !p->cu_seqlens_k) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;             // (fp32 inputs: no varlen form)
@@ -417,6 +430,10 @@ int run_varlen(const tfa_varlen_fwd_params* p, const int* w, void* stream, tfa::
     form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
     if (form < 0) return form;
   }
+  if (al) {
+    const int st = tfa::check_alibi(*al, p->H);
+    if (st != TFA_OK) return st;
+  }
   tfa_fwd_params f;
   memset(&f, 0, sizeof(f));
   f.q = p->q; f.k = p->k; f.v = p->v; f.out = p->out; f.lse = p->lse;
@@ -427,19 +444,20 @@ int run_varlen(const tfa_varlen_fwd_params* p, const int* w, void* stream, tfa::
   f.softmax_scale = p->softmax_scale; f.is_causal = form == tfa::WIN_CAUSAL; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
   tfa_fwd_params eq = f;
   eq.B = p->B;
-  return run_form(f, eq, p, form == tfa::WIN_LOCAL ? win : nullptr, stream, geom, dry, variant_out, rule_out);
+  return run_form(f, eq, p, (form == tfa::WIN_LOCAL || al) ? win : nullptr, al, stream, geom, dry, variant_out, rule_out);
 }
 
 // One forward call as an entry point names it: fixed-length (p) or packed variable-length (vp), with the {left, right} window of the _local entry points or
-// without (win == nullptr) — and the route that runs it.  The _plan, _variant and _rounding_rule entry points are dry runs of that route (no GPU needed).
+// without (win == nullptr), with the ALiBi slopes of the _alibi entry points (which always carry a window) or without — and the route that runs it.  The _plan, _variant and _rounding_rule entry points are dry runs of that route (no GPU needed).
 struct FwdCall {
   const tfa_fwd_params* p;
   const tfa_varlen_fwd_params* vp;
   const int* win;
+  const tfa::AlibiArg* alibi = nullptr;
 };
 int route(const FwdCall& c, void* stream, tfa::LaunchGeom* geom = nullptr, bool dry = false, int* variant_out = nullptr, int* rule_out = nullptr) {
-  if (c.vp) return run_varlen(c.vp, c.win, stream, geom, dry, variant_out, rule_out);
-  if (c.win) return run_local(c.p, c.win, stream, geom, dry, variant_out, rule_out);
+  if (c.vp) return run_varlen(c.vp, c.win, c.alibi, stream, geom, dry, variant_out, rule_out);
+  if (c.win) return run_local(c.p, c.win, c.alibi, stream, geom, dry, variant_out, rule_out);
   return run(c.p, stream, geom, dry, variant_out, rule_out);
 }
 int plan(const FwdCall& c, int* grid, int* block, int* lds_bytes) {
@@ -718,6 +736,55 @@ int tfa_fwd_varlen_local_rounding_rule(const tfa_varlen_fwd_params* p, int windo
   const int w[2] = {window_left, window_right};
   return variant_or_rule({nullptr, p, w}, true);
 }
+
+// ALiBi: the fixed-length (p) or varlen (vp) call with its slopes and window
+#define TFA_ALIBI_CALL(p, vp)                                   \
+  const int w[2] = {window_left, window_right};                 \
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};    \
+  const FwdCall call{p, vp, w, &al}
+int tfa_fwd_alibi(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream) {
+  TFA_ALIBI_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return route(call, stream);
+}
+int tfa_fwd_alibi_plan(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, int* grid, int* block,
+                       int* lds_bytes) {
+  TFA_ALIBI_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return plan(call, grid, block, lds_bytes);
+}
+int tfa_fwd_alibi_variant(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  TFA_ALIBI_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, false);
+}
+int tfa_fwd_alibi_rounding_rule(const tfa_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  TFA_ALIBI_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, true);
+}
+int tfa_fwd_varlen_alibi(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream) {
+  TFA_ALIBI_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return route(call, stream);
+}
+int tfa_fwd_varlen_alibi_plan(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, int* grid,
+                              int* block, int* lds_bytes) {
+  TFA_ALIBI_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return plan(call, grid, block, lds_bytes);
+}
+int tfa_fwd_varlen_alibi_variant(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  TFA_ALIBI_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, false);
+}
+int tfa_fwd_varlen_alibi_rounding_rule(const tfa_varlen_fwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  TFA_ALIBI_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, true);
+}
+#undef TFA_ALIBI_CALL
 
 int tfa_fwd_variant(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, false); }   // (run()'s final choice, after GQA packing and its fall-back)
 int tfa_fwd_rounding_rule(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, true); }

@@ -250,7 +250,8 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
 
 // The varlen and local forms: the dQ launch (which forms delta) and then the fused dK/dV launch of the form kernels (VARLEN / LOCAL instantiations:
 // tfa_bwd_form_inst.inc).  a holds everything but the gradients; v is the problem as the kernels see it (run_bwd_varlen: one sequence, batch stride 0).
-int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, void* stream, bool dry) {
+// alibi: the ALiBi form of the local kernels (a.slopes set; local is then true whatever the window)
+int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, bool alibi, void* stream, bool dry) {
   const int gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
   const bool causal = v.is_causal != 0, f32 = v.grad_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -260,6 +261,8 @@ int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, 
       using T = typename decltype(k)::T;
       constexpr int W = decltype(k)::W;
       if (!local) return tfa::launch_bwd_form<T, W, true, false>(m, keys, (int)grid, causal, f32, s, dry);   // (no window: always varlen here)
+      if (alibi) return varlen ? tfa::launch_bwd_form<T, W, true, true, true>(m, keys, (int)grid, causal, f32, s, dry)
+                               : tfa::launch_bwd_form<T, W, false, true, true>(m, keys, (int)grid, causal, f32, s, dry);
       return varlen ? tfa::launch_bwd_form<T, W, true, true>(m, keys, (int)grid, causal, f32, s, dry)
                     : tfa::launch_bwd_form<T, W, false, true>(m, keys, (int)grid, causal, f32, s, dry);
     });
@@ -283,30 +286,33 @@ int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, 
 
 // Local (sliding-window) attention, tfa_bwd_local: the window's form as the forward sees it (tfa_host_util.h: window_form) — FULL / CAUSAL run tfa_bwd's own
 // launches, a true window the LOCAL instantiations (every slice within one descriptor: no windowed local form)
-int run_bwd_local(const tfa_bwd_params* p, const int* w, void* stream, bool dry) {
+// tfa_bwd_alibi (al): every window, FULL and CAUSAL included, runs the ALiBi form of the local kernels
+int run_bwd_local(const tfa_bwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, bool dry) {
   if (!p) return TFA_ERR_NULL;
   int win[2] = {w[0], w[1]};
   const int form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->Nq, p->Nk);
   if (form < 0) return form;
-  if (form != tfa::WIN_LOCAL) {
+  if (form != tfa::WIN_LOCAL && !al) {
     tfa_bwd_params f = *p;
     f.is_causal = form == tfa::WIN_CAUSAL;
     return run_bwd(&f, stream, dry);
   }
   int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
   if (st) return st;
+  if (al && (st = tfa::check_alibi(*al, p->H)) != TFA_OK) return st;
   tfa::BArgs a;
   st = fill_args(*p, nullptr, &a);
   if (st) return st;
   a.fuse_delta = 1;                                  // (the dQ launch forms delta)
   tfa::set_window(&a, win[0], win[1], p->Nq, p->Nk);
-  return launch_form_pair(a, *p, false, true, stream, dry);
+  if (al) tfa::set_alibi(&a, *al);
+  return launch_form_pair(a, *p, false, true, al != nullptr, stream, dry);
 }
 
 // Packed variable-length batches (include/tfa.h: tfa_bwd_varlen, tfa_bwd_varlen_local — w: the window, or nullptr): as in the forward (tfa_api.hip: run_varlen)
 // the host checks ONE sequence of max_seqlen_q x max_seqlen_k rows — every slice must fit one descriptor, there is no windowed varlen form — sizes the grids
 // from it and never reads cu_seqlens: each work item reads its sequence's bounds itself.
-int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, void* stream, bool dry) {
+int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, bool dry) {
   if (!p) return TFA_ERR_NULL;
   tfa_bwd_params v;                                  // the fixed-length view: (head, row) strides as (batch, head, row) triples, batch stride 0
   memset(&v, 0, sizeof(v));
@@ -321,20 +327,23 @@ int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, void* stream, b
     win[0] = w[0];
     win[1] = w[1];
     form = tfa::window_form(&win[0], &win[1], p->is_causal != 0, p->max_seqlen_q, p->max_seqlen_k);
-    window_st = form < 0 ? form : (form == tfa::WIN_LOCAL && (int64_t)p->max_seqlen_q + p->max_seqlen_k >= (1 << 28)) ? TFA_ERR_SHAPE : TFA_OK;
+    window_st = form < 0 ? form : ((form == tfa::WIN_LOCAL || al) && (int64_t)p->max_seqlen_q + p->max_seqlen_k >= (1 << 28)) ? TFA_ERR_SHAPE : TFA_OK;
   }
+  const bool local = form == tfa::WIN_LOCAL || al;   // (the ALiBi kernels are a form of the local ones, whatever the window)
   v.is_causal = form == tfa::WIN_CAUSAL;
   const bool shape = p->total_q > 0 && p->total_k > 0 && p->flags == 0 && p->reserved_ == 0;
   int st = check_bwd(v, p->cu_seqlens_q && p->cu_seqlens_k, shape, 128, window_st, 4, (int64_t)p->H * p->total_q);
   if (st) return st;
+  if (al && (st = tfa::check_alibi(*al, p->H)) != TFA_OK) return st;
   tfa::BArgs a;
   st = fill_args(v, nullptr, &a);
   if (st) return st;
   a.fuse_delta = 1;                                  // (the dQ launch forms delta; no separate delta launch in varlen form)
   a.cu_q = p->cu_seqlens_q; a.cu_k = p->cu_seqlens_k;
   a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
-  if (form == tfa::WIN_LOCAL) tfa::set_window(&a, win[0], win[1], v.Nq, v.Nk);
-  return launch_form_pair(a, v, true, form == tfa::WIN_LOCAL, stream, dry);
+  if (local) tfa::set_window(&a, win[0], win[1], v.Nq, v.Nk);
+  if (al) tfa::set_alibi(&a, *al);
+  return launch_form_pair(a, v, true, local, al != nullptr, stream, dry);
 }
 
 }  // namespace
@@ -343,22 +352,42 @@ extern "C" {
 
 int tfa_bwd(const tfa_bwd_params* p, void* stream) { return run_bwd(p, stream, false); }
 int tfa_bwd_plan(const tfa_bwd_params* p) { return run_bwd(p, nullptr, true); }
-int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, nullptr, stream, false); }
+int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream) { return run_bwd_varlen(p, nullptr, nullptr, stream, false); }
 int tfa_bwd_local(const tfa_bwd_params* p, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_local(p, w, stream, false);
+  return run_bwd_local(p, w, nullptr, stream, false);
 }
 int tfa_bwd_local_plan(const tfa_bwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_local(p, w, nullptr, true);
+  return run_bwd_local(p, w, nullptr, nullptr, true);
 }
 int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_varlen(p, w, stream, false);
+  return run_bwd_varlen(p, w, nullptr, stream, false);
 }
 int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
-  return run_bwd_varlen(p, w, nullptr, true);
+  return run_bwd_varlen(p, w, nullptr, nullptr, true);
+}
+int tfa_bwd_alibi(const tfa_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};
+  return run_bwd_local(p, w, &al, stream, false);
+}
+int tfa_bwd_alibi_plan(const tfa_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};
+  return run_bwd_local(p, w, &al, nullptr, true);
+}
+int tfa_bwd_varlen_alibi(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};
+  return run_bwd_varlen(p, w, &al, stream, false);
+}
+int tfa_bwd_varlen_alibi_plan(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};
+  return run_bwd_varlen(p, w, &al, nullptr, true);
 }
 int tfa_debug_bwd_split(int on) { g_bwd_split = on & 15; return TFA_OK; }
 long long tfa_bwd_workspace_bytes(const tfa_bwd_params* p) {

@@ -1,0 +1,7 @@
+// one ALiBi (alibi_slopes) backward instantiation unit: dtype=f16 head_dim=64 fixed-length
+#define TFA_T _Float16
+#define TFA_D 64
+#define TFA_VARLEN false
+#define TFA_LOCAL true
+#define TFA_ALIBI true
+#include "tfa_bwd_form_inst.inc"

@@ -4,14 +4,20 @@
 // forms (the one with the hand-scheduled statement; varlen, for bf16, with the max-free row reference): no windowed, idle-wave or narrow twin — head dims below
 // the kernel's width run it with the missing columns read as zeros (KArgs::dv).  The local form drops the causal pairing (and with it PREF2) and is always the
 // CAUSAL template: the right edge is the causal limit moved by win_right (a window without a right edge carries win_right >= Nq - 1).
+// TFA_ALIBI (tfa_fwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip): the ALiBi form of the local instantiations (VF_IL_ALIBI) — full, causal and windowed attention with
+// slopes are this one kernel per (dtype, width, fixed / varlen), the window's missing sides carried as unbounded.
 #include "tfa_launch.h"
+#if !defined(TFA_ALIBI)
+#define TFA_ALIBI false
+#endif
 
 namespace tfa {
 
 template <>
-hipError_t launch_fwd_form_c<TFA_T, TFA_D, TFA_VARLEN, TFA_LOCAL, TFA_CAUSAL>(const KArgs& a, bool f32out, int variant, hipStream_t s, LaunchGeom* g, bool dry) {
+hipError_t launch_fwd_form_c<TFA_T, TFA_D, TFA_VARLEN, TFA_LOCAL, TFA_CAUSAL, TFA_ALIBI>(const KArgs& a, bool f32out, int variant, hipStream_t s, LaunchGeom* g, bool dry) {
   static_assert(TFA_CAUSAL || !TFA_LOCAL, "the local kernels are the causal template");
-  constexpr int FORM = (TFA_VARLEN ? VF_IL_VARLEN : 0) | (TFA_LOCAL ? VF_IL_LOCAL : 0);
+  static_assert(TFA_LOCAL || !TFA_ALIBI, "the ALiBi kernels are a form of the local ones");
+  constexpr int FORM = (TFA_VARLEN ? VF_IL_VARLEN : 0) | (TFA_LOCAL ? VF_IL_LOCAL : 0) | (TFA_ALIBI ? VF_IL_ALIBI : 0);
   constexpr int PAIR = TFA_LOCAL ? 0 : VF_PAIR;   // (the local form: one query block per work item, no causal pairs — and so no PREF2)
   constexpr int VF30 = PAIR | (TFA_LOCAL ? 0 : VF_IL_PREF2) | VF_IL_DMASPREAD | VF_IL_EPI | VF_IL_QLDS | FORM;   // variant 30's main instantiation (tfa_fwd_inst.inc)
   constexpr int VF32 = PAIR | VF_IL_EPI | VF_IL_EPI_INPLACE | FORM;                                              // variant 32's

@@ -106,8 +106,17 @@ struct KArgs {
   };
   float scale;      // softmax_scale
   float scale_log2; // softmax_scale * log2(e)
-  int grid;         // workgroups launched (persistent kernels walk work items with this stride)
-  unsigned long long* trace;  // debug: 8 x u64 per workgroup (cycle stamps), or nullptr
+  // (the ALiBi slopes share their bytes with `grid` and `trace` — only the persistent LDS-DMA launchers read `grid`, only the traced twins of the main kernels read
+  //  `trace`, and neither has an ALiBi form — so that every existing kernel keeps its argument layout and size: tfa_fwd_alibi, VF_IL_ALIBI; set_alibi fills
+  //  them after validate())
+  union {
+    int grid;       // workgroups launched (persistent kernels walk work items with this stride)
+    int slopes_bs;  // ALiBi: slopes[b * slopes_bs + h] — 0: one row of H slopes shared by the batch, else H
+  };
+  union {
+    unsigned long long* trace;  // debug: 8 x u64 per workgroup (cycle stamps), or nullptr
+    const float* slopes;        // ALiBi: one fp32 slope per (batch entry / sequence, query head) in device memory, read by the work item; never by the host
+  };
   int dv;           // valid head dim (<= the kernel's compile-time D, a multiple of 8): the 16-byte chunks of a row beyond dv are
                     // read as zeros (their LDS-DMA lanes / Q loads are pointed outside the buffer) and never stored
   int dbg;          // bring-up flags (tfa_debug_set_flags; 0 in normal use).  128: the trace stamps describe the workgroup's

@@ -75,6 +75,11 @@ constexpr int VF_IL_LOCAL = 1 << 22;     // local (sliding-window) attention (tf
                                          // intersect the block's windows, the right edge is the causal limit moved by `right`, and the tiles on the left edge run the
                                          // compiler-scheduled masked body.  Lazy row reference (TFA_RULE_LAZY): a row whose first visited tile is all masked re-bases
                                          // from -1e30.  (The bit is VF_X4 of the x4 kernel: each kernel reads only its own flags)
+constexpr int VF_IL_ALIBI = 256;         // ALiBi (tfa_fwd_alibi): S[i,j] = scale * q_i . k_j - slope[b,h] * |i + shift - j|, a form of the LOCAL instantiations (full and causal
+                                         // attention run it with the window's sides unbounded).  The work item reads its slope once (a scalar load) and folds the softmax
+                                         // scale in: the bias a * |c - ko|, a = -slope / scale, goes onto the RAW scores of every tile where apply_mask runs — in front of the
+                                         // row maximum, so the lazy reference, its trigger and the LSE work on biased scores unchanged.  The hand-scheduled statement carries no
+                                         // bias: every tile runs the compiler-scheduled bodies.  (The bit lies in the ping-pong kernel's VF_VPRE field: each kernel reads only its own flags)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -288,6 +293,9 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   constexpr bool LOCAL = (VF & VF_IL_LOCAL) != 0;
   static_assert(!LOCAL || (CAUSAL && !PAIR && !(VF & (VF_IL_KSPLIT | VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_EXACT | VF_IL_SEAM | VF_IL_PREF | VF_IL_PREF2)) &&
                            !TFA_IL_USE_EARLY), "local: the non-paired causal form of the il8 / il4 main instantiations");
+  constexpr bool ALIBI = (VF & VF_IL_ALIBI) != 0;
+  static_assert(!ALIBI || LOCAL, "alibi: a form of the local instantiations");
+  static_assert(!ALIBI || !(AB & ILAB_TRACE), "alibi: KArgs::slopes / slopes_bs share the bytes of trace / grid — no traced twin");
   int kofs = 0, wlen = 0;
   if constexpr (LOCAL) {
     const int nk_s = VARLEN ? vsq.nk : p.Nk;
@@ -299,6 +307,13 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   }
   const int shift = (VARLEN ? vsq.nk - vsq.nq : p.shift) + (LOCAL ? p.win_right - kofs : 0);
 #define IL_NK ((VARLEN ? vsq.nk : p.Nk) - (LOCAL ? kofs : 0))
+  // ALIBI: a = -slope / softmax_scale (the raw-score domain).  `shift` above is moved by win_right and by the block's key offset and key0_of() counts from kofs:
+  // the two kofs cancel, so the distance of key offset ko of tile t to the lane's row is (my_pos + shift - win_right - key0_of(t)) - ko
+  float alibi_a = 0.f;
+  if constexpr (ALIBI) {
+    typedef __attribute__((address_space(4))) const float cfloat4;
+    alibi_a = -((const cfloat4*)(uintptr_t)p.slopes)[(long long)b * p.slopes_bs + h] / p.scale;
+  }
 
   const T* qbase = reinterpret_cast<const T*>(p.q) + (VARLEN ? (long long)vsq.q0 * p.qs_n : b * p.qs_b) + h * p.qs_h;
   const T* kbase = reinterpret_cast<const T*>(p.k) + (VARLEN ? (long long)vsq.k0 * p.ks_n : b * p.ks_b) + hk * p.ks_h;
@@ -625,6 +640,14 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
           const int ko = 32 * tt + (r & 3) + 8 * (r >> 2);
           if (ko > lim || (LOCAL && ko < llo)) s[tt][r] = -INFINITY;
         }
+    };
+    // ALIBI: the bias of tile t onto its raw scores (a sub and an fma with |.| per score); masked scores stay -inf
+    auto apply_bias = [&](int t, f32x16 (&s)[2]) {
+      const float cf = (float)(my_pos + shift - p.win_right - key0_of(t) - 4 * hi);
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[tt][r] = fmaf(alibi_a, fabsf(cf - (float)(32 * tt + (r & 3) + 8 * (r >> 2))), s[tt][r]);
     };
     // Reference exponent of the row ("mref", log2 domain) instead of the exact running max: P = exp2(s*sc - mref)
     // where mref is the row's scaled running max as of the last re-base.  A wave re-bases (every row takes its current

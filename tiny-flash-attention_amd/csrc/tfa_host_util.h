@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <stdint.h>
 
 #include "tfa.h"
 
@@ -69,6 +70,25 @@ template <typename Args>
 static inline void set_window(Args* a, int left, int right, int nq, int nk) {
   a->win_left = left < 0 ? nq + nk : left;
   a->win_right = right < 0 ? nq + nk : right;
+}
+
+
+// ALiBi (tfa_fwd_alibi / tfa_bwd_alibi and their varlen forms): one fp32 slope per (batch / sequence, query head) in DEVICE memory, row stride 0 (one row shared
+// by the batch) or H.  Checked without reading it: the kernels' work items load their slope themselves (no copy, no synchronisation, graph-capturable).
+struct AlibiArg {
+  const float* slopes;
+  int64_t batch_stride;
+};
+static inline int check_alibi(const AlibiArg& al, int H) {
+  if (!al.slopes) return TFA_ERR_NULL;
+  if ((uintptr_t)al.slopes & 3) return TFA_ERR_ALIGN;
+  if (al.batch_stride != 0 && al.batch_stride != H) return TFA_ERR_STRIDE;
+  return TFA_OK;
+}
+template <typename Args>
+static inline void set_alibi(Args* a, const AlibiArg& al) {
+  a->slopes = al.slopes;
+  a->slopes_bs = (int)al.batch_stride;
 }
 
 }  // namespace tfa

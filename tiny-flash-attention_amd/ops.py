@@ -72,8 +72,41 @@ def _window(window_size, causal, nq, nk, dtype, D, extra=()):
     return (left, right)
 
 
+def _alibi(alibi_slopes, B, H, device, dtype, D, extra=()):
+    """FlashAttention-2's ``alibi_slopes`` checked as the C ABI needs them (include/tfa.h, ALiBi) without touching a device: float32, shape ``(H,)`` or
+    ``(B, H)`` (B: the batch, or the number of sequences of a packed call), contiguous, on ``device``.  Returns ``None`` for ``None``, else
+    ``(slopes, batch_stride)`` with batch_stride 0 for ``(H,)`` and H for ``(B, H)``.  The values are never read here: the kernels load them.
+    Unsupported combinations raise ValueError naming the limit; ``extra``: (condition, message) pairs that rule slopes out."""
+    if alibi_slopes is None:
+        return None
+    if not isinstance(alibi_slopes, torch.Tensor):
+        raise TypeError(f"alibi_slopes must be a float32 tensor (got {type(alibi_slopes).__name__})")
+    if alibi_slopes.dtype != torch.float32:
+        raise TypeError(f"alibi_slopes must be float32 (got {alibi_slopes.dtype})")
+    if tuple(alibi_slopes.shape) not in ((H,), (B, H)):
+        raise ValueError(f"alibi_slopes must have shape ({H},) or ({B}, {H}): one slope per query head, optionally per batch entry / sequence "
+                         f"(got {tuple(alibi_slopes.shape)})")
+    if not alibi_slopes.is_contiguous():
+        raise ValueError("alibi_slopes must be contiguous")
+    if alibi_slopes.device != device:
+        raise ValueError(f"alibi_slopes must be on q's device ({device}; got {alibi_slopes.device})")
+    if dtype == torch.float32:
+        raise ValueError("alibi_slopes: ALiBi runs on float16 / bfloat16 inputs only (no fp32 ALiBi path)")
+    if D > 128:
+        raise ValueError(f"alibi_slopes: ALiBi supports head dims up to 128 (got {D})")
+    for cond, msg in extra:
+        if cond:
+            raise ValueError(f"alibi_slopes: {msg}")
+    return alibi_slopes, (H if alibi_slopes.dim() == 2 else 0)
+
+
+def _alibi_window(win, is_causal):
+    """The window an ALiBi entry point is given: a true window as it is, else (-1, -1) / (-1, 0) — the ALiBi kernels run every mask."""
+    return win if win is not None else ((-1, 0) if is_causal else (-1, -1))
+
+
 def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd", out_f32=False,
-                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1)):
+                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), alibi_slopes=None):
     """General forward: q (B,H,Nq,D) / k,v (B,Hk,Nk,D) for ``layout='bhnd'`` or
     (B,N,H,D) for ``layout='bnhd'``; any batch/head/row strides, unit stride along D.
     Returns ``(out, lse)``; ``out`` has q's shape (fp32 when ``out_f32``), ``lse`` is (B,H,Nq) fp32.
@@ -83,7 +116,10 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     ``exact_max``: TFA_FWD_EXACT_MAX — P is rounded to 16 bits at the reference's own points (exact running row maximum per
     KV tile, main_torch_only.py:240-260); head dims up to 128.
     ``window_size=(left, right)``: FlashAttention-2's local (sliding-window) attention — key j is visible to row i iff
-    i + (Nk - Nq) - left <= j <= i + (Nk - Nq) + right, -1 = unbounded, ``is_causal`` forces right = 0 (tfa_fwd_local)."""
+    i + (Nk - Nq) - left <= j <= i + (Nk - Nq) + right, -1 = unbounded, ``is_causal`` forces right = 0 (tfa_fwd_local).
+    ``alibi_slopes``: FlashAttention-2's ALiBi — float32 (H,) or (B, H) on q's device; ``-slope[b, h] * |i + (Nk - Nq) - j|`` is added to the scaled
+    scores before the mask and the softmax, and the returned LSE includes it (tfa_fwd_alibi; the slopes are read by the kernels only; with any mask
+    or window; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -111,6 +147,8 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
                   extra=((exact_max, "no exact_max form of the local kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
     if win == (-1, 0):                               # (the causal mask itself: tfa_fwd with is_causal)
         win, is_causal = None, True
+    alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D,
+                   extra=((exact_max, "no exact_max form of the ALiBi kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
 
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
@@ -144,10 +182,13 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     # tfa_fwd_splitkv's merge writes a dense (B,H,Nq,D) result: gate on the exact strides it checks (is_contiguous() ignores the
     # strides of size-1 dims, and Nq == 1 is the very shape auto-split targets)
     dense_out = (out.stride(3) == 1 and out.stride(2) == D and out.stride(1) == Nq * D and out.stride(0) == H * Nq * D)
-    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None) else 1
+    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None) else 1
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if win is not None:
+        if alibi is not None:
+            aw = _alibi_window(win, is_causal)
+            _lib.check(L.tfa_fwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
+        elif win is not None:
             _lib.check(L.tfa_fwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
         elif splits > 1:
             need = L.tfa_fwd_splitkv_workspace(C.byref(p), int(splits))
@@ -263,14 +304,16 @@ def make_bwd_params(q, k, v, out, lse, dout, dq, dk, dv, delta, is_causal, softm
     return p
 
 
-def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None, window_size=(-1, -1)):
+def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None, window_size=(-1, -1),
+                   alibi_slopes=None):
     """Backward of ``flash_attn_fwd``: returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``).
     ``out`` and ``lse`` are the forward's results for the same q, k, v; ``dout`` is the upstream gradient
     (shape/dtype of ``out``).  The reference has no backward — it only saves the LSE for one
     (flash_attention_cutlass/csrc/flash_attention.cu:353-354,614-623); maps onto tfa_bwd (include/tfa.h).
     ``workspace``: None (default: the O(N)-memory 7-GEMM form), True (allocate tfa_bwd_workspace_bytes of scratch for this call)
     or a caller-owned uint8 / any-dtype CUDA tensor of at least that many bytes: tfa_bwd then keeps dS and executes 5 GEMMs.
-    ``window_size``: the forward's sliding window (tfa_bwd_local; no workspace form)."""
+    ``window_size``: the forward's sliding window (tfa_bwd_local; no workspace form).
+    ``alibi_slopes``: the forward's ALiBi slopes (tfa_bwd_alibi; no workspace form); they receive no gradient."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (dout, "dout")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -293,6 +336,8 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
     win = _window(window_size, is_causal, nq, nk, q.dtype, D, extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     if win == (-1, 0):
         win, is_causal = None, True
+    alibi = _alibi(alibi_slopes, q.shape[0], lse_shape[1], q.device, q.dtype, D,
+                   extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.empty(q.shape, dtype=gdt, device=q.device)
@@ -310,7 +355,10 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         p.workspace_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if win is not None:
+        if alibi is not None:
+            aw = _alibi_window(win, is_causal)
+            _lib.check(_lib.lib().tfa_bwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
+        elif win is not None:
             _lib.check(_lib.lib().tfa_bwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().tfa_bwd(C.byref(p), C.c_void_p(stream)))
@@ -378,31 +426,32 @@ class _FlashAttnBNHD(torch.autograd.Function):
     """autograd glue for ``flash_attn_func``: forward = tfa_fwd, backward = tfa_bwd, both on (B,N,H,D) views."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1)):
-        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size)
-        ctx.save_for_backward(q, k, v, out, lse)
+    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1), alibi_slopes=None):
+        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size, alibi_slopes=alibi_slopes)
+        ctx.save_for_backward(q, k, v, out, lse, alibi_slopes)   # (the slopes, or None: they get no gradient)
         ctx.causal, ctx.scale, ctx.window = causal, softmax_scale, window_size
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
+        q, k, v, out, lse, slopes = ctx.saved_tensors
         if dout.stride(3) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window)
-        return dq, dk, dv, None, None, None
+        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, alibi_slopes=slopes)
+        return dq, dk, dv, None, None, None, None
 
 
-def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1)):
+def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1), alibi_slopes=None):
     """(B,N,H,D)-layout entry with the signature the reference's scripts use for comparison
     (flash_attention_cutlass/test.py:71-76, flash_attention_py/main_torch_only.py:304);
     supports GQA/MQA (fewer K/V heads).  Differentiable (like the official function the reference
     compares against): when an input requires grad the backward runs tfa_bwd.  ``window_size=(left, right)``: FlashAttention-2's local
-    (sliding-window) attention, -1 = unbounded, ``causal`` forces right = 0 (tfa_fwd_local / tfa_bwd_local)."""
+    (sliding-window) attention, -1 = unbounded, ``causal`` forces right = 0 (tfa_fwd_local / tfa_bwd_local).  ``alibi_slopes``: FlashAttention-2's
+    ALiBi, float32 (H,) or (B, H): ``-slope * |i + (Nk - Nq) - j|`` added to the scaled scores (tfa_fwd_alibi / tfa_bwd_alibi); no gradient for them."""
     window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size)
-    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size)
+        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size, alibi_slopes)
+    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size, alibi_slopes=alibi_slopes)
     return out
 
 
@@ -447,12 +496,13 @@ def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
 
 
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1)):
+                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1), alibi_slopes=None):
     """Packed variable-length forward (tfa_fwd_varlen, include/tfa.h): q (total_q, H, D), k / v (total_k, Hk, D), sequence b is rows
     [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v (device int32, B + 1 entries, never read on the host).
     Causal masking per sequence, bottom-right aligned.  Returns ``(out, lse)``: ``out`` shaped like q (fp32 when ``out_f32``), ``lse`` fp32 (H, total_q).
     Rows outside every sequence are not written (a caller-provided ``out`` keeps them).  ``window_size``: FlashAttention-2's sliding window per
-    sequence (tfa_fwd_varlen_local)."""
+    sequence (tfa_fwd_varlen_local).  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H) with B the number of sequences; the distance is taken per sequence
+    (tfa_fwd_varlen_alibi)."""
     _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     B = cu_seqlens_q.numel() - 1
     total_q, H, D = q.shape
@@ -462,6 +512,7 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
     if win == (-1, 0):
         win, is_causal = None, True
+    alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
     else:
@@ -487,7 +538,10 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if win is not None:
+        if alibi is not None:
+            aw = _alibi_window(win, is_causal)
+            _lib.check(_lib.lib().tfa_fwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
+        elif win is not None:
             _lib.check(_lib.lib().tfa_fwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().tfa_fwd_varlen(C.byref(p), C.c_void_p(stream)))
@@ -495,7 +549,7 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
 
 
 def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          grad_f32=False, window_size=(-1, -1)):
+                          grad_f32=False, window_size=(-1, -1), alibi_slopes=None):
     """Backward of ``flash_attn_varlen_fwd`` (tfa_bwd_varlen): returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``); for GQA dk / dv
     are summed over the query heads of each K/V head within each sequence.  Rows outside every sequence get zero gradients: the kernels never write
     them, so the three results are allocated zeroed (one memset of dq, dk and dv per call)."""
@@ -512,6 +566,7 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
     if win == (-1, 0):
         win, is_causal = None, True
+    alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.zeros(q.shape, dtype=gdt, device=q.device)
@@ -535,7 +590,10 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     p.grad_dtype = _lib.TFA_F32 if grad_f32 else _DT[q.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if win is not None:
+        if alibi is not None:
+            aw = _alibi_window(win, is_causal)
+            _lib.check(_lib.lib().tfa_bwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
+        elif win is not None:
             _lib.check(_lib.lib().tfa_bwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().tfa_bwd_varlen(C.byref(p), C.c_void_p(stream)))
@@ -546,33 +604,35 @@ class _FlashAttnVarlen(torch.autograd.Function):
     """autograd glue for ``flash_attn_varlen_func``: forward = tfa_fwd_varlen, backward = tfa_bwd_varlen."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=(-1, -1)):
-        out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=window_size)
-        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=(-1, -1), alibi_slopes=None):
+        out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=window_size,
+                                         alibi_slopes=alibi_slopes)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, alibi_slopes)   # (the slopes, or None: they get no gradient)
         ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        q, k, v, out, lse, cu_q, cu_k, slopes = ctx.saved_tensors
         max_q, max_k, causal, scale, window = ctx.args
         if dout.stride(2) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window)
-        return dq, dk, dv, None, None, None, None, None, None, None
+        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window, alibi_slopes=slopes)
+        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
-                           window_size=(-1, -1)):
+                           window_size=(-1, -1), alibi_slopes=None):
     """Packed variable-length attention with FlashAttention-2's positional signature (flash_attn_varlen_func): q (total_q, H, D), k / v
     (total_k, Hk, D), cu_seqlens_q / _k device int32 (B + 1), max_seqlen_q / _k host integers.  Differentiable: when an input requires grad the
     backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0).  ``window_size=(left, right)``: FlashAttention-2's sliding
-    window per sequence, -1 = unbounded, ``causal`` forces right = 0."""
+    window per sequence, -1 = unbounded, ``causal`` forces right = 0.  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H), B = the number of sequences."""
     if dropout_p != 0.0:
         raise NotImplementedError("flash_attn_varlen_func: dropout is not supported (dropout_p must be 0)")
     window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale, window_size)
+        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale, window_size,
+                                      alibi_slopes)
     out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False,
-                                   window_size=window_size)
+                                   window_size=window_size, alibi_slopes=alibi_slopes)
     return out
