@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -84,7 +84,7 @@ enum tfa_status {
                                * slower — at every head dim since 0.1.9; tfa_fwd_splitkv then runs one windowed launch per key chunk) */
   TFA_ERR_ALIGN = -6,         /* a base pointer is not 16-byte aligned */
   TFA_ERR_VARIANT = -7,       /* unknown kernel variant */
-  TFA_ERR_SCALE = -8          /* softmax_scale is not finite or is <= 0 */
+  TFA_ERR_SCALE = -8          /* softmax_scale is not finite or is <= 0; the _softcap entry points: softcap is not finite or is <= 0 */
 };
 
 /*
@@ -510,6 +510,59 @@ int tfa_bwd_alibi_plan(const tfa_bwd_params* p, const float* alibi_slopes, int64
 int tfa_bwd_varlen_alibi(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
                          void* stream);
 int tfa_bwd_varlen_alibi_plan(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+
+/* ---- Soft-capping (FlashAttention-2's softcap: tanh logit capping, Gemma-2 / Grok style) -----------------------------------------------------
+ * The ALiBi entry points' arguments with `softcap` in front; alibi_slopes may be NULL here (no bias).  With x[i,j] = softmax_scale * q_i . k_j, c = softcap > 0
+ * and shift = Nk - Nq per sequence:
+ *     S[i,j] = c * tanh(x[i,j] / c)  -  alibi_slopes[b * slopes_batch_stride + h] * | i + shift - j |        (second term only with slopes)
+ * then the mask (is_causal / the window, as the _alibi entry points read them; (-1, -1) = none), the softmax and P V.  The ORDER is FlashAttention-2's: the cap
+ * on the scaled scores first, then the bias, then the mask.  Everything downstream is defined on S: lse is the true logsumexp_j S[i,j] (capped, biased,
+ * masked; tfa_bwd_softcap and tfa_merge consume it unchanged); rows that see no key get out = 0 and lse = +inf.  The backward recomputes P from the same S,
+ * forms dS = P o (dP - delta) and passes dS * (1 - tanh^2(x / c)) on to dq and dk (the chain rule through the cap); dv and delta are as without a cap.
+ * softcap is a host float: no gradient, nothing is read from the device, nothing synchronises, a call can be captured in a graph.  Zero slopes give the bits
+ * of NULL slopes.
+ * Every call runs the soft-capping form of the LOCAL instantiations, whatever the window and with or without slopes (one kernel per dtype, width and fixed /
+ * varlen; the slopes are a launch-uniform branch in it): il8 (variant 30) or il4 (32) as tfa_fwd_alibi chooses, every tile through the compiler-scheduled
+ * bodies, rounding rule TFA_RULE_LAZY for both dtypes; the backward is the dQ launch (which forms delta) and the fused dK/dV launch of that form,
+ * deterministic, never the dS-workspace form.  tfa_fwd_suggest_splits / split-KV have no soft-capping form.
+ * tanh: the GPU has no such instruction; the kernels form 1 - tanh(x / c) = 1 / (0.5 + exp2(2 log2(e) x / c - 1)) from one hardware exponential and one
+ * hardware reciprocal (1 ulp each).  It saturates to -c / +c when the exponential underflows / overflows, never NaN for finite scores.  Accuracy: a capped
+ * score is within 2^-20 * c (absolute, scaled-score domain) of the exact c * tanh(x / c) — 5e-5 at c = 50 — which is also the bound on what the cap adds
+ * to the LSE's error; the derivative 1 - tanh^2 is formed as q (2 - q), q = 1 - tanh, without cancellation.
+ * Refused, nothing launched: softcap <= 0 (0 included: without a cap call the other entry points), NaN or infinite (TFA_ERR_SCALE); with slopes, what
+ * tfa_fwd_alibi refuses for them (TFA_ERR_ALIGN, TFA_ERR_STRIDE); and what the local form refuses, with its codes: head dims above 128 (TFA_ERR_HEAD_DIM),
+ * fp32 inputs (TFA_ERR_DTYPE), any flag — TFA_FWD_EXACT_MAX included — (TFA_ERR_SHAPE), a window side below -1 (TFA_ERR_SHAPE), kv_offset / nk_total != 0
+ * (TFA_ERR_SHAPE), Nq + Nk >= 2^28 (TFA_ERR_SHAPE), slices that need per-tile descriptors (TFA_ERR_STRIDE), a forced variant other than 30 / 32
+ * (TFA_ERR_VARIANT).
+ * Tolerances: the header's "which tolerance each path guarantees", LSE |d| <= 1e-4 * max(1, |lse|) as for ALiBi.
+ * Rates: tools/bench_softcap.py measures them against the same masks without a cap (README.md, "Soft-capping"; DESIGN.md 8d). */
+int tfa_fwd_softcap(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                    void* stream);
+/* Validate and report the launch geometry of tfa_fwd_softcap without launching (no GPU needed). */
+int tfa_fwd_softcap_plan(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                         int* grid, int* block, int* lds_bytes);
+/* The kernel variant tfa_fwd_softcap runs for *p (30 or 32), or a negative TFA_ERR_* code. */
+int tfa_fwd_softcap_variant(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+/* The row reference P is rounded against: TFA_RULE_LAZY (bf16 and fp16), or a negative TFA_ERR_* code. */
+int tfa_fwd_softcap_rounding_rule(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                  int window_right);
+/* Packed variable-length batches: b indexes the sequence, the bias distance is taken per sequence. */
+int tfa_fwd_varlen_softcap(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                           int window_right, void* stream);
+int tfa_fwd_varlen_softcap_plan(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                int window_right, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_varlen_softcap_variant(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                   int window_right);
+int tfa_fwd_varlen_softcap_rounding_rule(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride,
+                                         int window_left, int window_right);
+/* The backward of a soft-capped forward (same softcap, slopes, window and params as tfa_bwd / tfa_bwd_varlen); _plan validates without launching. */
+int tfa_bwd_softcap(const tfa_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                    void* stream);
+int tfa_bwd_softcap_plan(const tfa_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right);
+int tfa_bwd_varlen_softcap(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                           int window_right, void* stream);
+int tfa_bwd_varlen_softcap_plan(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                int window_right);
 
 #ifdef __cplusplus
 }

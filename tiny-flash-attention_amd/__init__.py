@@ -11,7 +11,7 @@ Reference-named entry points (same names, argument order and return shapes):
 * ``flash_attention_v2_cuda(q, k, v) -> out`` (flash_attention_cuda/csrc/attention_api.cpp:6-14)
 * ``flash_attn(q, k, v, is_causal, softmax_scale) -> out`` (flash_attention_c/csrc/ops.cu:4-8)
 
-FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen_func`` with ``causal``, ``window_size`` and ``alibi_slopes``
+FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen_func`` with ``causal``, ``window_size``, ``alibi_slopes`` and ``softcap``
 (GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.
 """
 from .ops import (  # noqa: F401

@@ -68,6 +68,18 @@ SYMBOLS = (
     "tfa_bwd_alibi_plan",
     "tfa_bwd_varlen_alibi",
     "tfa_bwd_varlen_alibi_plan",
+    "tfa_fwd_softcap",
+    "tfa_fwd_softcap_plan",
+    "tfa_fwd_softcap_variant",
+    "tfa_fwd_softcap_rounding_rule",
+    "tfa_fwd_varlen_softcap",
+    "tfa_fwd_varlen_softcap_plan",
+    "tfa_fwd_varlen_softcap_variant",
+    "tfa_fwd_varlen_softcap_rounding_rule",
+    "tfa_bwd_softcap",
+    "tfa_bwd_softcap_plan",
+    "tfa_bwd_varlen_softcap",
+    "tfa_bwd_varlen_softcap_plan",
 )
 
 
@@ -317,6 +329,16 @@ def lib():
                        ("tfa_fwd_varlen_alibi_variant", [PV] + AL), ("tfa_fwd_varlen_alibi_rounding_rule", [PV] + AL),
                        ("tfa_bwd_alibi", [PB] + AL + [C.c_void_p]), ("tfa_bwd_alibi_plan", [PB] + AL),
                        ("tfa_bwd_varlen_alibi", [PVB] + AL + [C.c_void_p]), ("tfa_bwd_varlen_alibi_plan", [PVB] + AL)):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
+    # soft-capping: the ALiBi entry points' arguments with (float softcap) in front of the slopes, which may be NULL
+    SC = [C.c_float] + AL
+    for name, args in (("tfa_fwd_softcap", [PF] + SC + [C.c_void_p]), ("tfa_fwd_softcap_plan", [PF] + SC + [IP, IP, IP]),
+                       ("tfa_fwd_softcap_variant", [PF] + SC), ("tfa_fwd_softcap_rounding_rule", [PF] + SC),
+                       ("tfa_fwd_varlen_softcap", [PV] + SC + [C.c_void_p]), ("tfa_fwd_varlen_softcap_plan", [PV] + SC + [IP, IP, IP]),
+                       ("tfa_fwd_varlen_softcap_variant", [PV] + SC), ("tfa_fwd_varlen_softcap_rounding_rule", [PV] + SC),
+                       ("tfa_bwd_softcap", [PB] + SC + [C.c_void_p]), ("tfa_bwd_softcap_plan", [PB] + SC),
+                       ("tfa_bwd_varlen_softcap", [PVB] + SC + [C.c_void_p]), ("tfa_bwd_varlen_softcap_plan", [PVB] + SC)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     _lib = L

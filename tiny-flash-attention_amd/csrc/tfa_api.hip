@@ -341,7 +341,7 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
 //        (tfa_fwd_kernel.h: varlen_seq) — the host never reads them;
 //   win: the normalised {left, right} of a true window (window_form: WIN_LOCAL), or nullptr;
 //   al:  the ALiBi slopes (checked by the caller), or nullptr: with them the ALiBi form of the local kernels runs whatever the window is — win is then always given,
-//        its unbounded sides as -1 (set_window).
+//        its unbounded sides as -1 (set_window).  al->capped: the soft-capping form instead (tfa_fwd_softcap; al->slopes may then be null).
 // Kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else (the key-split kernels, split-KV and decode row packing have no such form); a
 // variant forced by tfa_set_variant must be one of the two.
 int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_varlen_fwd_params* vl, const int* win, const tfa::AlibiArg* al, void* stream,
@@ -381,6 +381,8 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     using T = typename decltype(k)::T;
     constexpr int W = decltype(k)::W;
     if (!win) return tfa::launch_fwd_form<T, W, true, false>(a, causal, f32out, variant, s, geom, dry);   // (no window: always varlen here)
+    if (al && al->capped) return vl ? tfa::launch_fwd_form<T, W, true, true, false, true>(a, causal, f32out, variant, s, geom, dry)
+                                    : tfa::launch_fwd_form<T, W, false, true, false, true>(a, causal, f32out, variant, s, geom, dry);
     if (al) return vl ? tfa::launch_fwd_form<T, W, true, true, true>(a, causal, f32out, variant, s, geom, dry)
                       : tfa::launch_fwd_form<T, W, false, true, true>(a, causal, f32out, variant, s, geom, dry);
     return vl ? tfa::launch_fwd_form<T, W, true, true>(a, causal, f32out, variant, s, geom, dry)
@@ -406,7 +408,7 @@ int run_local(const tfa_fwd_params* p, const int* w, const tfa::AlibiArg* al, vo
   if (p->flags != 0) return TFA_ERR_SHAPE;
   if (al) {
     if (p->H <= 0) return TFA_ERR_SHAPE;
-    const int st = tfa::check_alibi(*al, p->H);
+    const int st = tfa::check_alibi(*al, p->H, p->softmax_scale);
     if (st != TFA_OK) return st;
   }
   return run_form(*p, *p, nullptr, win, al, stream, geom, dry, variant_out, rule_out);
@@ -431,7 +433,7 @@ int run_varlen(const tfa_varlen_fwd_params* p, const int* w, const tfa::AlibiArg
     if (form < 0) return form;
   }
   if (al) {
-    const int st = tfa::check_alibi(*al, p->H);
+    const int st = tfa::check_alibi(*al, p->H, p->softmax_scale);
     if (st != TFA_OK) return st;
   }
   tfa_fwd_params f;
@@ -785,6 +787,60 @@ int tfa_fwd_varlen_alibi_rounding_rule(const tfa_varlen_fwd_params* p, const flo
   return variant_or_rule(call, true);
 }
 #undef TFA_ALIBI_CALL
+
+// Soft-capping: the ALiBi call with the cap in front; the slopes may be NULL
+#define TFA_SOFTCAP_CALL(p, vp)                                                 \
+  const int w[2] = {window_left, window_right};                                 \
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride, true, softcap};     \
+  const FwdCall call{p, vp, w, &al}
+int tfa_fwd_softcap(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                    void* stream) {
+  TFA_SOFTCAP_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return route(call, stream);
+}
+int tfa_fwd_softcap_plan(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                         int* grid, int* block, int* lds_bytes) {
+  TFA_SOFTCAP_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return plan(call, grid, block, lds_bytes);
+}
+int tfa_fwd_softcap_variant(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  TFA_SOFTCAP_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, false);
+}
+int tfa_fwd_softcap_rounding_rule(const tfa_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                  int window_right) {
+  TFA_SOFTCAP_CALL(p, nullptr);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, true);
+}
+int tfa_fwd_varlen_softcap(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                           int window_right, void* stream) {
+  TFA_SOFTCAP_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return route(call, stream);
+}
+int tfa_fwd_varlen_softcap_plan(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                int window_right, int* grid, int* block, int* lds_bytes) {
+  TFA_SOFTCAP_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return plan(call, grid, block, lds_bytes);
+}
+int tfa_fwd_varlen_softcap_variant(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                   int window_right) {
+  TFA_SOFTCAP_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, false);
+}
+int tfa_fwd_varlen_softcap_rounding_rule(const tfa_varlen_fwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride,
+                                         int window_left, int window_right) {
+  TFA_SOFTCAP_CALL(nullptr, p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, true);
+}
+#undef TFA_SOFTCAP_CALL
 
 int tfa_fwd_variant(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, false); }   // (run()'s final choice, after GQA packing and its fall-back)
 int tfa_fwd_rounding_rule(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, true); }

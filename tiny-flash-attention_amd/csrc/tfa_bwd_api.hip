@@ -250,8 +250,9 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
 
 // The varlen and local forms: the dQ launch (which forms delta) and then the fused dK/dV launch of the form kernels (VARLEN / LOCAL instantiations:
 // tfa_bwd_form_inst.inc).  a holds everything but the gradients; v is the problem as the kernels see it (run_bwd_varlen: one sequence, batch stride 0).
-// alibi: the ALiBi form of the local kernels (a.slopes set; local is then true whatever the window)
-int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, bool alibi, void* stream, bool dry) {
+// alibi: the ALiBi form of the local kernels (a.slopes set; local is then true whatever the window); capped: their soft-capping form instead (a.softcap_cr set,
+// a.slopes set or null)
+int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, bool alibi, bool capped, void* stream, bool dry) {
   const int gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
   const bool causal = v.is_causal != 0, f32 = v.grad_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -261,6 +262,8 @@ int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, 
       using T = typename decltype(k)::T;
       constexpr int W = decltype(k)::W;
       if (!local) return tfa::launch_bwd_form<T, W, true, false>(m, keys, (int)grid, causal, f32, s, dry);   // (no window: always varlen here)
+      if (capped) return varlen ? tfa::launch_bwd_form<T, W, true, true, false, true>(m, keys, (int)grid, causal, f32, s, dry)
+                                : tfa::launch_bwd_form<T, W, false, true, false, true>(m, keys, (int)grid, causal, f32, s, dry);
       if (alibi) return varlen ? tfa::launch_bwd_form<T, W, true, true, true>(m, keys, (int)grid, causal, f32, s, dry)
                                : tfa::launch_bwd_form<T, W, false, true, true>(m, keys, (int)grid, causal, f32, s, dry);
       return varlen ? tfa::launch_bwd_form<T, W, true, true>(m, keys, (int)grid, causal, f32, s, dry)
@@ -299,14 +302,14 @@ int run_bwd_local(const tfa_bwd_params* p, const int* w, const tfa::AlibiArg* al
   }
   int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
   if (st) return st;
-  if (al && (st = tfa::check_alibi(*al, p->H)) != TFA_OK) return st;
+  if (al && (st = tfa::check_alibi(*al, p->H, p->softmax_scale)) != TFA_OK) return st;
   tfa::BArgs a;
   st = fill_args(*p, nullptr, &a);
   if (st) return st;
   a.fuse_delta = 1;                                  // (the dQ launch forms delta)
   tfa::set_window(&a, win[0], win[1], p->Nq, p->Nk);
   if (al) tfa::set_alibi(&a, *al);
-  return launch_form_pair(a, *p, false, true, al != nullptr, stream, dry);
+  return launch_form_pair(a, *p, false, true, al != nullptr, al && al->capped, stream, dry);
 }
 
 // Packed variable-length batches (include/tfa.h: tfa_bwd_varlen, tfa_bwd_varlen_local — w: the window, or nullptr): as in the forward (tfa_api.hip: run_varlen)
@@ -334,7 +337,7 @@ int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, const tfa::Alib
   const bool shape = p->total_q > 0 && p->total_k > 0 && p->flags == 0 && p->reserved_ == 0;
   int st = check_bwd(v, p->cu_seqlens_q && p->cu_seqlens_k, shape, 128, window_st, 4, (int64_t)p->H * p->total_q);
   if (st) return st;
-  if (al && (st = tfa::check_alibi(*al, p->H)) != TFA_OK) return st;
+  if (al && (st = tfa::check_alibi(*al, p->H, p->softmax_scale)) != TFA_OK) return st;
   tfa::BArgs a;
   st = fill_args(v, nullptr, &a);
   if (st) return st;
@@ -343,7 +346,7 @@ int run_bwd_varlen(const tfa_varlen_bwd_params* p, const int* w, const tfa::Alib
   a.total_q = p->total_q; a.total_k = p->total_k;   // (BArgs: in the bytes of the windowed / workspace forms' fields, which varlen launches never read)
   if (local) tfa::set_window(&a, win[0], win[1], v.Nq, v.Nk);
   if (al) tfa::set_alibi(&a, *al);
-  return launch_form_pair(a, v, true, local, al != nullptr, stream, dry);
+  return launch_form_pair(a, v, true, local, al != nullptr, al && al->capped, stream, dry);
 }
 
 }  // namespace
@@ -387,6 +390,29 @@ int tfa_bwd_varlen_alibi(const tfa_varlen_bwd_params* p, const float* alibi_slop
 int tfa_bwd_varlen_alibi_plan(const tfa_varlen_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
   const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride};
+  return run_bwd_varlen(p, w, &al, nullptr, true);
+}
+int tfa_bwd_softcap(const tfa_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right,
+                    void* stream) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride, true, softcap};
+  return run_bwd_local(p, w, &al, stream, false);
+}
+int tfa_bwd_softcap_plan(const tfa_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride, true, softcap};
+  return run_bwd_local(p, w, &al, nullptr, true);
+}
+int tfa_bwd_varlen_softcap(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                           int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride, true, softcap};
+  return run_bwd_varlen(p, w, &al, stream, false);
+}
+int tfa_bwd_varlen_softcap_plan(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
+                                int window_right) {
+  const int w[2] = {window_left, window_right};
+  const tfa::AlibiArg al{alibi_slopes, slopes_batch_stride, true, softcap};
   return run_bwd_varlen(p, w, &al, nullptr, true);
 }
 int tfa_debug_bwd_split(int on) { g_bwd_split = on & 15; return TFA_OK; }

@@ -1,0 +1,7 @@
+// one soft-capping (softcap) backward instantiation unit: dtype=bf16 head_dim=64 fixed-length
+#define TFA_T __bf16
+#define TFA_D 64
+#define TFA_VARLEN false
+#define TFA_LOCAL true
+#define TFA_SOFTCAP true
+#include "tfa_bwd_form_inst.inc"

@@ -55,8 +55,9 @@ hipError_t launch_bwd_dq_ws(const BArgs& a, int grid, bool causal, bool f32out, 
 // the packed variable-length (VARLEN: tfa_bwd_varlen) and local (LOCAL: tfa_bwd_local, tfa_bwd_varlen_local) forms: keys = false the dQ launch
 // (grid = B * H * ceil(Nq / 256)), keys = true the fused dK/dV launch (grid = B * Hk * ceil(Nk / 128)) — Nq / Nk = max_seqlen_q / _k for varlen.  The local
 // kernels are the causal template only (`causal` is ignored).  One unit per (dtype, width, form): tfa_bwd_inst_varlen_<dtype>_<D>.hip (VARLEN) and
-// tfa_bwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN); ALIBI: the ALiBi form of the local kernels, tfa_bwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip
-template <typename T, int D, bool VARLEN, bool LOCAL, bool ALIBI = false>
+// tfa_bwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN); ALIBI: the ALiBi form of the local kernels, tfa_bwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip;
+// SOFTCAP: their soft-capping form (slopes optional at run time), tfa_bwd_inst_softcap_<dtype>_<D>_<fx|vl>.hip
+template <typename T, int D, bool VARLEN, bool LOCAL, bool ALIBI = false, bool SOFTCAP = false>
 hipError_t launch_bwd_form(const BArgs& a, bool keys, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
 template <typename T, int D>
 hipError_t launch_delta(const void* o, const void* dout, float* delta, const long long* os, const long long* ds, int H, int Nq, long long rows,

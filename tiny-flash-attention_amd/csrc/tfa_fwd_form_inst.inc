@@ -6,18 +6,24 @@
 // CAUSAL template: the right edge is the causal limit moved by win_right (a window without a right edge carries win_right >= Nq - 1).
 // TFA_ALIBI (tfa_fwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip): the ALiBi form of the local instantiations (VF_IL_ALIBI) — full, causal and windowed attention with
 // slopes are this one kernel per (dtype, width, fixed / varlen), the window's missing sides carried as unbounded.
+// TFA_SOFTCAP (tfa_fwd_inst_softcap_<dtype>_<D>_<fx|vl>.hip): the soft-capping form of the local instantiations (VF_IL_SOFTCAP), with or without slopes (a run-time
+// choice of the one kernel: TFA_ALIBI stays false), every mask.
 #include "tfa_launch.h"
 #if !defined(TFA_ALIBI)
 #define TFA_ALIBI false
+#endif
+#if !defined(TFA_SOFTCAP)
+#define TFA_SOFTCAP false
 #endif
 
 namespace tfa {
 
 template <>
-hipError_t launch_fwd_form_c<TFA_T, TFA_D, TFA_VARLEN, TFA_LOCAL, TFA_CAUSAL, TFA_ALIBI>(const KArgs& a, bool f32out, int variant, hipStream_t s, LaunchGeom* g, bool dry) {
+hipError_t launch_fwd_form_c<TFA_T, TFA_D, TFA_VARLEN, TFA_LOCAL, TFA_CAUSAL, TFA_ALIBI, TFA_SOFTCAP>(const KArgs& a, bool f32out, int variant, hipStream_t s, LaunchGeom* g, bool dry) {
   static_assert(TFA_CAUSAL || !TFA_LOCAL, "the local kernels are the causal template");
   static_assert(TFA_LOCAL || !TFA_ALIBI, "the ALiBi kernels are a form of the local ones");
-  constexpr int FORM = (TFA_VARLEN ? VF_IL_VARLEN : 0) | (TFA_LOCAL ? VF_IL_LOCAL : 0) | (TFA_ALIBI ? VF_IL_ALIBI : 0);
+  static_assert(!TFA_SOFTCAP || (TFA_LOCAL && !TFA_ALIBI), "the softcap kernels are a form of the local ones; their slopes are a run-time choice");
+  constexpr int FORM = (TFA_VARLEN ? VF_IL_VARLEN : 0) | (TFA_LOCAL ? VF_IL_LOCAL : 0) | (TFA_ALIBI ? VF_IL_ALIBI : 0) | (TFA_SOFTCAP ? VF_IL_SOFTCAP : 0);
   constexpr int PAIR = TFA_LOCAL ? 0 : VF_PAIR;   // (the local form: one query block per work item, no causal pairs — and so no PREF2)
   constexpr int VF30 = PAIR | (TFA_LOCAL ? 0 : VF_IL_PREF2) | VF_IL_DMASPREAD | VF_IL_EPI | VF_IL_QLDS | FORM;   // variant 30's main instantiation (tfa_fwd_inst.inc)
   constexpr int VF32 = PAIR | VF_IL_EPI | VF_IL_EPI_INPLACE | FORM;                                              // variant 32's

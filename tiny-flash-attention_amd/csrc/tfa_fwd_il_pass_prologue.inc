@@ -68,7 +68,7 @@
       const unsigned kb = kbuf * TILE_BYTES;
 #pragma unroll
       for (int i = 0; i < N1; ++i) s[KT(i)] = E::mfma(k_frag_rt(kb, i), qf[KS(i)], s[KT(i)]);
-      if constexpr (ALIBI) apply_bias(t, s);
+      if constexpr (SMOD) apply_bias(t, s);
       if (needs_mask(t)) apply_mask(t, s);
       float mx = s[0][0];
 #pragma unroll

@@ -67,7 +67,7 @@
         TFA_IL_PAD_HERE
         __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (ALIBI) {                          // the bias in front of the mask and of the row maximum, on every tile
+      if constexpr (SMOD) {                           // the cap and / or the bias in front of the mask and of the row maximum, on every tile
         apply_bias(j + 1, snext);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -134,7 +134,7 @@
     // process (either parity), S of that tile in sA / sB by parity, its half-wave row maximum in mx.  Everything else — masked and last tiles, re-bases,
     // odd entries — stays with the compiler-scheduled bodies below.
     constexpr bool ASMBASE = (D == 128 || D == 64) && DVB == D / 32 && (AB & ~ILAB_TRACE) == 0 && !WIN && !(VF & VF_IL_IDLE) && !(VF & (VF_IL_DMASTAGGER | VF_IL_SEAM)) &&
-                             (PPW == 1 || PPW == 2 || PPW == 4) && (!EXACT || (D == 128 && PPW == 2)) && TFA_IL_USE_ASMLOOP && !ALIBI;   // (the statement carries no bias)
+                             (PPW == 1 || PPW == 2 || PPW == 4) && (!EXACT || (D == 128 && PPW == 2)) && TFA_IL_USE_ASMLOOP && !SMOD;   // (the statement carries no bias and no cap)
     constexpr bool ASMLOOP = ASMBASE && !EXACT;        // the lazy-reference loop
     constexpr bool ASMLOOPX = ASMBASE && EXACT;        // the exact-running-max loop (variant 38): four bodies — parity x {plain, also re-basing O}
     // (the loop's LDS-DMA requests carry the tile's byte offset as their SCALAR offset, which the descriptor's bounds check does not see: it only asks for
@@ -262,7 +262,7 @@
       //  behind it, the last tiles of a block whose keys end inside a tile — goes to the burst-structured path, which serves any tile: same operations in the
       //  same order, bits identical; four unrolled instantiations of `fused` and their registers less in the kernel)
       if (!ASMLOOP && j + 1 < nact && !trigger(mA)) {
-        if (ALIBI ? !needs_mask(j + 1) : j + 1 < fm) fused(C0{}, MN{}, MN{}, 1.f, j, sA, sB, mB);   // (ALIBI: the pinned bodies take the left-edge tiles too)
+        if (SMOD ? !needs_mask(j + 1) : j + 1 < fm) fused(C0{}, MN{}, MN{}, 1.f, j, sA, sB, mB);   // (ALIBI, SOFTCAP: the pinned bodies take the left-edge tiles too)
         else fused(C0{}, MY{}, MN{}, 1.f, j, sA, sB, mB);
       } else {
         slow(j, sA, mA, sB, mB);
@@ -274,7 +274,7 @@
         break;
       }
       if (!ASMLOOP && j + 2 < nact && !trigger(mB)) {
-        if (ALIBI ? !needs_mask(j + 2) : j + 2 < fm) fused(C1{}, MN{}, MN{}, 1.f, j + 1, sB, sA, mA);
+        if (SMOD ? !needs_mask(j + 2) : j + 2 < fm) fused(C1{}, MN{}, MN{}, 1.f, j + 1, sB, sA, mA);
         else fused(C1{}, MY{}, MN{}, 1.f, j + 1, sB, sA, mA);
       } else {
         slow(j + 1, sB, mB, sA, mA);

@@ -24,6 +24,7 @@
 //     (out-of-range rows read as 0 / are not written).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace tfa {
@@ -85,6 +86,9 @@ struct KArgs {
   int nmb;          // number of query blocks per (b,h)
   int nwork;        // work items per (b,h): nmb, or ceil(nmb/2) when causal blocks are paired
   int nbh;          // B*H
+  float softcap_cr; // soft-capping (tfa_fwd_softcap, VF_IL_SOFTCAP): cr = softcap / softmax_scale, the cap in the raw-score domain.  The field fills the four bytes
+                    // of alignment padding in front of qs_b: no other field moves and the struct keeps its size (asserted below), so every existing kernel keeps
+                    // its argument layout; only the softcap instantiations read it, and the host writes it for them alone (set_softcap)
   long long qs_b, qs_h, qs_n;
   long long ks_b, ks_h, ks_n;
   long long vs_b, vs_h, vs_n;
@@ -132,6 +136,7 @@ struct KArgs {
   int kv_stream;    // K and V together reach 768 MiB — a cache the 256 MB memory-side cache cannot keep until the next call: decode
                     // kernels whose K/V tiles no other workgroup reads may stream them with the non-temporal hint (set by the host)
 };
+static_assert(offsetof(KArgs, softcap_cr) == 100 && offsetof(KArgs, qs_b) == 104 && sizeof(KArgs) == 328, "KArgs::softcap_cr lies in former padding: no field moves");
 
 // One sequence of a packed variable-length batch, read on the device (scalar loads: b is uniform) — the host never reads cu_seqlens.  The bounds are clamped
 // into the packed tensors and the lengths to the host's max_seqlen (the arguments' Nq / Nk), so a bad cu_seqlens can misplace rows but never address outside
@@ -209,6 +214,14 @@ static __device__ __forceinline__ s16x4 lds_read_tr16_b64(const char* p) {
 }
 
 static __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// Soft-capping (tfa_fwd_softcap / tfa_bwd_softcap): a raw score s becomes cr * tanh(s / cr), cr = softcap / softmax_scale.  gfx950 has no tanh instruction:
+//   q = 1 / (0.5 + exp2(k2 * s - 1)) = 2 / (1 + e^(2 s / cr)) = 1 - tanh(s / cr),   k2 = 2 log2(e) / cr
+// (v_fma, v_exp_f32, v_add, v_rcp_f32); then cr * tanh = fma(-cr, q, cr) and the derivative 1 - tanh^2 = q * (2 - q), without cancellation.  An exponential
+// that overflows gives q = 1 / inf = 0 (the score +cr, derivative 0), one that underflows q = 2 (-cr, 0): no inf * 0, no inf - inf, no NaN from finite scores.
+// Accuracy: v_exp_f32 and v_rcp_f32 are good to 1 ulp each and q <= 2, so tanh is within 2^-20 and a capped score within 2^-20 * softcap of the exact one.
+static __device__ __forceinline__ float softcap_q(float s, float k2) { return __builtin_amdgcn_rcpf(0.5f + fast_exp2(fmaf(s, k2, -1.f))); }
+static __device__ __forceinline__ float softcap_k2(float cr) { return 2.8853900817779268f / cr; }   // 2 log2(e) / cr, once per work item
 
 // Exchange between the two half-waves (lane l <-> lane l^32) with ONE v_permlane32_swap.
 // After `v_permlane32_swap a, b` (a: upper half <-> b: lower half) with a == b == x on entry:

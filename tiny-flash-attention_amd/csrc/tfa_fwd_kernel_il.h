@@ -80,6 +80,11 @@ constexpr int VF_IL_ALIBI = 256;         // ALiBi (tfa_fwd_alibi): S[i,j] = scal
                                          // scale in: the bias a * |c - ko|, a = -slope / scale, goes onto the RAW scores of every tile where apply_mask runs — in front of the
                                          // row maximum, so the lazy reference, its trigger and the LSE work on biased scores unchanged.  The hand-scheduled statement carries no
                                          // bias: every tile runs the compiler-scheduled bodies.  (The bit lies in the ping-pong kernel's VF_VPRE field: each kernel reads only its own flags)
+constexpr int VF_IL_SOFTCAP = 512;       // soft-capping (tfa_fwd_softcap): S[i,j] = c * tanh(scale * q_i . k_j / c) [- slope * |i + shift - j|], a form of the LOCAL instantiations like
+                                         // ALIBI and on its hook: every raw score s of every tile becomes cr * tanh(s / cr), cr = c / scale = KArgs::softcap_cr (softcap_q: five VALU
+                                         // per score), where apply_bias runs and in front of it; mask, row maximum, lazy reference, trigger and LSE work on the capped scores.
+                                         // With KArgs::slopes != nullptr the ALiBi bias follows the cap — one launch-uniform scalar branch per tile, so that a call without slopes
+                                         // does not pay the bias arithmetic and a second set of instantiations is not needed.  (Bit: the VF_VPRE field again)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -296,6 +301,9 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   constexpr bool ALIBI = (VF & VF_IL_ALIBI) != 0;
   static_assert(!ALIBI || LOCAL, "alibi: a form of the local instantiations");
   static_assert(!ALIBI || !(AB & ILAB_TRACE), "alibi: KArgs::slopes / slopes_bs share the bytes of trace / grid — no traced twin");
+  constexpr bool SOFTCAP = (VF & VF_IL_SOFTCAP) != 0;
+  static_assert(!SOFTCAP || (LOCAL && !ALIBI && !(AB & ILAB_TRACE)), "softcap: a form of the local instantiations; its slopes are a run-time choice (KArgs::slopes may be null)");
+  constexpr bool SMOD = ALIBI || SOFTCAP;            // the raw scores of every tile are modified in front of the mask: compiler-scheduled bodies only
   int kofs = 0, wlen = 0;
   if constexpr (LOCAL) {
     const int nk_s = VARLEN ? vsq.nk : p.Nk;
@@ -313,6 +321,16 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   if constexpr (ALIBI) {
     typedef __attribute__((address_space(4))) const float cfloat4;
     alibi_a = -((const cfloat4*)(uintptr_t)p.slopes)[(long long)b * p.slopes_bs + h] / p.scale;
+  }
+  // SOFTCAP: cr and k2 = 2 log2(e) / cr of softcap_q; the slopes are optional — launch-uniform, so `with_slopes` is a scalar condition
+  float cap_cr = 0.f, cap_k2 = 0.f;
+  bool with_slopes = false;
+  if constexpr (SOFTCAP) {
+    typedef __attribute__((address_space(4))) const float cfloat4;
+    cap_cr = p.softcap_cr;
+    cap_k2 = softcap_k2(cap_cr);
+    with_slopes = p.slopes != nullptr;
+    if (with_slopes) alibi_a = -((const cfloat4*)(uintptr_t)p.slopes)[(long long)b * p.slopes_bs + h] / p.scale;
   }
 
   const T* qbase = reinterpret_cast<const T*>(p.q) + (VARLEN ? (long long)vsq.q0 * p.qs_n : b * p.qs_b) + h * p.qs_h;
@@ -642,7 +660,15 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
         }
     };
     // ALIBI: the bias of tile t onto its raw scores (a sub and an fma with |.| per score); masked scores stay -inf
+    // SOFTCAP: the cap first — s <- cr * tanh(s / cr) on every raw score of the tile — and the bias only when the launch has slopes
     auto apply_bias = [&](int t, f32x16 (&s)[2]) {
+      if constexpr (SOFTCAP) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[tt][r] = fmaf(-cap_cr, softcap_q(s[tt][r], cap_k2), cap_cr);
+        if (!with_slopes) return;
+      }
       const float cf = (float)(my_pos + shift - p.win_right - key0_of(t) - 4 * hi);
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)

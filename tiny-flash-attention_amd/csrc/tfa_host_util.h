@@ -78,8 +78,17 @@ static inline void set_window(Args* a, int left, int right, int nq, int nk) {
 struct AlibiArg {
   const float* slopes;
   int64_t batch_stride;
+  // soft-capping (tfa_fwd_softcap / tfa_bwd_softcap and their varlen forms) rides on the same argument: capped = the call came through a _softcap entry point, which
+  // wants softcap > 0 and finite and takes slopes == nullptr as "no bias".  A host scalar, folded into the raw-score domain here (softcap_cr = softcap / scale)
+  bool capped = false;
+  float softcap = 0.f;
 };
-static inline int check_alibi(const AlibiArg& al, int H) {
+static inline int check_alibi(const AlibiArg& al, int H, float scale) {
+  if (al.capped) {
+    const float cr = al.softcap / scale;
+    if (!(al.softcap > 0.f) || !(al.softcap <= 3.0e38f) || !(cr > 0.f) || !(cr <= 3.0e38f)) return TFA_ERR_SCALE;   // (0, negative, NaN, inf; or the cap leaves fp32 over the scale)
+    if (!al.slopes) return TFA_OK;
+  }
   if (!al.slopes) return TFA_ERR_NULL;
   if ((uintptr_t)al.slopes & 3) return TFA_ERR_ALIGN;
   if (al.batch_stride != 0 && al.batch_stride != H) return TFA_ERR_STRIDE;
@@ -88,7 +97,8 @@ static inline int check_alibi(const AlibiArg& al, int H) {
 template <typename Args>
 static inline void set_alibi(Args* a, const AlibiArg& al) {
   a->slopes = al.slopes;
-  a->slopes_bs = (int)al.batch_stride;
+  a->slopes_bs = al.slopes ? (int)al.batch_stride : 0;
+  if (al.capped) a->softcap_cr = al.softcap / a->scale;
 }
 
 }  // namespace tfa

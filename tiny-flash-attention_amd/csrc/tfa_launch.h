@@ -131,8 +131,9 @@ static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, in
 }
 // the packed variable-length (VF_IL_VARLEN) and local (sliding-window, VF_IL_LOCAL) forms of variants 30 and 32: one translation unit per (dtype, width, form,
 // causal) — tfa_fwd_inst_varlen_<dtype>_<D>_c<0|1>.hip (VARLEN) and tfa_fwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN: the CAUSAL template
-// only, tfa_fwd_form_inst.inc) and tfa_fwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip (ALIBI: the ALiBi form of the local kernels)
-template <typename T, int D, bool VARLEN, bool LOCAL, bool CAUSAL, bool ALIBI = false>
+// only, tfa_fwd_form_inst.inc) and tfa_fwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip (ALIBI: the ALiBi form of the local kernels) and
+// tfa_fwd_inst_softcap_<dtype>_<D>_<fx|vl>.hip (SOFTCAP: the soft-capping form of the local kernels, slopes optional at run time)
+template <typename T, int D, bool VARLEN, bool LOCAL, bool CAUSAL, bool ALIBI = false, bool SOFTCAP = false>
 hipError_t launch_fwd_form_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
 #define TFA_FWD_FORM_UNITS(T, D)                                                                                         \
   template <> hipError_t launch_fwd_form_c<T, D, true, false, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
@@ -140,13 +141,17 @@ hipError_t launch_fwd_form_c(const KArgs& a, bool f32out, int variant, hipStream
   template <> hipError_t launch_fwd_form_c<T, D, false, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
   template <> hipError_t launch_fwd_form_c<T, D, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
   template <> hipError_t launch_fwd_form_c<T, D, false, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, true, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
+  template <> hipError_t launch_fwd_form_c<T, D, true, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
+  template <> hipError_t launch_fwd_form_c<T, D, false, true, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
+  template <> hipError_t launch_fwd_form_c<T, D, true, true, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
 TFA_FWD_FORM_UNITS(__bf16, 64) TFA_FWD_FORM_UNITS(__bf16, 128) TFA_FWD_FORM_UNITS(_Float16, 64) TFA_FWD_FORM_UNITS(_Float16, 128)
 #undef TFA_FWD_FORM_UNITS
-template <typename T, int D, bool VARLEN, bool LOCAL, bool ALIBI = false>
+template <typename T, int D, bool VARLEN, bool LOCAL, bool ALIBI = false, bool SOFTCAP = false>
 static inline hipError_t launch_fwd_form(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
   static_assert(LOCAL || !ALIBI, "the ALiBi kernels are a form of the local ones");
-  if constexpr (ALIBI) return launch_fwd_form_c<T, D, VARLEN, true, true, true>(a, f32out, variant, stream, geom, dry);
+  static_assert(!SOFTCAP || (LOCAL && !ALIBI), "the softcap kernels are a form of the local ones (slopes: KArgs::slopes, or null)");
+  if constexpr (SOFTCAP) return launch_fwd_form_c<T, D, VARLEN, true, true, false, true>(a, f32out, variant, stream, geom, dry);
+  else if constexpr (ALIBI) return launch_fwd_form_c<T, D, VARLEN, true, true, true>(a, f32out, variant, stream, geom, dry);
   else if constexpr (LOCAL) return launch_fwd_form_c<T, D, VARLEN, true, true>(a, f32out, variant, stream, geom, dry);   // (the window carries the right edge)
   else return causal ? launch_fwd_form_c<T, D, VARLEN, false, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_form_c<T, D, VARLEN, false, false>(a, f32out, variant, stream, geom, dry);
 }

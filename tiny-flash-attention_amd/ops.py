@@ -100,13 +100,40 @@ def _alibi(alibi_slopes, B, H, device, dtype, D, extra=()):
     return alibi_slopes, (H if alibi_slopes.dim() == 2 else 0)
 
 
+def _softcap(softcap, dtype, D, extra=()):
+    """FlashAttention-2's ``softcap`` checked as the C ABI needs it (include/tfa.h, soft-capping): a host number, 0.0 (the default) = no cap.  Returns 0.0 for
+    no cap — the caller then takes the code path it took before the argument existed — else the cap as a float.  Negative, NaN and infinite values and the
+    combinations the soft-capping kernels do not run raise ValueError naming the limit; ``extra``: (condition, message) pairs that rule a cap out."""
+    if isinstance(softcap, torch.Tensor):
+        raise TypeError("softcap must be a host number, not a tensor (nothing is read from the device)")
+    cap = float(softcap)
+    if cap == 0.0:
+        return 0.0
+    if not (cap > 0.0) or math.isinf(cap):
+        raise ValueError(f"softcap must be a finite number >= 0 (0 = no cap; got {softcap})")
+    if dtype == torch.float32:
+        raise ValueError("softcap: soft-capping runs on float16 / bfloat16 inputs only (no fp32 soft-capping path)")
+    if D > 128:
+        raise ValueError(f"softcap: soft-capping supports head dims up to 128 (got {D})")
+    for cond, msg in extra:
+        if cond:
+            raise ValueError(f"softcap: {msg}")
+    return cap
+
+
+def _slopes_arg(alibi):
+    """(pointer or None, batch stride) of checked slopes for a _softcap entry point, which takes NULL as "no bias"."""
+    return (None, 0) if alibi is None else (alibi[0].data_ptr(), alibi[1])
+
+
 def _alibi_window(win, is_causal):
     """The window an ALiBi entry point is given: a true window as it is, else (-1, -1) / (-1, 0) — the ALiBi kernels run every mask."""
     return win if win is not None else ((-1, 0) if is_causal else (-1, -1))
 
 
 def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd", out_f32=False,
-                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), alibi_slopes=None):
+                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), softcap=0.0,
+                   alibi_slopes=None):
     """General forward: q (B,H,Nq,D) / k,v (B,Hk,Nk,D) for ``layout='bhnd'`` or
     (B,N,H,D) for ``layout='bnhd'``; any batch/head/row strides, unit stride along D.
     Returns ``(out, lse)``; ``out`` has q's shape (fp32 when ``out_f32``), ``lse`` is (B,H,Nq) fp32.
@@ -119,7 +146,10 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     i + (Nk - Nq) - left <= j <= i + (Nk - Nq) + right, -1 = unbounded, ``is_causal`` forces right = 0 (tfa_fwd_local).
     ``alibi_slopes``: FlashAttention-2's ALiBi — float32 (H,) or (B, H) on q's device; ``-slope[b, h] * |i + (Nk - Nq) - j|`` is added to the scaled
     scores before the mask and the softmax, and the returned LSE includes it (tfa_fwd_alibi; the slopes are read by the kernels only; with any mask
-    or window; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored)."""
+    or window; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored).
+    ``softcap``: FlashAttention-2's tanh logit capping, a host float, 0.0 = none: the scaled scores x become ``softcap * tanh(x / softcap)`` FIRST, then the
+    ALiBi bias is added, then the mask applies; the LSE is that of the capped scores (tfa_fwd_softcap; tanh within 2^-20; float16 / bfloat16, head dims up to
+    128, any mask or window, with or without slopes; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored; negative / NaN / inf: ValueError)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -149,6 +179,8 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
         win, is_causal = None, True
     alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D,
                    extra=((exact_max, "no exact_max form of the ALiBi kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
+    cap = _softcap(softcap, q.dtype, D,
+                   extra=((exact_max, "no exact_max form of the soft-capping kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
 
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
@@ -182,10 +214,13 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     # tfa_fwd_splitkv's merge writes a dense (B,H,Nq,D) result: gate on the exact strides it checks (is_contiguous() ignores the
     # strides of size-1 dims, and Nq == 1 is the very shape auto-split targets)
     dense_out = (out.stride(3) == 1 and out.stride(2) == D and out.stride(1) == Nq * D and out.stride(0) == H * Nq * D)
-    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None) else 1
+    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None and not cap) else 1
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if alibi is not None:
+        if cap:
+            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
+            _lib.check(L.tfa_fwd_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
+        elif alibi is not None:
             aw = _alibi_window(win, is_causal)
             _lib.check(L.tfa_fwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
         elif win is not None:
@@ -305,7 +340,7 @@ def make_bwd_params(q, k, v, out, lse, dout, dq, dk, dv, delta, is_causal, softm
 
 
 def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None, window_size=(-1, -1),
-                   alibi_slopes=None):
+                   softcap=0.0, alibi_slopes=None):
     """Backward of ``flash_attn_fwd``: returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``).
     ``out`` and ``lse`` are the forward's results for the same q, k, v; ``dout`` is the upstream gradient
     (shape/dtype of ``out``).  The reference has no backward — it only saves the LSE for one
@@ -313,7 +348,8 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
     ``workspace``: None (default: the O(N)-memory 7-GEMM form), True (allocate tfa_bwd_workspace_bytes of scratch for this call)
     or a caller-owned uint8 / any-dtype CUDA tensor of at least that many bytes: tfa_bwd then keeps dS and executes 5 GEMMs.
     ``window_size``: the forward's sliding window (tfa_bwd_local; no workspace form).
-    ``alibi_slopes``: the forward's ALiBi slopes (tfa_bwd_alibi; no workspace form); they receive no gradient."""
+    ``alibi_slopes``: the forward's ALiBi slopes (tfa_bwd_alibi; no workspace form); they receive no gradient.
+    ``softcap``: the forward's soft cap (tfa_bwd_softcap; no workspace form): dS is multiplied by 1 - tanh^2 on its way to dq and dk; no gradient for it."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (dout, "dout")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -338,6 +374,7 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         win, is_causal = None, True
     alibi = _alibi(alibi_slopes, q.shape[0], lse_shape[1], q.device, q.dtype, D,
                    extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
+    cap = _softcap(softcap, q.dtype, D, extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.empty(q.shape, dtype=gdt, device=q.device)
@@ -355,7 +392,10 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         p.workspace_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if alibi is not None:
+        if cap:
+            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
+            _lib.check(_lib.lib().tfa_bwd_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
+        elif alibi is not None:
             aw = _alibi_window(win, is_causal)
             _lib.check(_lib.lib().tfa_bwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
         elif win is not None:
@@ -426,10 +466,10 @@ class _FlashAttnBNHD(torch.autograd.Function):
     """autograd glue for ``flash_attn_func``: forward = tfa_fwd, backward = tfa_bwd, both on (B,N,H,D) views."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1), alibi_slopes=None):
-        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size, alibi_slopes=alibi_slopes)
+    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
+        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
         ctx.save_for_backward(q, k, v, out, lse, alibi_slopes)   # (the slopes, or None: they get no gradient)
-        ctx.causal, ctx.scale, ctx.window = causal, softmax_scale, window_size
+        ctx.causal, ctx.scale, ctx.window, ctx.softcap = causal, softmax_scale, window_size, softcap
         return out
 
     @staticmethod
@@ -437,21 +477,33 @@ class _FlashAttnBNHD(torch.autograd.Function):
         q, k, v, out, lse, slopes = ctx.saved_tensors
         if dout.stride(3) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, alibi_slopes=slopes)
-        return dq, dk, dv, None, None, None, None
+        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, alibi_slopes=slopes,
+                                    softcap=ctx.softcap)
+        return dq, dk, dv, None, None, None, None, None   # (causal, scale, window, softcap, slopes: no gradient)
 
 
-def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1), alibi_slopes=None):
+def _positional_slopes(extra, alibi_slopes, name):
+    """``alibi_slopes`` given as the one positional argument behind ``window_size`` (where it stood before ``softcap`` existed) or as a keyword."""
+    if len(extra) > 1 or (extra and alibi_slopes is not None):
+        raise TypeError(f"{name}: at most one positional argument behind window_size (alibi_slopes), and not together with the keyword")
+    return extra[0] if extra else alibi_slopes
+
+
+def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1), *extra, softcap=0.0, alibi_slopes=None):
     """(B,N,H,D)-layout entry with the signature the reference's scripts use for comparison
     (flash_attention_cutlass/test.py:71-76, flash_attention_py/main_torch_only.py:304);
     supports GQA/MQA (fewer K/V heads).  Differentiable (like the official function the reference
     compares against): when an input requires grad the backward runs tfa_bwd.  ``window_size=(left, right)``: FlashAttention-2's local
     (sliding-window) attention, -1 = unbounded, ``causal`` forces right = 0 (tfa_fwd_local / tfa_bwd_local).  ``alibi_slopes``: FlashAttention-2's
-    ALiBi, float32 (H,) or (B, H): ``-slope * |i + (Nk - Nq) - j|`` added to the scaled scores (tfa_fwd_alibi / tfa_bwd_alibi); no gradient for them."""
+    ALiBi, float32 (H,) or (B, H): ``-slope * |i + (Nk - Nq) - j|`` added to the scaled scores (tfa_fwd_alibi / tfa_bwd_alibi); no gradient for them.
+    ``softcap``: FlashAttention-2's tanh logit capping (Gemma-2 style), a host float, 0.0 = none: scaled scores x become ``softcap * tanh(x / softcap)`` before
+    the ALiBi bias and the mask (cap, then bias, then mask); differentiable through the cap (tfa_fwd_softcap / tfa_bwd_softcap), no gradient for the value itself.
+    ``softcap`` is keyword-only; ``alibi_slopes`` stays the last parameter and may still be passed as the positional argument behind ``window_size``."""
+    alibi_slopes = _positional_slopes(extra, alibi_slopes, "flash_attn_func")
     window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size, alibi_slopes)
-    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size, alibi_slopes=alibi_slopes)
+        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size, softcap, alibi_slopes)
+    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
     return out
 
 
@@ -496,13 +548,13 @@ def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
 
 
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1), alibi_slopes=None):
+                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
     """Packed variable-length forward (tfa_fwd_varlen, include/tfa.h): q (total_q, H, D), k / v (total_k, Hk, D), sequence b is rows
     [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v (device int32, B + 1 entries, never read on the host).
     Causal masking per sequence, bottom-right aligned.  Returns ``(out, lse)``: ``out`` shaped like q (fp32 when ``out_f32``), ``lse`` fp32 (H, total_q).
     Rows outside every sequence are not written (a caller-provided ``out`` keeps them).  ``window_size``: FlashAttention-2's sliding window per
     sequence (tfa_fwd_varlen_local).  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H) with B the number of sequences; the distance is taken per sequence
-    (tfa_fwd_varlen_alibi)."""
+    (tfa_fwd_varlen_alibi).  ``softcap``: tanh logit capping of the scaled scores before the bias and the mask, 0.0 = none (tfa_fwd_varlen_softcap)."""
     _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     B = cu_seqlens_q.numel() - 1
     total_q, H, D = q.shape
@@ -513,6 +565,7 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     if win == (-1, 0):
         win, is_causal = None, True
     alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
+    cap = _softcap(softcap, q.dtype, D)
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
     else:
@@ -538,7 +591,10 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if alibi is not None:
+        if cap:
+            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
+            _lib.check(_lib.lib().tfa_fwd_varlen_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
+        elif alibi is not None:
             aw = _alibi_window(win, is_causal)
             _lib.check(_lib.lib().tfa_fwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
         elif win is not None:
@@ -549,10 +605,10 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
 
 
 def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          grad_f32=False, window_size=(-1, -1), alibi_slopes=None):
+                          grad_f32=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
     """Backward of ``flash_attn_varlen_fwd`` (tfa_bwd_varlen): returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``); for GQA dk / dv
     are summed over the query heads of each K/V head within each sequence.  Rows outside every sequence get zero gradients: the kernels never write
-    them, so the three results are allocated zeroed (one memset of dq, dk and dv per call)."""
+    them, so the three results are allocated zeroed (one memset of dq, dk and dv per call).  ``window_size``, ``alibi_slopes``, ``softcap``: the forward's."""
     _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, extra=((out, "out"), (dout, "dout")))
     if out.shape != q.shape or dout.shape != q.shape or out.dtype != q.dtype or dout.dtype != q.dtype:
         raise RuntimeError("out and dout must be shaped like q, in q's dtype")
@@ -567,6 +623,7 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     if win == (-1, 0):
         win, is_causal = None, True
     alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
+    cap = _softcap(softcap, q.dtype, D)
     lse = lse.contiguous()
     gdt = torch.float32 if grad_f32 else q.dtype
     dq = torch.zeros(q.shape, dtype=gdt, device=q.device)
@@ -590,7 +647,10 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     p.grad_dtype = _lib.TFA_F32 if grad_f32 else _DT[q.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if alibi is not None:
+        if cap:
+            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
+            _lib.check(_lib.lib().tfa_bwd_varlen_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
+        elif alibi is not None:
             aw = _alibi_window(win, is_causal)
             _lib.check(_lib.lib().tfa_bwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
         elif win is not None:
@@ -604,35 +664,40 @@ class _FlashAttnVarlen(torch.autograd.Function):
     """autograd glue for ``flash_attn_varlen_func``: forward = tfa_fwd_varlen, backward = tfa_bwd_varlen."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=(-1, -1), alibi_slopes=None):
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=(-1, -1), softcap=0.0,
+                alibi_slopes=None):
         out, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size=window_size,
-                                         alibi_slopes=alibi_slopes)
+                                         alibi_slopes=alibi_slopes, softcap=softcap)
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, alibi_slopes)   # (the slopes, or None: they get no gradient)
-        ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size)
+        ctx.args = (max_seqlen_q, max_seqlen_k, causal, softmax_scale, window_size, softcap)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse, cu_q, cu_k, slopes = ctx.saved_tensors
-        max_q, max_k, causal, scale, window = ctx.args
+        max_q, max_k, causal, scale, window, softcap = ctx.args
         if dout.stride(2) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window, alibi_slopes=slopes)
-        return dq, dk, dv, None, None, None, None, None, None, None, None
+        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window, alibi_slopes=slopes,
+                                           softcap=softcap)
+        return dq, dk, dv, None, None, None, None, None, None, None, None, None
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
-                           window_size=(-1, -1), alibi_slopes=None):
+                           window_size=(-1, -1), *extra, softcap=0.0, alibi_slopes=None):
     """Packed variable-length attention with FlashAttention-2's positional signature (flash_attn_varlen_func): q (total_q, H, D), k / v
     (total_k, Hk, D), cu_seqlens_q / _k device int32 (B + 1), max_seqlen_q / _k host integers.  Differentiable: when an input requires grad the
     backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0).  ``window_size=(left, right)``: FlashAttention-2's sliding
-    window per sequence, -1 = unbounded, ``causal`` forces right = 0.  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H), B = the number of sequences."""
+    window per sequence, -1 = unbounded, ``causal`` forces right = 0.  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H), B = the number of sequences.
+    ``softcap``: tanh logit capping, a host float, 0.0 = none: cap on the scaled scores, then the bias, then the mask (tfa_fwd_varlen_softcap / tfa_bwd_varlen_softcap).
+    ``softcap`` is keyword-only; ``alibi_slopes`` stays the last parameter and may still be passed as the positional argument behind ``window_size``."""
+    alibi_slopes = _positional_slopes(extra, alibi_slopes, "flash_attn_varlen_func")
     if dropout_p != 0.0:
         raise NotImplementedError("flash_attn_varlen_func: dropout is not supported (dropout_p must be 0)")
     window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale, window_size,
-                                      alibi_slopes)
+                                      softcap, alibi_slopes)
     out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False,
-                                   window_size=window_size, alibi_slopes=alibi_slopes)
+                                   window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
     return out
