@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -563,6 +563,84 @@ int tfa_bwd_varlen_softcap(const tfa_varlen_bwd_params* p, float softcap, const 
                            int window_right, void* stream);
 int tfa_bwd_varlen_softcap_plan(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
                                 int window_right);
+
+/* ---- attention over a K/V cache (FlashAttention-2's flash_attn_with_kvcache: cache_seqlens, paged KV, in-place append) ------------------------
+ * The inference step of a serving loop: B sequences, each with its own number of cached keys, the lengths in DEVICE memory.
+ *   cache_seqlens: int32, B entries, never read on the host — no copy, no synchronisation; a call can be captured in a graph and replayed after the
+ *     lengths were advanced in place.  Every work item reads its sequence's length itself (a scalar load): len_b = cache_seqlens[b] + n_new, clamped
+ *     into [0, capacity].  Sequence b attends keys [0, len_b); a sequence with len_b = 0 gets out = 0, lse = +inf.
+ *   contiguous cache (block_table NULL): k_cache / v_cache are (B, capacity, Hk, D) by strides {batch, head, row} in elements, unit stride along D.
+ *   paged cache (block_table != NULL): k_cache / v_cache are (num_pages, page_size, Hk, D) by strides {page, head, row}; key j of sequence b is row
+ *     j % page_size of page block_table[b * block_table_stride + j / page_size]; capacity = max_blocks * page_size (the caller states it); page_size is a
+ *     positive multiple of 64, so a 64-key tile never straddles pages.  Entries are clamped into [0, num_pages) for reading; the append drops a row whose
+ *     entry lies outside.
+ *   is_causal: bottom-right aligned per sequence — key j is visible to query row i iff j <= i + (len_b - Nq); rows that see no key (len_b < Nq): out = 0,
+ *     lse = +inf.
+ *   k_new / v_new (both or neither; n_new rows per sequence, (B, n_new, Hk, D) by strides {batch, head, row}): copied into the cache at key positions
+ *     cache_seqlens[b] + t first (a launch of its own on `stream`, 16-byte loads and stores), then attended.  A row at or beyond the capacity is not
+ *     written — and not attended, as the length is clamped.  Nothing is stored outside the cache tensors.  cache_seqlens itself is not modified: the
+ *     caller advances it, as in FlashAttention-2.
+ * Whatever the cache holds behind len_b — the tail of the last page, stale keys of an earlier request, NaN — is never read into a result: every K/V buffer
+ * descriptor ends at the last valid key, so those rows arrive as zeros (a masked P = 0 times a non-finite V would be NaN).
+ * Kernel: the KV-cache form of the LDS-DMA kernel behind tfa_fwd_splitkv (variant 17; exact running max: TFA_RULE_EXACT_MAX), 64 or 128 wide.  The key range
+ * of EVERY sequence is cut into `splits` chunks from its own length on the device — chunk_b = round_up(ceil(len_b / splits), 64) — so ragged batches stay
+ * balanced; chunks behind a sequence's end give empty partials, which tfa_merge skips.  splits == 1 writes out / lse directly (any out strides, no workspace);
+ * splits >= 2 writes fp32 partials to `workspace` and tfa_merge writes out, which must then be contiguous (B, H, Nq, D).  lse: (B, H, Nq) fp32 or NULL.
+ * GQA / MQA decode (Nq == 1, Hk < H, H / Hk <= 128): the H / Hk query heads of a K/V head run as rows of one problem, K and V stream once per K/V head.
+ * Nq > 1 runs unpacked: K and V are streamed once per QUERY head (position-aware packing for this form is future work).
+ * Everything is enqueued on `stream` alone — append, attention, merge, in that order; no side streams, no events: a captured step is a straight line.
+ * Refused, nothing launched: a NULL params / q / out / k_cache / v_cache / cache_seqlens, one of k_new / v_new without the other or with n_new <= 0
+ * (TFA_ERR_NULL / TFA_ERR_SHAPE); dtype other than TFA_F16 / TFA_BF16 (TFA_ERR_DTYPE); D not a multiple of 8 in [8, 128] (TFA_ERR_HEAD_DIM); B, H, Hk, Nq,
+ * capacity <= 0, H % Hk != 0, n_new < 0, splits < 1 (TFA_ERR_SHAPE); paged: page_size not a positive multiple of 64, capacity not a multiple of page_size,
+ * num_pages <= 0 (TFA_ERR_SHAPE), block_table_stride < capacity / page_size (TFA_ERR_STRIDE); strides negative, not 16-byte aligned or overlapping rows, a
+ * contiguous (b, h) slice — or a page — that does not fit one 2 GiB descriptor, out not contiguous (B, H, Nq, D) with splits >= 2 (TFA_ERR_STRIDE); base
+ * pointers not 16-byte aligned, block_table / cache_seqlens / lse not 4-byte aligned, a misaligned workspace (TFA_ERR_ALIGN); a NULL workspace with
+ * splits >= 2 (TFA_ERR_NULL); softmax_scale not finite or <= 0 (TFA_ERR_SCALE).
+ * Out of scope: rotary embedding, cache_batch_idx, cache_leftpad, windows, softcap, ALiBi, head dims above 128, fp32 inputs, TFA_FWD_EXACT_MAX, a backward.
+ * Tolerances: the header's "which tolerance each path guarantees".  Measured: profiles/kvcache_bench.txt (tools/bench_kvcache.py), quoted in README.md. */
+typedef struct tfa_kvcache_params {
+  const void* q;                 /* (B, H, Nq, D) by q_stride */
+  void* out;                     /* (B, H, Nq, D) by o_stride, input dtype */
+  float* lse;                    /* (B, H, Nq) fp32 contiguous, or NULL to skip */
+  void* k_cache;                 /* written only by the append */
+  void* v_cache;
+  const int32_t* block_table;    /* device (B, max_blocks) int32, or NULL: contiguous cache */
+  const int32_t* cache_seqlens;  /* device, B entries */
+  const void* k_new;             /* (B, n_new, Hk, D), or NULL */
+  const void* v_new;
+  int32_t B, H, Hk, Nq, D;
+  int32_t capacity;              /* keys a sequence can hold: Nk_max, or max_blocks * page_size */
+  int32_t n_new;                 /* rows of k_new / v_new per sequence; 0 without them */
+  int32_t page_size;             /* paged: keys per page, a positive multiple of 64; contiguous: ignored */
+  int32_t num_pages;             /* paged: pages in k_cache / v_cache; contiguous: ignored */
+  int32_t reserved_;             /* must be 0 */
+  int64_t q_stride[3];           /* batch, head, row (elements) */
+  int64_t o_stride[3];
+  int64_t k_stride[3];           /* batch (contiguous) or page (paged), head, row */
+  int64_t v_stride[3];
+  int64_t knew_stride[3];        /* batch, head, row */
+  int64_t vnew_stride[3];
+  int64_t block_table_stride;    /* elements between the rows of block_table */
+  float softmax_scale;
+  int32_t is_causal;
+  int32_t dtype;                 /* TFA_F16 or TFA_BF16: q, caches, k_new / v_new, out */
+  int32_t reserved2_;            /* must be 0 */
+} tfa_kvcache_params;
+
+/* Append (when k_new / v_new are given), attend, merge — on `stream`, asynchronous, never allocates, never reads device memory on the host.
+ * workspace: tfa_fwd_kvcache_workspace(p, splits) floats, 16-byte aligned; may be NULL when that is 0 (splits == 1). */
+int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream);
+/* Floats of workspace the call uses: 0 for one chunk, else chunks * B * H * Nq * (D + 1) — chunks = min(splits, ceil(capacity / 64)); negative = TFA_ERR_*. */
+long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits);
+/* Validate *p and `splits` without launching (no GPU needed); on success optionally reports the attention launch's geometry. */
+int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes);
+/* The split count to use for *p, from host-known sizes only: the capacity stands in for the lengths, the CU count comes from the library.  1 when the
+ * grid already fills the chip (B * heads * ceil(rows / 128) workgroups on more than half of the CUs — heads = Hk and rows = H / Hk for packed GQA decode),
+ * the capacity is below 4096 keys, or causal with Nq > capacity / 4; else one chunk per idle CU (two per CU from a quarter of the CUs on), at most
+ * capacity / 1024 and at most 32: tfa_fwd_suggest_splits' rule. */
+int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p);
+/* The append alone (k_new / v_new required): q, out, lse, Nq, H, softmax_scale and is_causal are not looked at. */
+int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream);
 
 #ifdef __cplusplus
 }

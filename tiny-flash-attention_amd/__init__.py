@@ -13,6 +13,7 @@ Reference-named entry points (same names, argument order and return shapes):
 
 FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen_func`` with ``causal``, ``window_size``, ``alibi_slopes`` and ``softcap``
 (GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.
+Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append).
 """
 from .ops import (  # noqa: F401
     flash_attention_v2_cutlass,
@@ -29,6 +30,7 @@ from .ops import (  # noqa: F401
     flash_attn_varlen_func,
     flash_attn_varlen_fwd,
     flash_attn_varlen_bwd,
+    flash_attn_with_kvcache,
 )
 from . import _lib  # noqa: F401
 
@@ -47,4 +49,5 @@ __all__ = [
     "flash_attn_varlen_func",
     "flash_attn_varlen_fwd",
     "flash_attn_varlen_bwd",
+    "flash_attn_with_kvcache",
 ]

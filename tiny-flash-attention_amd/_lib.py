@@ -80,6 +80,11 @@ SYMBOLS = (
     "tfa_bwd_softcap_plan",
     "tfa_bwd_varlen_softcap",
     "tfa_bwd_varlen_softcap_plan",
+    "tfa_fwd_kvcache",
+    "tfa_fwd_kvcache_workspace",
+    "tfa_fwd_kvcache_plan",
+    "tfa_fwd_kvcache_suggest_splits",
+    "tfa_kvcache_append",
 )
 
 
@@ -226,6 +231,43 @@ class TfaVarlenBwdParams(C.Structure):
     ]
 
 
+class TfaKvcacheParams(C.Structure):
+    """struct tfa_kvcache_params (include/tfa.h): attention over a K/V cache with device-side lengths, contiguous or paged."""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("out", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("k_cache", C.c_void_p),
+        ("v_cache", C.c_void_p),
+        ("block_table", C.c_void_p),
+        ("cache_seqlens", C.c_void_p),
+        ("k_new", C.c_void_p),
+        ("v_new", C.c_void_p),
+        ("B", C.c_int32),
+        ("H", C.c_int32),
+        ("Hk", C.c_int32),
+        ("Nq", C.c_int32),
+        ("D", C.c_int32),
+        ("capacity", C.c_int32),
+        ("n_new", C.c_int32),
+        ("page_size", C.c_int32),
+        ("num_pages", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("q_stride", C.c_int64 * 3),
+        ("o_stride", C.c_int64 * 3),
+        ("k_stride", C.c_int64 * 3),
+        ("v_stride", C.c_int64 * 3),
+        ("knew_stride", C.c_int64 * 3),
+        ("vnew_stride", C.c_int64 * 3),
+        ("block_table_stride", C.c_int64),
+        ("softmax_scale", C.c_float),
+        ("is_causal", C.c_int32),
+        ("dtype", C.c_int32),
+        ("reserved2_", C.c_int32),
+    ]
+
+
 class TfaError(RuntimeError):
     def __init__(self, status, text):
         super().__init__(f"tfa status {status}: {text}")
@@ -341,6 +383,18 @@ def lib():
                        ("tfa_bwd_varlen_softcap", [PVB] + SC + [C.c_void_p]), ("tfa_bwd_varlen_softcap_plan", [PVB] + SC)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
+    # attention over a K/V cache (tfa_kvcache_params)
+    PK = C.POINTER(TfaKvcacheParams)
+    L.tfa_fwd_kvcache.restype = C.c_int
+    L.tfa_fwd_kvcache.argtypes = [PK, C.c_int, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_workspace.argtypes = [PK, C.c_int]
+    L.tfa_fwd_kvcache_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_plan.argtypes = [PK, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_suggest_splits.argtypes = [PK]
+    L.tfa_kvcache_append.restype = C.c_int
+    L.tfa_kvcache_append.argtypes = [PK, C.c_void_p]
     _lib = L
     return L
 

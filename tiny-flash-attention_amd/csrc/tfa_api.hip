@@ -10,6 +10,7 @@
 
 #include "tfa.h"
 #include "tfa_launch.h"
+#include "tfa_kvcache.h"
 
 namespace tfa {
 // fp32 tensors (the reference's fp32 fixtures: a correctness path on v_mfma_f32_32x32x2_f32): tfa_fwd_f32.hip
@@ -699,6 +700,176 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   // (tools/bench_decode_wide.py, profiles/r03_decode_wide.txt)
   if (!one_descriptor(p_in) && s > 4) s = 4;            // (the caller's strides, as tfa_fwd_splitkv tests them — not the packed ones)
   return s >= 2 ? (int)s : 1;
+}
+
+// ---- attention over a K/V cache (tfa.h: tfa_fwd_kvcache) ----------------------------------------------------------------------------------
+// What the append and the attention both need of *p: the cache side.  Nothing here (or anywhere on this path) reads device memory.
+static int kvcache_check_cache(const tfa_kvcache_params* p) {
+  if (!p) return TFA_ERR_NULL;
+  if (!p->k_cache || !p->v_cache || !p->cache_seqlens) return TFA_ERR_NULL;
+  if ((p->k_new == nullptr) != (p->v_new == nullptr)) return TFA_ERR_NULL;
+  if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
+  if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;
+  if (p->B <= 0 || p->Hk <= 0 || p->capacity <= 0 || p->n_new < 0 || p->reserved_ != 0 || p->reserved2_ != 0) return TFA_ERR_SHAPE;
+  if (p->k_new ? p->n_new <= 0 : p->n_new != 0) return TFA_ERR_SHAPE;
+  const bool paged = p->block_table != nullptr;
+  if (paged) {
+    if (p->page_size <= 0 || (p->page_size % 64) != 0 || (p->capacity % p->page_size) != 0 || p->num_pages <= 0) return TFA_ERR_SHAPE;
+    if (p->block_table_stride < p->capacity / p->page_size) return TFA_ERR_STRIDE;
+  }
+  const int64_t span = paged ? p->page_size : p->capacity;       // rows one buffer descriptor has to reach: a page, or a sequence's slice
+  const int64_t* st[4] = {p->k_stride, p->v_stride, p->knew_stride, p->vnew_stride};
+  for (int t = 0; t < (p->k_new ? 4 : 2); ++t) {
+    for (int i = 0; i < 3; ++i)
+      if (st[t][i] < 0 || (st[t][i] * 2) % 16 != 0) return TFA_ERR_STRIDE;
+    if (st[t][2] < p->D) return TFA_ERR_STRIDE;
+    if (t < 2 && ((span + 512) * st[t][2] + p->D) * 2 >= (int64_t)0x7fffffff) return TFA_ERR_STRIDE;   // (one_descriptor's bound)
+  }
+  if (((uintptr_t)p->k_cache | (uintptr_t)p->v_cache | (uintptr_t)p->k_new | (uintptr_t)p->v_new) & 15) return TFA_ERR_ALIGN;
+  if (((uintptr_t)p->cache_seqlens | (uintptr_t)p->block_table) & 3) return TFA_ERR_ALIGN;
+  return TFA_OK;
+}
+
+// the chunk count a call runs: every chunk of a full sequence holds at least one 64-key tile
+static int kvcache_chunks(const tfa_kvcache_params* p, int splits) {
+  const int tiles = (p->capacity + 63) / 64;
+  return splits < tiles ? splits : tiles;
+}
+
+// GQA / MQA decode runs packed (pack_gqa_rows: one query row per head, the H / Hk heads of a K/V head as rows of one non-causal problem)
+static bool kvcache_packs(const tfa_kvcache_params* p) { return p->Nq == 1 && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128; }
+
+static int kvcache_run(const tfa_kvcache_params* p, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+  int st = kvcache_check_cache(p);
+  if (st != TFA_OK) return st;
+  if (!p->q || !p->out) return TFA_ERR_NULL;
+  if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
+  const bool paged = p->block_table != nullptr;
+  const int ns = kvcache_chunks(p, splits);
+  const long long rows = (long long)p->B * p->H * p->Nq;
+  tfa_fwd_params f;
+  memset(&f, 0, sizeof(f));
+  f.q = p->q; f.k = p->k_cache; f.v = p->v_cache; f.out = p->out; f.lse = p->lse;
+  f.B = p->B; f.H = p->H; f.Hk = p->Hk; f.Nq = p->Nq; f.D = p->D;
+  f.Nk = paged ? p->page_size : p->capacity;              // the rows one K/V descriptor spans (validate: slice_bytes)
+  for (int i = 0; i < 3; ++i) { f.q_stride[i] = p->q_stride[i]; f.k_stride[i] = p->k_stride[i]; f.v_stride[i] = p->v_stride[i]; f.o_stride[i] = p->o_stride[i]; }
+  f.softmax_scale = p->softmax_scale;
+  f.is_causal = p->is_causal ? 1 : 0;
+  f.dtype = f.out_dtype = p->dtype;
+  float* ws_o = workspace;
+  float* ws_l = workspace ? workspace + (long long)ns * rows * p->D : nullptr;
+  if (ns > 1) {
+    // the merge writes contiguous rows: out must be a contiguous (B,H,Nq,D) tensor; the partial pass writes fp32 O and LSE of every chunk into the workspace
+    if (p->o_stride[2] != p->D || p->o_stride[1] != (int64_t)p->Nq * p->D || p->o_stride[0] != (int64_t)p->H * p->Nq * p->D) return TFA_ERR_STRIDE;
+    if (((uintptr_t)p->out & 15)) return TFA_ERR_ALIGN;
+    if (p->lse && ((uintptr_t)p->lse & 3)) return TFA_ERR_ALIGN;
+    if (!dry) {
+      if (!workspace) return TFA_ERR_NULL;
+      if ((uintptr_t)workspace & 15) return TFA_ERR_ALIGN;
+    }
+    f.out = dry ? (void*)p->out : (void*)ws_o;            // (a plan has no workspace: any aligned address stands in)
+    f.lse = dry ? nullptr : ws_l;
+    f.out_dtype = TFA_F32;
+  }
+  tfa::KArgs a;
+  {
+    tfa_fwd_params fp;
+    st = TFA_ERR_SHAPE;
+    if (kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
+      st = validate(&fp, &a, tfa::kSplitVariant);
+      if (st == TFA_OK) f = fp;
+    }
+    if (st != TFA_OK) st = validate(&f, &a, tfa::kSplitVariant);
+  }
+  if (st != TFA_OK) return st;
+  tfa::KvcArgs ka;
+  memset(&ka, 0, sizeof(ka));
+  static_cast<tfa::KArgs&>(ka) = a;
+  ka.nsplit = ns;
+  ka.chunk = 0;                                            // (formed per sequence on the device)
+  ka.o_part_stride = ns > 1 ? rows * p->D : 0;
+  ka.lse_part_stride = ns > 1 ? rows : 0;
+  ka.trace = nullptr;
+  ka.seqlens = p->cache_seqlens;
+  ka.block_table = p->block_table;
+  ka.bt_stride = p->block_table_stride;
+  ka.n_new = p->n_new;
+  ka.capacity = p->capacity;
+  ka.num_pages = paged ? p->num_pages : 1;
+  ka.nq_pos = p->Nq;
+  ka.tpp = paged ? p->page_size / 64 : 1;
+  ka.fd_nsplit = tfa::fastdiv_of((unsigned)ns);
+  ka.fd_tpp = tfa::fastdiv_of((unsigned)ka.tpp);
+  ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * 4 >= (768ll << 20)) ? 1 : 0;
+  if ((long long)ka.nbh * ka.nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  const bool causal = f.is_causal != 0;                    // (the packed one-row problem is non-causal)
+  const bool nt = ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;   // tfa_fwd_splitkv's rule for the non-temporal hint
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!dry && p->k_new) {                                  // this step's keys first, on the same stream
+    st = tfa_kvcache_append(p, stream);
+    if (st != TFA_OK) return st;
+  }
+  const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
+    return tfa::launch_kvc<typename decltype(k)::T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
+  });
+  if (e != hipSuccess) return (int)e;
+  if (dry || ns == 1) return TFA_OK;
+  return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
+}
+
+int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, splits, workspace, stream, nullptr, false); }
+
+int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = kvcache_run(p, splits, nullptr, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+
+long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) {
+  const int st = kvcache_run(p, splits, nullptr, nullptr, nullptr, true);
+  if (st != TFA_OK) return st;
+  const int ns = kvcache_chunks(p, splits);
+  return ns > 1 ? (long long)ns * p->B * p->H * p->Nq * (p->D + 1) : 0;
+}
+
+int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) {
+  if (!p || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->capacity <= 0 || p->H % p->Hk != 0) return 1;
+  // tfa_fwd_suggest_splits' rule on host-known sizes: the capacity stands in for the lengths (which live on the device)
+  const bool packed = kvcache_packs(p);
+  const long long blocks = (long long)p->B * (packed ? p->Hk : p->H) * (((packed ? p->H / p->Hk : p->Nq) + 127) / 128);
+  const int cus = num_cus();
+  if (blocks * 2 > cus || p->capacity < 4096) return 1;
+  if (p->is_causal && !packed && (long long)p->Nq * 4 > p->capacity) return 1;
+  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
+  if (s > p->capacity / 1024) s = p->capacity / 1024;
+  if (s > 32) s = 32;
+  return s >= 2 ? (int)s : 1;
+}
+
+int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream) {
+  const int st = kvcache_check_cache(p);
+  if (st != TFA_OK) return st;
+  if (!p->k_new) return TFA_ERR_NULL;
+  tfa::AppendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.k_new = p->k_new; a.v_new = p->v_new; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
+  a.seqlens = p->cache_seqlens;
+  a.block_table = p->block_table;
+  a.bt_stride = p->block_table_stride;
+  a.ks_b = p->k_stride[0]; a.ks_h = p->k_stride[1]; a.ks_n = p->k_stride[2];
+  a.vs_b = p->v_stride[0]; a.vs_h = p->v_stride[1]; a.vs_n = p->v_stride[2];
+  a.kn_b = p->knew_stride[0]; a.kn_h = p->knew_stride[1]; a.kn_n = p->knew_stride[2];
+  a.vn_b = p->vnew_stride[0]; a.vn_h = p->vnew_stride[1]; a.vn_n = p->vnew_stride[2];
+  a.n_new = p->n_new; a.Hk = p->Hk; a.cpr = p->D / 8;
+  a.total = (long long)p->B * p->n_new * p->Hk * a.cpr;
+  a.capacity = p->capacity;
+  a.page_size = p->block_table ? p->page_size : 1;
+  a.num_pages = p->block_table ? p->num_pages : 1;
+  return (int)tfa::launch_kvcache_append(a, reinterpret_cast<hipStream_t>(stream));
 }
 
 int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return route({nullptr, p, nullptr}, stream); }

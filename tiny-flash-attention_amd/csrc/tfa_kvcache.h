@@ -1,0 +1,30 @@
+// tfa_kvcache.h — host-side declarations of the K/V-cache path (include/tfa.h: tfa_fwd_kvcache, tfa_kvcache_append): the append kernel's
+// arguments and the launchers of the KV-cache form of the LDS-DMA kernel (tfa_fwd_kernel_dma.h: VF_KVCACHE, KvcArgs), one translation unit
+// per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace tfa {
+
+// tfa_kvcache_append.hip (strides in ELEMENTS; 16-bit elements, 16-byte chunks)
+struct AppendArgs {
+  const void* k_new;          // (B, n_new, Hk, D) by strides kn_* / vn_*
+  const void* v_new;
+  void* k_cache;
+  void* v_cache;
+  const int* seqlens;         // device, B entries: row t of sequence b goes to key position seqlens[b] + t
+  const int* block_table;     // device (B, max_blocks) by bt_stride, or nullptr: contiguous cache
+  long long bt_stride;
+  long long ks_b, ks_h, ks_n; // cache strides: batch (contiguous) or page (paged), head, row
+  long long vs_b, vs_h, vs_n;
+  long long kn_b, kn_h, kn_n; // k_new strides: batch, head, row
+  long long vn_b, vn_h, vn_n;
+  long long total;            // threads with work: B * n_new * Hk * cpr
+  int n_new, Hk, cpr;         // cpr = D / 8: 16-byte chunks per row
+  int capacity;               // keys a sequence can hold: Nk_max, or max_blocks * page_size
+  int page_size, num_pages;
+};
+hipError_t launch_kvcache_append(const AppendArgs& a, hipStream_t stream);
+
+}  // namespace tfa

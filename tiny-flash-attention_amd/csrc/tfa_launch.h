@@ -203,6 +203,14 @@ static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* 
 template <typename T>
 hipError_t launch_splitkv_wide(const KArgs& a, bool causal, hipStream_t stream, LaunchGeom* geom, bool dry);
 
+// The KV-cache form of the LDS-DMA kernel (tfa_fwd_kvcache; fwd_kernel_dma_kvc): one translation unit per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.hip.
+// f32out: fp32 partials of a split launch (nt: with the non-temporal hint), else the 16-bit output of a single chunk
+template <typename T, int D>
+hipError_t launch_kvc(const KvcArgs& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVC_UNITS(T, D) template <> hipError_t launch_kvc<T, D>(const KvcArgs&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+TFA_KVC_UNITS(__bf16, 64) TFA_KVC_UNITS(__bf16, 128) TFA_KVC_UNITS(_Float16, 64) TFA_KVC_UNITS(_Float16, 128)
+#undef TFA_KVC_UNITS
+
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32>.hip —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).
 template <typename T, int D, bool CAUSAL, bool F32OUT>

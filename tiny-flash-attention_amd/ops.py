@@ -701,3 +701,144 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False,
                                    window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
     return out
+
+
+def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k_new, v_new, softmax_scale, causal):
+    """A TfaKvcacheParams for FlashAttention-2's layouts: q / out (B, Nq, H, D) (out: any 4-D strides given as (B, H, Nq, D)), the caches
+    (B, Nk_max, Hk, D) or paged (num_pages, page_size, Hk, D), k_new / v_new (B, n_new, Hk, D)."""
+    p = _lib.TfaKvcacheParams()
+    B, Nq, H, D = q.shape
+    Hk = k_cache.shape[2]
+    p.q, p.out = q.data_ptr(), out.data_ptr()
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    p.cache_seqlens = cache_seqlens.data_ptr()
+    p.B, p.H, p.Hk, p.Nq, p.D = B, H, Hk, Nq, D
+    if block_table is not None:
+        p.block_table = block_table.data_ptr()
+        p.block_table_stride = block_table.stride(0)
+        p.page_size, p.num_pages = k_cache.shape[1], k_cache.shape[0]
+        p.capacity = block_table.shape[1] * k_cache.shape[1]
+    else:
+        p.block_table = None
+        p.capacity = k_cache.shape[1]
+    for name, t in (("q_stride", q), ("k_stride", k_cache), ("v_stride", v_cache)):
+        arr = getattr(p, name)
+        arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)          # (B, N, H, D) tensors: batch / page, head, row
+    p.o_stride[0], p.o_stride[1], p.o_stride[2] = out.stride(0), out.stride(1), out.stride(2)   # out is handed over as (B, H, Nq, D)
+    if k_new is not None:
+        p.k_new, p.v_new, p.n_new = k_new.data_ptr(), v_new.data_ptr(), k_new.shape[1]
+        for name, t in (("knew_stride", k_new), ("vnew_stride", v_new)):
+            arr = getattr(p, name)
+            arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)
+    p.softmax_scale = float(softmax_scale)
+    p.is_causal = 1 if causal else 0
+    p.dtype = _DT[q.dtype]
+    return p
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
+                            num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
+                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
+    """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
+
+    ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
+    with ``block_table`` (B, max_blocks) int32 on the device (page_size a multiple of 64); ``cache_seqlens`` (B,) int32 on the device — never read on the
+    host, so the call does not synchronise and can be captured in a graph —, a host int (broadcast) or None (the full capacity).  ``k`` / ``v``
+    (B, n_new, Hk, D): appended IN PLACE at positions cache_seqlens[b] + t first (rows beyond the capacity are dropped), then attended;
+    ``cache_seqlens`` itself is not advanced.  ``causal``: bottom-right aligned per sequence.  ``num_splits``: key chunks per sequence (0 = the library's
+    suggestion from host-known sizes); the chunks are cut from each sequence's own length on the device.  GQA / MQA decode (Nq == 1) streams K / V once
+    per K/V head; Nq > 1 runs unpacked (K / V once per query head).
+    Returns ``out`` (B, Nq, H, D) — with more than one chunk a transposed view of the dense (B, H, Nq, D) result the merge writes — and with
+    ``return_softmax_lse`` also ``lse`` (B, H, Nq) fp32.  Not differentiable: an input that requires grad raises.
+    Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes,
+    fp32 inputs, head dims above 128."""
+    name = "flash_attn_with_kvcache"
+    for arg, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad),
+                     ("alibi_slopes", alibi_slopes)):
+        if val is not None:
+            raise NotImplementedError(f"{name}: {arg} is not implemented in the K/V-cache path")
+    if tuple(int(w) for w in window_size) != (-1, -1):
+        raise NotImplementedError(f"{name}: window_size is not implemented in the K/V-cache path (got {tuple(window_size)})")
+    if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
+        raise NotImplementedError(f"{name}: softcap is not implemented in the K/V-cache path")
+    for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be a 4-D tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+    if q.dtype == torch.float32:
+        raise ValueError(f"{name}: float16 / bfloat16 inputs only (no fp32 K/V-cache path)")
+    if q.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
+    B, Nq, H, D = q.shape
+    if D > 128:
+        raise ValueError(f"{name}: head dims up to 128 (got {D})")
+    if D % 8 != 0 or D < 8:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype")
+    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
+        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    Hk = k_cache.shape[2]
+    if Hk <= 0 or H % Hk != 0:
+        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
+    for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(3) != 1:
+            raise ValueError(f"{name}: {n} must have unit stride along the head dim")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks)")
+        if block_table.device != q.device or block_table.stride(1) != 1:
+            raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
+        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0:
+            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
+        capacity = block_table.shape[1] * k_cache.shape[1]
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"{name}: a contiguous cache must have q's batch size {B} (got {k_cache.shape[0]}); cache_batch_idx is not implemented")
+        capacity = k_cache.shape[1]
+    if capacity <= 0:
+        raise ValueError(f"{name}: the cache holds no key")
+    if (k is None) != (v is None):
+        raise ValueError(f"{name}: k and v must be given together")
+    if k is not None:
+        if cache_seqlens is None:
+            raise ValueError(f"{name}: k / v are appended at cache_seqlens, which must then be given")
+        for n, t in (("k", k), ("v", v)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[0] != B or t.shape[2] != Hk or t.shape[3] != D or t.shape[1] < 1:
+                raise ValueError(f"{name}: {n} must have shape ({B}, n_new, {Hk}, {D})")
+            if t.dtype != q.dtype or t.stride(3) != 1 or t.device != q.device:
+                raise ValueError(f"{name}: {n} must have q's dtype and device and unit stride along the head dim")
+        if k.shape != v.shape:
+            raise ValueError(f"{name}: k and v must have one shape")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
+        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
+    if cache_seqlens is None:
+        cache_seqlens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
+    elif isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), int(cache_seqlens), dtype=torch.int32, device=q.device)
+    elif (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
+          or not cache_seqlens.is_contiguous() or cache_seqlens.device != q.device):
+        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},) on q's device, a host int, or None")
+    num_splits = int(num_splits)
+    if num_splits < 0:
+        raise ValueError(f"{name}: num_splits must be >= 0 (0 = automatic; got {num_splits})")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+
+    L = _lib.lib()
+    lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device) if return_softmax_lse else None
+    dense = torch.empty((B, H, Nq, D), dtype=q.dtype, device=q.device)            # what the merge writes; one chunk: the kernel writes it the same way
+    p = _kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal)
+    if num_splits == 0:
+        num_splits = max(1, int(L.tfa_fwd_kvcache_suggest_splits(C.byref(p))))
+    need = L.tfa_fwd_kvcache_workspace(C.byref(p), num_splits)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+    out = dense.transpose(1, 2)
+    return (out, lse) if return_softmax_lse else out
