@@ -642,6 +642,48 @@ int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p);
 /* The append alone (k_new / v_new required): q, out, lse, Nq, H, softmax_scale and is_causal are not looked at. */
 int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream);
 
+/* ---- an fp8 (OCP e4m3fn) K/V cache behind the same calls ---------------------------------------------------------------------------------------
+ * k_cache / v_cache hold e4m3fn bytes (torch.float8_e4m3fn: 254 finite codes, 0x7f / 0xff NaN, no infinities) with one fp32 descale per (sequence, K/V head);
+ * q, out and the new rows k_new / v_new keep the 16-bit dtype p->dtype.  The calls take tfa_kvcache_params as above plus this struct; in them k_stride /
+ * v_stride count cache ELEMENTS, which are bytes, and everything said above about lengths, chunks, pages, empty rows, packing, splits, the single stream and graph
+ * capture holds unchanged.
+ *   Definition: attention over the exactly decoded cache.  e4m3fn -> bf16 / f16 is exact for every finite code, so
+ *     S[i,j] = softmax_scale * k_descale[b,hk] * q_i . dec(k8_j),  causal mask,  softmax,  out = v_descale[b,hk] * P . dec(v8),  lse = logsumexp(S).
+ *   Q and P are not quantised and no fp8 MFMA is used: with descales of 1.0 (or NULL) out and lse are BIT-IDENTICAL to tfa_fwd_kvcache over the caches converted to
+ *   p->dtype, for the same `splits`.  k_descale is folded into the score scale of the work item, v_descale multiplied into O in fp32 in front of its one rounding
+ *   (splits >= 2: into the fp32 partials; tfa_merge is unchanged).
+ *   k_descale / v_descale: device fp32, element (b, hk) at b * stride[0] + hk * stride[1] (elements; 0 allowed: a broadcast per-tensor scale), or NULL = 1.0.  With a
+ *     paged cache they are still indexed by the sequence b, not by the page.  Read by the kernels only (a scalar load per work item) — never on the host, so a captured
+ *     step sees values overwritten in place.  Precondition: finite and > 0; other values give unspecified results but no access out of bounds.
+ *   Zero fill: the descriptor extents end at the last valid key, now in bytes of 1-byte elements; the byte 0x00 decodes to +0, so NaN codes behind len_b never reach a result.
+ *   Append (k_new / v_new, 16-bit): quantised on the device and stored in place, byte = rne_e4m3fn(clamp(float(x) / descale[b,hk], -448, 448)) — a true fp32 division,
+ *     the clamp in front of the (non-saturating) conversion, NaN stays NaN; capacity and page checks as in tfa_kvcache_append; the rows are then attended as quantised.
+ *   D: a multiple of 16 in [16, 128] — 16-byte rows of 1-byte elements, and no 16-byte chunk reaches into the next head's bytes.
+ * Kernel: the e4m3 form of the KV-cache kernel.  A tile's LDS-DMA becomes register staging: 8 bytes per lane and piece through the same descriptors, decoded once
+ * (v_cvt_pk_f32_fp8, then the exact conversion to p->dtype) and written to the LDS bytes the DMA would have filled, so the tile loop, the LDS layout and the LDS size —
+ * 4 * 64 * W * 2 bytes, W = 64 or 128 the kernel width: 32 / 64 KiB, two workgroups per CU — are the 16-bit form's.  Grid and block equal tfa_fwd_kvcache_plan's.
+ * Refused, nothing launched — everything tfa_fwd_kvcache refuses (p->dtype: TFA_F16 / TFA_BF16 only), and: a NULL tfa_kvcache_fp8 (TFA_ERR_NULL); format other than
+ * TFA_KV_E4M3 (TFA_ERR_DTYPE); reserved_ != 0 (TFA_ERR_SHAPE); D not a multiple of 16 in [16, 128] (TFA_ERR_HEAD_DIM); cache strides not multiples of 16 bytes, a
+ * negative descale stride (TFA_ERR_STRIDE); a descale pointer not 4-byte aligned (TFA_ERR_ALIGN).
+ * tfa_fwd_kvcache_suggest_splits serves both cache types (it reads sizes only).
+ * Out of scope: e5m2 and e4m3fnuz caches, per-token or per-page scales, an fp8 q or out, fp8 in tfa_fwd / varlen / the backward, D > 128, and what tfa_fwd_kvcache leaves out.
+ * The 2 GiB bound on a contiguous (b, h) slice is still counted as for 2-byte elements (TFA_ERR_STRIDE as in tfa_fwd_kvcache for the same strides): an fp8 cache
+ * halves the bytes streamed and stored, it does not double the rows one contiguous slice may span; pages are not affected.
+ * Not measured yet (tools/bench_kvcache_fp8.py). */
+#define TFA_KV_E4M3 1
+typedef struct tfa_kvcache_fp8 {
+  const float* k_descale;        /* device, or NULL = 1.0 */
+  const float* v_descale;
+  int64_t k_descale_stride[2];   /* batch, K/V head (elements; 0 allowed) */
+  int64_t v_descale_stride[2];
+  int32_t format;                /* TFA_KV_E4M3 */
+  int32_t reserved_;             /* must be 0 */
+} tfa_kvcache_fp8;
+int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream);
+long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits);
+int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes);
+int tfa_kvcache_append_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

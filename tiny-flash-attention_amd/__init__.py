@@ -13,7 +13,7 @@ Reference-named entry points (same names, argument order and return shapes):
 
 FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen_func`` with ``causal``, ``window_size``, ``alibi_slopes`` and ``softcap``
 (GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.
-Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append).
+Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append; 16-bit or fp8 e4m3 caches with ``k_descale`` / ``v_descale``).
 """
 from .ops import (  # noqa: F401
     flash_attention_v2_cutlass,

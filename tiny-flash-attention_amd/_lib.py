@@ -85,6 +85,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_plan",
     "tfa_fwd_kvcache_suggest_splits",
     "tfa_kvcache_append",
+    "tfa_fwd_kvcache_fp8",
+    "tfa_fwd_kvcache_fp8_workspace",
+    "tfa_fwd_kvcache_fp8_plan",
+    "tfa_kvcache_append_fp8",
 )
 
 
@@ -268,6 +272,22 @@ class TfaKvcacheParams(C.Structure):
     ]
 
 
+TFA_KV_E4M3 = 1
+
+
+class TfaKvcacheFp8(C.Structure):
+    """struct tfa_kvcache_fp8 (include/tfa.h): the descales of an e4m3 K/V cache, handed to the _fp8 entry points beside TfaKvcacheParams."""
+
+    _fields_ = [
+        ("k_descale", C.c_void_p),
+        ("v_descale", C.c_void_p),
+        ("k_descale_stride", C.c_int64 * 2),
+        ("v_descale_stride", C.c_int64 * 2),
+        ("format", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
 class TfaError(RuntimeError):
     def __init__(self, status, text):
         super().__init__(f"tfa status {status}: {text}")
@@ -395,6 +415,16 @@ def lib():
     L.tfa_fwd_kvcache_suggest_splits.argtypes = [PK]
     L.tfa_kvcache_append.restype = C.c_int
     L.tfa_kvcache_append.argtypes = [PK, C.c_void_p]
+    # ... with an e4m3 cache (tfa_kvcache_fp8)
+    P8 = C.POINTER(TfaKvcacheFp8)
+    L.tfa_fwd_kvcache_fp8.restype = C.c_int
+    L.tfa_fwd_kvcache_fp8.argtypes = [PK, P8, C.c_int, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_fp8_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_fp8_workspace.argtypes = [PK, P8, C.c_int]
+    L.tfa_fwd_kvcache_fp8_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_fp8_plan.argtypes = [PK, P8, C.c_int, IP, IP, IP]
+    L.tfa_kvcache_append_fp8.restype = C.c_int
+    L.tfa_kvcache_append_fp8.argtypes = [PK, P8, C.c_void_p]
     _lib = L
     return L
 

@@ -704,8 +704,18 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
 
 // ---- attention over a K/V cache (tfa.h: tfa_fwd_kvcache) ----------------------------------------------------------------------------------
 // What the append and the attention both need of *p: the cache side.  Nothing here (or anywhere on this path) reads device memory.
-static int kvcache_check_cache(const tfa_kvcache_params* p) {
+// q8 != nullptr: the cache holds e4m3 bytes (tfa_fwd_kvcache_fp8) — its strides count bytes, its rows are 16-byte chunks of 16 elements; q, out and the new rows stay 16-bit
+static int kvcache_check_cache(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8 = nullptr) {
   if (!p) return TFA_ERR_NULL;
+  const int ces = q8 ? 1 : 2;                                     // bytes per cache element
+  if (q8) {
+    if (q8->format != TFA_KV_E4M3) return TFA_ERR_DTYPE;
+    if (q8->reserved_ != 0) return TFA_ERR_SHAPE;
+    if (p->D < 16 || p->D > 128 || (p->D % 16) != 0) return TFA_ERR_HEAD_DIM;
+    for (int i = 0; i < 2; ++i)
+      if (q8->k_descale_stride[i] < 0 || q8->v_descale_stride[i] < 0) return TFA_ERR_STRIDE;
+    if (((uintptr_t)q8->k_descale | (uintptr_t)q8->v_descale) & 3) return TFA_ERR_ALIGN;
+  }
   if (!p->k_cache || !p->v_cache || !p->cache_seqlens) return TFA_ERR_NULL;
   if ((p->k_new == nullptr) != (p->v_new == nullptr)) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
@@ -720,10 +730,11 @@ static int kvcache_check_cache(const tfa_kvcache_params* p) {
   const int64_t span = paged ? p->page_size : p->capacity;       // rows one buffer descriptor has to reach: a page, or a sequence's slice
   const int64_t* st[4] = {p->k_stride, p->v_stride, p->knew_stride, p->vnew_stride};
   for (int t = 0; t < (p->k_new ? 4 : 2); ++t) {
+    const int es = t < 2 ? ces : 2;
     for (int i = 0; i < 3; ++i)
-      if (st[t][i] < 0 || (st[t][i] * 2) % 16 != 0) return TFA_ERR_STRIDE;
+      if (st[t][i] < 0 || (st[t][i] * es) % 16 != 0) return TFA_ERR_STRIDE;
     if (st[t][2] < p->D) return TFA_ERR_STRIDE;
-    if (t < 2 && ((span + 512) * st[t][2] + p->D) * 2 >= (int64_t)0x7fffffff) return TFA_ERR_STRIDE;   // (one_descriptor's bound)
+    if (t < 2 && ((span + 512) * st[t][2] + p->D) * es >= (int64_t)0x7fffffff) return TFA_ERR_STRIDE;   // (one_descriptor's bound)
   }
   if (((uintptr_t)p->k_cache | (uintptr_t)p->v_cache | (uintptr_t)p->k_new | (uintptr_t)p->v_new) & 15) return TFA_ERR_ALIGN;
   if (((uintptr_t)p->cache_seqlens | (uintptr_t)p->block_table) & 3) return TFA_ERR_ALIGN;
@@ -739,8 +750,11 @@ static int kvcache_chunks(const tfa_kvcache_params* p, int splits) {
 // GQA / MQA decode runs packed (pack_gqa_rows: one query row per head, the H / Hk heads of a K/V head as rows of one non-causal problem)
 static bool kvcache_packs(const tfa_kvcache_params* p) { return p->Nq == 1 && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128; }
 
-static int kvcache_run(const tfa_kvcache_params* p, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
-  int st = kvcache_check_cache(p);
+static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
+
+// one host path for the 16-bit cache (q8 == nullptr: tfa_fwd_kvcache) and the e4m3 cache (tfa_fwd_kvcache_fp8): validation, chunking, packing and the three launches
+static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+  int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   if (!p->q || !p->out) return TFA_ERR_NULL;
   if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
@@ -782,7 +796,7 @@ static int kvcache_run(const tfa_kvcache_params* p, int splits, float* workspace
     if (st != TFA_OK) st = validate(&f, &a, tfa::kSplitVariant);
   }
   if (st != TFA_OK) return st;
-  tfa::KvcArgs ka;
+  tfa::Kvc8Args ka;                                         // (the 16-bit launch takes its KvcArgs base)
   memset(&ka, 0, sizeof(ka));
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
@@ -800,28 +814,33 @@ static int kvcache_run(const tfa_kvcache_params* p, int splits, float* workspace
   ka.tpp = paged ? p->page_size / 64 : 1;
   ka.fd_nsplit = tfa::fastdiv_of((unsigned)ns);
   ka.fd_tpp = tfa::fastdiv_of((unsigned)ka.tpp);
-  ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * 4 >= (768ll << 20)) ? 1 : 0;
+  ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * (q8 ? 2 : 4) >= (768ll << 20)) ? 1 : 0;
   if ((long long)ka.nbh * ka.nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
   const bool causal = f.is_causal != 0;                    // (the packed one-row problem is non-causal)
   const bool nt = ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;   // tfa_fwd_splitkv's rule for the non-temporal hint
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (!dry && p->k_new) {                                  // this step's keys first, on the same stream
-    st = tfa_kvcache_append(p, stream);
+    st = kvcache_append_run(p, q8, stream);
     if (st != TFA_OK) return st;
   }
+  if (q8) {
+    ka.k_descale = q8->k_descale; ka.v_descale = q8->v_descale;
+    ka.kd_b = q8->k_descale_stride[0]; ka.kd_h = q8->k_descale_stride[1];
+    ka.vd_b = q8->v_descale_stride[0]; ka.vd_h = q8->v_descale_stride[1];
+  }
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
-    return tfa::launch_kvc<typename decltype(k)::T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
+    using T = typename decltype(k)::T;
+    if (q8) return tfa::launch_kvc8<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
+    return tfa::launch_kvc<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
   });
   if (e != hipSuccess) return (int)e;
   if (dry || ns == 1) return TFA_OK;
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
 }
 
-int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, splits, workspace, stream, nullptr, false); }
-
-int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) {
+static int kvcache_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
   tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_run(p, splits, nullptr, nullptr, &g, true);
+  const int st = kvcache_run(p, q8, splits, nullptr, nullptr, &g, true);
   if (st != TFA_OK) return st;
   if (grid) *grid = g.grid;
   if (block) *block = g.block;
@@ -829,12 +848,25 @@ int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int
   return TFA_OK;
 }
 
-long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) {
-  const int st = kvcache_run(p, splits, nullptr, nullptr, nullptr, true);
+static long long kvcache_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) {
+  const int st = kvcache_run(p, q8, splits, nullptr, nullptr, nullptr, true);
   if (st != TFA_OK) return st;
   const int ns = kvcache_chunks(p, splits);
   return ns > 1 ? (long long)ns * p->B * p->H * p->Nq * (p->D + 1) : 0;
 }
+
+int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, nullptr, splits, workspace, stream, nullptr, false); }
+int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) { return kvcache_plan(p, nullptr, splits, grid, block, lds_bytes); }
+long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) { return kvcache_workspace(p, nullptr, splits); }
+
+// the e4m3 cache: the second struct is required (its NULL descale pointers mean 1.0)
+int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream) {
+  return q8 ? kvcache_run(p, q8, splits, workspace, stream, nullptr, false) : TFA_ERR_NULL;
+}
+int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
+  return q8 ? kvcache_plan(p, q8, splits, grid, block, lds_bytes) : TFA_ERR_NULL;
+}
+long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) { return q8 ? kvcache_workspace(p, q8, splits) : (long long)TFA_ERR_NULL; }
 
 int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) {
   if (!p || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->capacity <= 0 || p->H % p->Hk != 0) return 1;
@@ -850,11 +882,11 @@ int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) {
   return s >= 2 ? (int)s : 1;
 }
 
-int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream) {
-  const int st = kvcache_check_cache(p);
+static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {
+  const int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   if (!p->k_new) return TFA_ERR_NULL;
-  tfa::AppendArgs a;
+  tfa::Append8Args a;                                      // (the 16-bit launch takes its AppendArgs base)
   memset(&a, 0, sizeof(a));
   a.k_new = p->k_new; a.v_new = p->v_new; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
   a.seqlens = p->cache_seqlens;
@@ -869,8 +901,16 @@ int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream) {
   a.capacity = p->capacity;
   a.page_size = p->block_table ? p->page_size : 1;
   a.num_pages = p->block_table ? p->num_pages : 1;
-  return (int)tfa::launch_kvcache_append(a, reinterpret_cast<hipStream_t>(stream));
+  if (!q8) return (int)tfa::launch_kvcache_append(a, reinterpret_cast<hipStream_t>(stream));
+  a.k_descale = q8->k_descale; a.v_descale = q8->v_descale;
+  a.kd_b = q8->k_descale_stride[0]; a.kd_h = q8->k_descale_stride[1];
+  a.vd_b = q8->v_descale_stride[0]; a.vd_h = q8->v_descale_stride[1];
+  a.bf16 = p->dtype == TFA_BF16 ? 1 : 0;
+  return (int)tfa::launch_kvcache_append_fp8(a, reinterpret_cast<hipStream_t>(stream));
 }
+
+int tfa_kvcache_append(const tfa_kvcache_params* p, void* stream) { return kvcache_append_run(p, nullptr, stream); }
+int tfa_kvcache_append_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) { return q8 ? kvcache_append_run(p, q8, stream) : TFA_ERR_NULL; }
 
 int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return route({nullptr, p, nullptr}, stream); }
 int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes) { return plan({nullptr, p, nullptr}, grid, block, lds_bytes); }

@@ -123,6 +123,43 @@ struct KvcArgs : KArgs {
   int pad_;
 };
 
+// The e4m3 form of the KV-cache form (tfa_fwd_kvcache_fp8): k_cache / v_cache hold OCP e4m3fn bytes with one fp32 descale per (sequence, K/V head).  The tile loop is
+// the 16-bit one: a tile's LDS-DMA is replaced by register staging — every lane loads the 8 source bytes behind the 16 LDS bytes its DMA piece would have filled
+// (same descriptors, same extents, now in bytes of 1-byte elements: rows behind the length still arrive as zeros, and 0x00 decodes to +0), decodes them to T (exact:
+// every finite e4m3 value is a bf16 and an f16) and writes them to that LDS address.  K swizzle, V layout, fragment reads, MFMAs, softmax and epilogue see what they see
+// in the 16-bit form; each cache element is decoded once.  k_descale is folded into the score scale, v_descale multiplied into O in fp32 in the epilogue.
+constexpr int VF_KV_E4M3 = 1 << 29;
+struct Kvc8Args : KvcArgs {
+  const float* k_descale;   // device fp32 by (kd_b, kd_h) elements, or nullptr = 1.0; indexed by (sequence, K/V head), paged or not
+  const float* v_descale;
+  long long kd_b, kd_h, vd_b, vd_h;
+};
+template <bool KV8>
+struct Kvc8View {
+  template <typename A> static __device__ __forceinline__ const Kvc8Args& of(const A& a) { return a; }
+};
+template <bool KV8, typename T> struct KvElem { using type = T; };
+template <typename T> struct KvElem<true, T> { using type = unsigned char; };
+
+// 8 e4m3 bytes of a K/V row (NT: with the non-temporal hint)
+template <bool NT>
+static __device__ __forceinline__ u32x2 kv8_load(__amdgpu_buffer_rsrc_t rs, int voffset) {
+  return __builtin_amdgcn_raw_buffer_load_b64(rs, voffset, 0, NT ? 2 : 0);
+}
+// 8 e4m3 bytes -> 8 T (v_cvt_pk_f32_fp8: OCP e4m3fn on gfx950; the fp32 -> T conversion of an e4m3 value is exact)
+template <typename T>
+static __device__ __forceinline__ u32x4 kv8_decode(u32x2 s) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  typedef __attribute__((ext_vector_type(8))) T t8;
+  t8 r;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)s[h], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)s[h], true);
+    r[4 * h + 0] = (T)lo[0]; r[4 * h + 1] = (T)lo[1]; r[4 * h + 2] = (T)hi[0]; r[4 * h + 3] = (T)hi[1];
+  }
+  return __builtin_bit_cast(u32x4, r);
+}
+
 // The kernel walks a STREAM of query blocks: workgroup g takes work items g, g+G, g+2G, ... (G =
 // gridDim.x; a causal work item is the pair {heavy block nmb-1-i, light block i}, so every item costs
 // the same).  With G = number of CUs the launch is persistent: no workgroup turn-around between
@@ -151,6 +188,13 @@ __global__ __launch_bounds__(NW * 64, D > 128 ? 1 : 2) void fwd_kernel_dma(const
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc(const KvcArgs p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (NT ? VF_DMA_NT : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+
+// The e4m3 form of the KV-cache form (tfa_fwd_kvcache_fp8): T is the type of q, out and of the decoded tiles
+template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8(const Kvc8Args p) {
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
 #include "tfa_fwd_kernel_dma_body.inc"
 }
 

@@ -2,6 +2,9 @@
 // argument `p` (KArgs, or KvcArgs in the KV-cache form) and T, D, NW, CAUSAL, F32OUT, VF, AB.
   using E = Elem<T>;
   constexpr bool KVC = (VF & VF_KVCACHE) != 0;
+  constexpr bool KV8 = (VF & VF_KV_E4M3) != 0;     // the K/V cache holds e4m3 bytes (tfa_fwd_kvcache_fp8): tiles are staged through registers and decoded to T on the way into LDS
+  constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
+  using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
   constexpr int BM = NW * 32;
   constexpr int BN = 64;
@@ -18,6 +21,7 @@
   static_assert(PPW >= 1 && PPW * NW == PIECES, "tile does not split into whole DMA pieces per wave");
   static_assert(!WIDE || (NW == 4 && AB == 0), "the 256-wide form: four waves, no ablations");
   static_assert(!KVC || (!WIDE && AB == 0 && !(VF & (VF_PERSIST | VF_LDSEPI))), "the KV-cache form: 64 / 128 wide, one work item per workgroup");
+  static_assert(!KV8 || (KVC && NBUF == 2), "the e4m3 form: a form of the two-buffer KV-cache kernel (one tile staged in registers)");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const kl = smem;                           // K buffers 0..2
@@ -47,24 +51,28 @@
       const int row = pc * (1024 / (D * 2)) + lane / CPR;
       const int cpos = lane % CPR;
       const int kch = cpos ^ k_swz<D>(row);            // source chunk of this lane; chunks beyond the valid head dim read as zeros
-      k_src[i] = kch * 8 < p.dv ? row * (int)p.ks_n * 2 + (kch << 4) : (int)TFA_OOB;
+      k_src[i] = kch * 8 < p.dv ? row * (int)p.ks_n * ES + kch * (8 * ES) : (int)TFA_OOB;
     }
     {  // V: invert v_lds_off(): LDS offset -> (key, 16-byte chunk)
       const int o = pc * 1024 + lane * 16;
       const int sub = o >> 9, R = (o >> 6) & 7, pcs = (o >> 4) & 3;
       const int dt = sub % DT, sh = sub / DT;
       const int key = 16 * (sh >> 1) + 4 * (sh & 1) + 8 * (R >> 2) + (R & 3);
-      v_src[i] = (dt * 4 + pcs) * 8 < p.dv ? key * (int)p.vs_n * 2 + ((dt * 4 + pcs) << 4) : (int)TFA_OOB;
+      v_src[i] = (dt * 4 + pcs) * 8 < p.dv ? key * (int)p.vs_n * ES + (dt * 4 + pcs) * (8 * ES) : (int)TFA_OOB;
     }
   }
-  const int k_tile_stride = BN * (int)p.ks_n * 2;
-  const int v_tile_stride = BN * (int)p.vs_n * 2;
+  const int k_tile_stride = BN * (int)p.ks_n * ES;
+  const int v_tile_stride = BN * (int)p.vs_n * ES;
 
   const int k_rd_base = qi * (D * 2);
   const int k_rd_swz = k_swz<D>(qi);
   const int i16 = lane & 15, g16 = (lane >> 4) & 1;
   const int v_rd_base = (hi * DT << 9) + ((i16 >> 2) << 6) + (g16 << 5) + ((i16 & 3) << 3);
-  const float sc = p.scale_log2;
+  float sc = p.scale_log2;
+  // e4m3 form: the descales of the work item's (sequence, K/V head) — k_descale goes into the score scale (sc, and the LSE's), v_descale into the epilogue.  One
+  // decode() reads them for the block it describes; the epilogue of the block before uses the copies taken in front of that decode() (cur_scale_lse, cur_vd)
+  float scale_lse = p.scale, vd_w = 1.f;
+  u32x2 st_k[KV8 ? PPW : 1], st_v[KV8 ? PPW : 1];   // e4m3 form: the tile in flight (8 bytes per piece and tensor)
 
   // ---- the block stream ----------------------------------------------------------------------
   struct Blk {
@@ -135,8 +143,8 @@
       } else {
         koff = (long long)k.tile0 * 64 * p.ks_n;
         voff = (long long)k.tile0 * 64 * p.vs_n;
-        kb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.ks_n + p.dv) * 2) : 0u;
-        vb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.vs_n + p.dv) * 2) : 0u;
+        kb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.ks_n + p.dv) * ES) : 0u;
+        vb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.vs_n + p.dv) * ES) : 0u;
       }
     } else if (nsplit > 1) {                                     // descriptor over the chunk only: OOB rows read as zeros
       koff = (long long)k.sp * p.chunk * p.ks_n;
@@ -147,8 +155,16 @@
       kb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.ks_n + p.dv) * 2) : 0u;
       vb = k.nk > 0 ? (unsigned)(((long long)(k.nk - 1) * p.vs_n + p.dv) * 2) : 0u;
     }
-    k.k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const T*>(p.k) + b * p.ks_b + hk * p.ks_h + koff), 0, kb, 0x00020000);
-    k.v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const T*>(p.v) + b * p.vs_b + hk * p.vs_h + voff), 0, vb, 0x00020000);
+    k.k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const KT*>(p.k) + b * p.ks_b + hk * p.ks_h + koff), 0, kb, 0x00020000);
+    k.v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const KT*>(p.v) + b * p.vs_b + hk * p.vs_h + voff), 0, vb, 0x00020000);
+    if constexpr (KV8) {
+      const Kvc8Args& p8 = Kvc8View<KV8>::of(p);
+      typedef __attribute__((address_space(4))) const float cfloat4;
+      const float kd = p8.k_descale ? ((cfloat4*)(uintptr_t)p8.k_descale)[b * p8.kd_b + hk * p8.kd_h] : 1.f;
+      vd_w = p8.v_descale ? ((cfloat4*)(uintptr_t)p8.v_descale)[b * p8.vd_b + hk * p8.vd_h] : 1.f;
+      sc = p.scale_log2 * kd;
+      scale_lse = p.scale * kd;
+    }
   };
   // KV-cache form, paged: the page of global tile `gt` of block-table row `row` (clamped into the cache: a bad entry can misplace a read, never leave the tensors)
   auto page_of = [&](int row, int gt) -> int {
@@ -179,14 +195,17 @@
         const int row0 = (gt - pidx * pk.tpp) << 6;
         int rows = k.nk - j * BN;
         rows = rows > BN ? BN : rows;
-        const unsigned kb = rows > 0 ? (unsigned)(((long long)(rows - 1) * p.ks_n + p.dv) * 2) : 0u;
-        const unsigned vb = rows > 0 ? (unsigned)(((long long)(rows - 1) * p.vs_n + p.dv) * 2) : 0u;
-        const auto k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const T*>(p.k) + page * p.ks_b + k.k_hoff + (long long)row0 * p.ks_n), 0, kb, 0x00020000);
-        const auto v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const T*>(p.v) + page * p.vs_b + k.v_hoff + (long long)row0 * p.vs_n), 0, vb, 0x00020000);
+        const unsigned kb = rows > 0 ? (unsigned)(((long long)(rows - 1) * p.ks_n + p.dv) * ES) : 0u;
+        const unsigned vb = rows > 0 ? (unsigned)(((long long)(rows - 1) * p.vs_n + p.dv) * ES) : 0u;
+        const auto k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const KT*>(p.k) + page * p.ks_b + k.k_hoff + (long long)row0 * p.ks_n), 0, kb, 0x00020000);
+        const auto v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const KT*>(p.v) + page * p.vs_b + k.v_hoff + (long long)row0 * p.vs_n), 0, vb, 0x00020000);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
           const int pc = wave * PPW + i;
-          if constexpr ((VF & VF_DMA_NT) != 0) {
+          if constexpr (KV8) {
+            st_k[i] = kv8_load<(VF & VF_DMA_NT) != 0>(k_rs, k_src[i]);
+            st_v[i] = kv8_load<(VF & VF_DMA_NT) != 0>(v_rs, v_src[i]);
+          } else if constexpr ((VF & VF_DMA_NT) != 0) {
             lds_dma16_nt(k_rs, lds_base + buf * TILE_BYTES + pc * 1024, k_src[i]);
             lds_dma16_nt(v_rs, lds_base + (NBUF + buf) * TILE_BYTES + pc * 1024, v_src[i]);
           } else {
@@ -201,12 +220,26 @@
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
       const int pc = wave * PPW + i;
-      if constexpr ((VF & VF_DMA_NT) != 0) {
+      if constexpr (KV8) {
+        st_k[i] = kv8_load<(VF & VF_DMA_NT) != 0>(k.k_rs, k_src[i] + j * k_tile_stride);
+        st_v[i] = kv8_load<(VF & VF_DMA_NT) != 0>(k.v_rs, v_src[i] + j * v_tile_stride);
+      } else if constexpr ((VF & VF_DMA_NT) != 0) {
         lds_dma16_nt(k.k_rs, lds_base + buf * TILE_BYTES + pc * 1024, k_src[i] + j * k_tile_stride);
         lds_dma16_nt(k.v_rs, lds_base + (NBUF + buf) * TILE_BYTES + pc * 1024, v_src[i] + j * v_tile_stride);
       } else {
         lds_dma16(k.k_rs, lds_base + buf * TILE_BYTES + pc * 1024, k_src[i] + j * k_tile_stride);
         lds_dma16(k.v_rs, lds_base + (NBUF + buf) * TILE_BYTES + pc * 1024, v_src[i] + j * v_tile_stride);
+      }
+    }
+  };
+  // e4m3 form: the staged tile, decoded (exactly: every e4m3 value is a T) and written to the 16 LDS bytes per piece this lane's DMA would have filled
+  auto stage_commit = [&](int buf) {
+    if constexpr (KV8) {
+#pragma unroll
+      for (int i = 0; i < PPW; ++i) {
+        const int o = (wave * PPW + i) * 1024 + lane * 16;
+        lds_write_b128(kl, buf * TILE_BYTES + o, kv8_decode<T>(st_k[i]));
+        lds_write_b128(vl, buf * TILE_BYTES + o, kv8_decode<T>(st_v[i]));
       }
     }
   };
@@ -250,6 +283,10 @@
 
     // tiles 0/1 and Q have been requested (prologue, or beside the previous block's epilogue)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (KV8) {
+      if (nt > 0) stage_commit(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
 #pragma unroll
     for (int s = 0; s < DS; ++s) {
       if (WIDE) asm volatile("" : "+a"(qf[s])); else asm volatile("" : "+v"(qf[s]));
@@ -434,6 +471,9 @@
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      // e4m3 form: tile j+1 goes from the staging registers into the other buffer — every wave left it at the barrier behind tile j-1; the barrier below
+      // puts the writes in front of tile j+1's reads
+      if constexpr (KV8) { if (more) stage_commit((buf + PD) % NBUF); }
       if (AB & 256) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // AB_NOBARRIER (timing only)
       else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
@@ -455,6 +495,7 @@
 
     // ---- next block of the stream ----------------------------------------------------------------
     const int cur_bh = cur.bh;
+    const float cur_scale_lse = scale_lse, cur_vd = vd_w;   // e4m3 form: the finished block's descales — decode() of the next block overwrites sc / scale_lse / vd_w
     const long long o_part = (long long)cur.sp * p.o_part_stride, lse_part = (long long)cur.sp * p.lse_part_stride;   // 0 unless split
     constexpr bool LDS_EPI = !F32OUT && (VF & VF_LDSEPI);   // 16-bit O goes out through LDS as whole rows
     bool have_next;
@@ -481,9 +522,9 @@
     auto ov = [&](int d, int i) -> float { return WIDE ? og[WIDE ? d : 0][i] : oacc[WIDE ? 0 : d][i]; };
     const float l_tot = pair_sum(l_run);
     const bool empty = !(l_tot > 0.f);
-    const float inv = empty ? 1.f : 1.f / l_tot;
+    const float inv = KV8 ? (empty ? 1.f : 1.f / l_tot) * cur_vd : (empty ? 1.f : 1.f / l_tot);   // e4m3 form: v_descale in fp32, in front of the one rounding of O
     if (p.lse != nullptr && hi == 0 && my_row < p.Nq) {
-      const float lse = empty ? INFINITY : (m_run * p.scale + __builtin_amdgcn_logf(l_tot) * 0.6931471805599453f);
+      const float lse = empty ? INFINITY : (m_run * (KV8 ? cur_scale_lse : p.scale) + __builtin_amdgcn_logf(l_tot) * 0.6931471805599453f);
       p.lse[lse_part + (long long)cur_bh * p.Nq + my_row] = lse;
     }
     if (F32OUT) {

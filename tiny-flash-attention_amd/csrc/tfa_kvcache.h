@@ -27,4 +27,14 @@ struct AppendArgs {
 };
 hipError_t launch_kvcache_append(const AppendArgs& a, hipStream_t stream);
 
+// tfa_kvcache_append_fp8.hip: the same append into an e4m3 cache — the new rows are 16-bit (bf16: the k_new / v_new dtype), the cache strides count bytes, every thread
+// turns 8 elements into 8 bytes: byte = rne_e4m3fn(clamp(float(x) / descale[b, hk], -448, 448)), NaN stays NaN
+struct Append8Args : AppendArgs {
+  const float* k_descale;     // device fp32 by (kd_b, kd_h) elements, or nullptr = 1.0
+  const float* v_descale;
+  long long kd_b, kd_h, vd_b, vd_h;
+  int bf16;                   // the new rows' dtype: 1 = bf16, 0 = f16
+};
+hipError_t launch_kvcache_append_fp8(const Append8Args& a, hipStream_t stream);
+
 }  // namespace tfa

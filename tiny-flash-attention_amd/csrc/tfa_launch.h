@@ -210,6 +210,12 @@ hipError_t launch_kvc(const KvcArgs& a, bool causal, bool f32out, bool nt, hipSt
 #define TFA_KVC_UNITS(T, D) template <> hipError_t launch_kvc<T, D>(const KvcArgs&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
 TFA_KVC_UNITS(__bf16, 64) TFA_KVC_UNITS(__bf16, 128) TFA_KVC_UNITS(_Float16, 64) TFA_KVC_UNITS(_Float16, 128)
 #undef TFA_KVC_UNITS
+// ... and its e4m3 form (tfa_fwd_kvcache_fp8; fwd_kernel_dma_kvc8): tfa_kvc8_inst_<dtype>_<W>.hip, T the type of q and out
+template <typename T, int D>
+hipError_t launch_kvc8(const Kvc8Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVC8_UNITS(T, D) template <> hipError_t launch_kvc8<T, D>(const Kvc8Args&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+TFA_KVC8_UNITS(__bf16, 64) TFA_KVC8_UNITS(__bf16, 128) TFA_KVC8_UNITS(_Float16, 64) TFA_KVC8_UNITS(_Float16, 128)
+#undef TFA_KVC8_UNITS
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32>.hip —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

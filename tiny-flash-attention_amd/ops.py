@@ -739,7 +739,7 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
-                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
+                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, k_descale=None, v_descale=None):
     """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
 
     ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
@@ -751,8 +751,14 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     per K/V head; Nq > 1 runs unpacked (K / V once per query head).
     Returns ``out`` (B, Nq, H, D) — with more than one chunk a transposed view of the dense (B, H, Nq, D) result the merge writes — and with
     ``return_softmax_lse`` also ``lse`` (B, H, Nq) fp32.  Not differentiable: an input that requires grad raises.
+    An fp8 cache (tfa_fwd_kvcache_fp8): ``k_cache`` and ``v_cache`` of dtype ``torch.float8_e4m3fn`` with ``k_descale`` / ``v_descale``, float32 device
+    tensors of shape (B, Hk) with any strides (an ``expand``ed per-tensor scale works), None = 1.0; with a paged cache they are still indexed by the sequence.
+    ``q``, ``k`` / ``v`` and ``out`` keep q's 16-bit dtype.  The result is attention over the exactly decoded cache: scores scaled by ``k_descale[b, hk]``, the
+    output by ``v_descale[b, hk]`` in fp32; Q and P are not quantised.  ``k`` / ``v`` are quantised on the device as they are appended —
+    ``rne_e4m3fn(clamp(x / descale, -448, 448))`` — and attended as quantised.  The descales are read by the kernels only (no synchronisation; a captured step sees
+    values overwritten in place) and must be finite and > 0.  The head dim must be a multiple of 16.
     Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes,
-    fp32 inputs, head dims above 128."""
+    fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
     name = "flash_attn_with_kvcache"
     for arg, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad),
                      ("alibi_slopes", alibi_slopes)):
@@ -776,13 +782,26 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise ValueError(f"{name}: head dims up to 128 (got {D})")
     if D % 8 != 0 or D < 8:
         raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
+        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype, or both caches be torch.float8_e4m3fn (got {q.dtype}, {k_cache.dtype}, "
+                        f"{v_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
+    if fp8 and D % 16 != 0:
+        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError(f"{name}: k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a {k_cache.dtype} cache)")
     if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
         raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
     Hk = k_cache.shape[2]
     if Hk <= 0 or H % Hk != 0:
         raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
+    for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name}: {n} must be a float32 tensor")
+        if tuple(t.shape) != (B, Hk) or t.device != q.device:
+            raise ValueError(f"{name}: {n} must have shape ({B}, {Hk}) on q's device (got {tuple(t.shape)} on {t.device})")
     for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if t.stride(3) != 1:
             raise ValueError(f"{name}: {n} must have unit stride along the head dim")
@@ -833,12 +852,24 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     p = _kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal)
     if num_splits == 0:
         num_splits = max(1, int(L.tfa_fwd_kvcache_suggest_splits(C.byref(p))))
-    need = L.tfa_fwd_kvcache_workspace(C.byref(p), num_splits)
+    if fp8:
+        p8 = _lib.TfaKvcacheFp8()
+        p8.format = _lib.TFA_KV_E4M3
+        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
+            if t is not None:
+                setattr(p8, ptr, t.data_ptr())
+                strides[0], strides[1] = t.stride(0), t.stride(1)
+        need = L.tfa_fwd_kvcache_fp8_workspace(C.byref(p), C.byref(p8), num_splits)
+    else:
+        need = L.tfa_fwd_kvcache_workspace(C.byref(p), num_splits)
     if need < 0:
         _lib.check(int(need))
     ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        if fp8:
+            _lib.check(L.tfa_fwd_kvcache_fp8(C.byref(p), C.byref(p8), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        else:
+            _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
     out = dense.transpose(1, 2)
     return (out, lse) if return_softmax_lse else out
