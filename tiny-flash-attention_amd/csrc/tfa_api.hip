@@ -381,13 +381,9 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
   return (int)tfa::by_dtype_width<64, 128>(f.dtype, f.D, [&](auto k) {
     using T = typename decltype(k)::T;
     constexpr int W = decltype(k)::W;
-    if (!win) return tfa::launch_fwd_form<T, W, true, false>(a, causal, f32out, variant, s, geom, dry);   // (no window: always varlen here)
-    if (al && al->capped) return vl ? tfa::launch_fwd_form<T, W, true, true, false, true>(a, causal, f32out, variant, s, geom, dry)
-                                    : tfa::launch_fwd_form<T, W, false, true, false, true>(a, causal, f32out, variant, s, geom, dry);
-    if (al) return vl ? tfa::launch_fwd_form<T, W, true, true, true>(a, causal, f32out, variant, s, geom, dry)
-                      : tfa::launch_fwd_form<T, W, false, true, true>(a, causal, f32out, variant, s, geom, dry);
-    return vl ? tfa::launch_fwd_form<T, W, true, true>(a, causal, f32out, variant, s, geom, dry)
-              : tfa::launch_fwd_form<T, W, false, true>(a, causal, f32out, variant, s, geom, dry);
+    return tfa::by_form(vl != nullptr, win != nullptr, al != nullptr, al && al->capped, [&](auto form) {
+      return tfa::launch_fwd_form<T, W, decltype(form)::FORM>(a, causal, f32out, variant, s, geom, dry);
+    });
   });
 }
 

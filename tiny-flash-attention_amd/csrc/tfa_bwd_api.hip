@@ -261,13 +261,9 @@ int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, 
     return (int)tfa::by_dtype_width<64, 128>(v.dtype, v.D, [&](auto k) {
       using T = typename decltype(k)::T;
       constexpr int W = decltype(k)::W;
-      if (!local) return tfa::launch_bwd_form<T, W, true, false>(m, keys, (int)grid, causal, f32, s, dry);   // (no window: always varlen here)
-      if (capped) return varlen ? tfa::launch_bwd_form<T, W, true, true, false, true>(m, keys, (int)grid, causal, f32, s, dry)
-                                : tfa::launch_bwd_form<T, W, false, true, false, true>(m, keys, (int)grid, causal, f32, s, dry);
-      if (alibi) return varlen ? tfa::launch_bwd_form<T, W, true, true, true>(m, keys, (int)grid, causal, f32, s, dry)
-                               : tfa::launch_bwd_form<T, W, false, true, true>(m, keys, (int)grid, causal, f32, s, dry);
-      return varlen ? tfa::launch_bwd_form<T, W, true, true>(m, keys, (int)grid, causal, f32, s, dry)
-                    : tfa::launch_bwd_form<T, W, false, true>(m, keys, (int)grid, causal, f32, s, dry);
+      return tfa::by_form(varlen, local, alibi, capped, [&](auto form) {
+        return tfa::launch_bwd_form<T, W, decltype(form)::FORM>(m, keys, (int)grid, causal, f32, s, dry);
+      });
     });
   };
   // dQ (and delta): 256-row resident blocks of each (sequence, query head)

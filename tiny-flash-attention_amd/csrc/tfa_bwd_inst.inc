@@ -1,4 +1,4 @@
-// tfa_bwd_inst.inc — instantiates the backward kernels for one (dtype, head dim); included by tfa_bwd_inst_*.hip
+// tfa_bwd_inst.inc — instantiates the backward kernels for one (dtype, head dim); compiled as the units tfa_bwd_inst_* (the Makefile turns a unit's name into the defines)
 #include <hip/hip_runtime.h>
 #include "tfa_bwd_launch.h"
 
@@ -29,7 +29,7 @@ static hipError_t launch_bwd_mode(const BArgs& a, int grid, bool causal, bool f3
 }
 
 #if defined(TFA_DVB)
-// one unit per (dtype, valid column blocks) of the 256-wide kernels: tfa_bwd_inst_<dtype>_256_v<5..8>.hip
+// one unit per (dtype, valid column blocks) of the 256-wide kernels: tfa_bwd_inst_<dtype>_256_v<5..8>
 template <>
 hipError_t launch_bwd_wide<TFA_T, TFA_DVB>(const BArgs& a, int mode, int grid, bool causal, bool f32out, hipStream_t s, bool dry) {
   switch (mode) {

@@ -1,5 +1,5 @@
 // tfa_dma256_inst.inc — the LDS-DMA kernel 256 wide for one dtype: the partial pass of tfa_fwd_splitkv at head dims 136..256
-// (fp32 partial O + LSE per key chunk, the chunk index in the grid).  Included by tfa_dma_inst_<dtype>_256.hip.
+// (fp32 partial O + LSE per key chunk, the chunk index in the grid).  Compiled as the units tfa_dma_inst_<dtype>_256.
 #include "tfa_launch.h"
 
 namespace tfa {

@@ -1,5 +1,5 @@
 // tfa_fwd_inst.inc — instantiates the kernel variants for one (TFA_T, TFA_D, TFA_CAUSAL).
-// Included by tfa_fwd_inst_<dtype>_<D>_c<0|1>.hip so the eight units compile in parallel.
+// Compiled as the units tfa_fwd_inst_<dtype>_<D>_c<0|1> so the eight units compile in parallel.
 // Product build: the dispatched kernels only; -DTFA_EXPERIMENTAL adds the A/B arms (tfa_launch.h).
 #include "tfa_launch.h"
 

@@ -52,6 +52,37 @@ static inline auto by_dtype_width(int dtype, int D, F&& f) {
   return dtype == TFA_BF16 ? f(Shape<__bf16, W>{}) : f(Shape<_Float16, W>{});
 }
 
+// The form of an il8 / il4 forward or backward dQ / dK/dV launch beyond the plain fixed-length one: a mask of these bits, a template argument of launch_fwd_form
+// and launch_bwd_form.  The ALiBi and softcap kernels are forms of the local ones; softcap's slopes are a run-time choice of its one kernel (no ALIBI bit);
+// the local kernels exist as the causal template only (the window carries the right edge).
+enum : int { FORM_VARLEN = 1, FORM_LOCAL = 2, FORM_ALIBI = 4, FORM_SOFTCAP = 8 };
+constexpr bool form_legal(int form, bool causal = true) {
+  return form > 0 && form < 16 && ((form & FORM_LOCAL) ? causal : !(form & (FORM_ALIBI | FORM_SOFTCAP))) && !((form & FORM_ALIBI) && (form & FORM_SOFTCAP));
+}
+// THE list of the legal forms, X(mask): each is one instantiation unit per (dtype, width) of the forward (tfa_fwd_inst_<varlen|local|alibi|softcap>_...) and of
+// the backward (tfa_bwd_inst_...), fixed-length (_fx) or varlen (_vl) — the Makefile's words of those names carry the same masks.  The declarations of tfa_launch.h
+// and tfa_bwd_launch.h and by_form's switch come from here
+#define TFA_FORMS(X)                                                                                                        \
+  X(FORM_VARLEN) X(FORM_LOCAL) X(FORM_LOCAL | FORM_VARLEN) X(FORM_LOCAL | FORM_ALIBI) X(FORM_LOCAL | FORM_ALIBI | FORM_VARLEN) \
+  X(FORM_LOCAL | FORM_SOFTCAP) X(FORM_LOCAL | FORM_SOFTCAP | FORM_VARLEN)
+// ... and the (dtype, width) pairs each of them is built for: X(T, D, ...)
+#define TFA_FORM_SHAPES(X, ...) X(__bf16, 64, __VA_ARGS__) X(__bf16, 128, __VA_ARGS__) X(_Float16, 64, __VA_ARGS__) X(_Float16, 128, __VA_ARGS__)
+template <int FORM_>
+struct Form {
+  static constexpr int FORM = FORM_;
+};
+// The one run-time -> compile-time switch of the form: calls f(Form<mask>{}).  No window: the plain varlen form (the only caller without one); else the local
+// form or, with slopes, its ALiBi form or, capped (slopes or not), its softcap form — fixed-length or varlen.
+template <typename F>
+static inline auto by_form(bool varlen, bool local, bool alibi, bool capped, F&& f) {
+  const int form = !local ? FORM_VARLEN : FORM_LOCAL | (varlen ? FORM_VARLEN : 0) | (capped ? FORM_SOFTCAP : alibi ? FORM_ALIBI : 0);
+#define TFA_BY_FORM(mask) \
+  if (form == (mask)) return f(Form<(mask)>{});
+  TFA_FORMS(TFA_BY_FORM)
+#undef TFA_BY_FORM
+  return f(Form<FORM_VARLEN>{});   // (never: the line above names every value `form` takes)
+}
+
 // Local (sliding-window) attention, FlashAttention-2's window: key j is visible to row i iff i + shift - left <= j <= i + shift + right, -1 = unbounded on
 // that side, causal forces right = 0.  A side that reaches past every key of every row is unbounded: left >= nk - 1, right >= nq - 1 (max_seqlen for
 // varlen).  What is left is FULL (-1, -1), CAUSAL (-1, 0) — the fixed-length and varlen kernels, same bits — or a true window, the LOCAL instantiations.
@@ -71,7 +102,6 @@ static inline void set_window(Args* a, int left, int right, int nq, int nk) {
   a->win_left = left < 0 ? nq + nk : left;
   a->win_right = right < 0 ? nq + nk : right;
 }
-
 
 // ALiBi (tfa_fwd_alibi / tfa_bwd_alibi and their varlen forms): one fp32 slope per (batch / sequence, query head) in DEVICE memory, row stride 0 (one row shared
 // by the batch) or H.  Checked without reading it: the kernels' work items load their slope themselves (no copy, no synchronisation, graph-capturable).

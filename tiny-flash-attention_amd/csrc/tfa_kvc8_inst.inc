@@ -1,5 +1,5 @@
 // tfa_kvc8_inst.inc — instantiates the e4m3 form of the KV-cache kernel (tfa_fwd_kernel_dma.h: fwd_kernel_dma_kvc8) for one (TFA_T, TFA_D), as tfa_kvc_inst.inc does for
-// the 16-bit form: causal and not, fp32 partials (split) with and without the non-temporal hint, the 16-bit direct output of a single chunk.  Included by tfa_kvc8_inst_<dtype>_<W>.hip.
+// the 16-bit form: causal and not, fp32 partials (split) with and without the non-temporal hint, the 16-bit direct output of a single chunk.  Compiled as the units tfa_kvc8_inst_<dtype>_<W>.
 #include "tfa_launch.h"
 #include "tfa_kvcache.h"
 

@@ -1,5 +1,5 @@
 // tfa_kvc_inst.inc — instantiates the KV-cache form of the LDS-DMA kernel (tfa_fwd_kernel_dma.h: fwd_kernel_dma_kvc) for one (TFA_T, TFA_D): causal and not,
-// fp32 partials (split) with and without the non-temporal hint, and the 16-bit direct output of a single chunk.  Included by tfa_kvc_inst_<dtype>_<W>.hip.
+// fp32 partials (split) with and without the non-temporal hint, and the 16-bit direct output of a single chunk.  Compiled as the units tfa_kvc_inst_<dtype>_<W>.
 #include "tfa_launch.h"
 #include "tfa_kvcache.h"
 

@@ -117,7 +117,7 @@ constexpr int il_lds_bytes() {
   return ((VF & VF_IL_KSPLIT) ? 8 : 4) * 64 * D * 2 + (((VF & VF_IL_EPI) && !(VF & VF_IL_EPI_INPLACE)) ? NW * 32 * D * 2 : 0) + 16 + NW * 32 * 4;
 }
 
-// one translation unit per (dtype, width, causal): tfa_fwd_inst_<dtype>_<D>_c<0|1>.hip specialises launch_fwd_c
+// one translation unit per (dtype, width, causal): tfa_fwd_inst_<dtype>_<D>_c<0|1> specialises launch_fwd_c
 template <typename T, int D, bool CAUSAL>
 hipError_t launch_fwd_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
 #define TFA_FWD_UNITS(T, D)                                                                             \
@@ -129,31 +129,21 @@ template <typename T, int D>
 static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
   return causal ? launch_fwd_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
-// the packed variable-length (VF_IL_VARLEN) and local (sliding-window, VF_IL_LOCAL) forms of variants 30 and 32: one translation unit per (dtype, width, form,
-// causal) — tfa_fwd_inst_varlen_<dtype>_<D>_c<0|1>.hip (VARLEN) and tfa_fwd_inst_local_<dtype>_<D>_<fx|vl>.hip (LOCAL, fixed-length or VARLEN: the CAUSAL template
-// only, tfa_fwd_form_inst.inc) and tfa_fwd_inst_alibi_<dtype>_<D>_<fx|vl>.hip (ALIBI: the ALiBi form of the local kernels) and
-// tfa_fwd_inst_softcap_<dtype>_<D>_<fx|vl>.hip (SOFTCAP: the soft-capping form of the local kernels, slopes optional at run time)
-template <typename T, int D, bool VARLEN, bool LOCAL, bool CAUSAL, bool ALIBI = false, bool SOFTCAP = false>
+// the forms of variants 30 and 32 (tfa_host_util.h: TFA_FORMS — packed variable-length, local, and the local kernels' ALiBi and softcap forms): one translation
+// unit per (dtype, width, form) — the local forms as the CAUSAL template only (units tfa_fwd_inst_<local|alibi|softcap>_<dtype>_<D>_<fx|vl>), plain varlen per
+// causal too (units tfa_fwd_inst_varlen_<dtype>_<D>_c<0|1>) — each specialising launch_fwd_form_c (tfa_fwd_form_inst.inc)
+template <typename T, int D, int FORM, bool CAUSAL>
 hipError_t launch_fwd_form_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_FWD_FORM_UNITS(T, D)                                                                                         \
-  template <> hipError_t launch_fwd_form_c<T, D, true, false, false>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool); \
-  template <> hipError_t launch_fwd_form_c<T, D, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, false, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, false, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, true, true, true, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, false, true, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);  \
-  template <> hipError_t launch_fwd_form_c<T, D, true, true, true, false, true>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
-TFA_FWD_FORM_UNITS(__bf16, 64) TFA_FWD_FORM_UNITS(__bf16, 128) TFA_FWD_FORM_UNITS(_Float16, 64) TFA_FWD_FORM_UNITS(_Float16, 128)
+#define TFA_FWD_FORM_UNIT(T, D, FORM, CAUSAL) template <> hipError_t launch_fwd_form_c<T, D, (FORM), CAUSAL>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
+#define TFA_FWD_FORM_UNITS(FORM) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM, true)
+TFA_FORMS(TFA_FWD_FORM_UNITS) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM_VARLEN, false)
 #undef TFA_FWD_FORM_UNITS
-template <typename T, int D, bool VARLEN, bool LOCAL, bool ALIBI = false, bool SOFTCAP = false>
+#undef TFA_FWD_FORM_UNIT
+template <typename T, int D, int FORM>
 static inline hipError_t launch_fwd_form(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
-  static_assert(LOCAL || !ALIBI, "the ALiBi kernels are a form of the local ones");
-  static_assert(!SOFTCAP || (LOCAL && !ALIBI), "the softcap kernels are a form of the local ones (slopes: KArgs::slopes, or null)");
-  if constexpr (SOFTCAP) return launch_fwd_form_c<T, D, VARLEN, true, true, false, true>(a, f32out, variant, stream, geom, dry);
-  else if constexpr (ALIBI) return launch_fwd_form_c<T, D, VARLEN, true, true, true>(a, f32out, variant, stream, geom, dry);
-  else if constexpr (LOCAL) return launch_fwd_form_c<T, D, VARLEN, true, true>(a, f32out, variant, stream, geom, dry);   // (the window carries the right edge)
-  else return causal ? launch_fwd_form_c<T, D, VARLEN, false, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_form_c<T, D, VARLEN, false, false>(a, f32out, variant, stream, geom, dry);
+  static_assert(form_legal(FORM), "not a form of the il kernels (tfa_host_util.h: form_legal)");
+  if constexpr (FORM & FORM_LOCAL) return launch_fwd_form_c<T, D, FORM, true>(a, f32out, variant, stream, geom, dry);   // (the window carries the right edge)
+  else return causal ? launch_fwd_form_c<T, D, FORM, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_form_c<T, D, FORM, false>(a, f32out, variant, stream, geom, dry);
 }
 
 // common tail of every launcher: report the geometry, opt in to the dynamic LDS size on this device, launch, and return
@@ -199,25 +189,25 @@ static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* 
   return launch_common(kern, attr_mask, a.nbh * a.nwork, NW * 64, lds, a, stream, geom, dry);
 }
 
-// The LDS-DMA kernel 256 wide, fp32 partial output: tfa_fwd_splitkv's one-launch form for head dims above 128 (tfa_dma_inst_<dtype>_256.hip)
+// The LDS-DMA kernel 256 wide, fp32 partial output: tfa_fwd_splitkv's one-launch form for head dims above 128 (tfa_dma_inst_<dtype>_256)
 template <typename T>
 hipError_t launch_splitkv_wide(const KArgs& a, bool causal, hipStream_t stream, LaunchGeom* geom, bool dry);
 
-// The KV-cache form of the LDS-DMA kernel (tfa_fwd_kvcache; fwd_kernel_dma_kvc): one translation unit per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.hip.
+// The KV-cache form of the LDS-DMA kernel (tfa_fwd_kvcache; fwd_kernel_dma_kvc): one translation unit per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.
 // f32out: fp32 partials of a split launch (nt: with the non-temporal hint), else the 16-bit output of a single chunk
 template <typename T, int D>
 hipError_t launch_kvc(const KvcArgs& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
 #define TFA_KVC_UNITS(T, D) template <> hipError_t launch_kvc<T, D>(const KvcArgs&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
 TFA_KVC_UNITS(__bf16, 64) TFA_KVC_UNITS(__bf16, 128) TFA_KVC_UNITS(_Float16, 64) TFA_KVC_UNITS(_Float16, 128)
 #undef TFA_KVC_UNITS
-// ... and its e4m3 form (tfa_fwd_kvcache_fp8; fwd_kernel_dma_kvc8): tfa_kvc8_inst_<dtype>_<W>.hip, T the type of q and out
+// ... and its e4m3 form (tfa_fwd_kvcache_fp8; fwd_kernel_dma_kvc8): tfa_kvc8_inst_<dtype>_<W>, T the type of q and out
 template <typename T, int D>
 hipError_t launch_kvc8(const Kvc8Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
 #define TFA_KVC8_UNITS(T, D) template <> hipError_t launch_kvc8<T, D>(const Kvc8Args&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
 TFA_KVC8_UNITS(__bf16, 64) TFA_KVC8_UNITS(__bf16, 128) TFA_KVC8_UNITS(_Float16, 64) TFA_KVC8_UNITS(_Float16, 128)
 #undef TFA_KVC8_UNITS
 
-// The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32>.hip —
+// The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).
 template <typename T, int D, bool CAUSAL, bool F32OUT>
 hipError_t launch_x4_piece(const KArgs& a, int ablate, hipStream_t stream, LaunchGeom* geom, bool dry);
@@ -230,7 +220,7 @@ TFA_X4_PIECES(__bf16, 64) TFA_X4_PIECES(__bf16, 128) TFA_X4_PIECES(__bf16, 256)
 TFA_X4_PIECES(_Float16, 64) TFA_X4_PIECES(_Float16, 128) TFA_X4_PIECES(_Float16, 256)
 #undef TFA_X4_PIECES
 // the 256-wide x4 kernel with fewer than eight valid 32-column blocks (head dims 136..224): one unit per (dtype, causal, output type,
-// block count) — tfa_x4_inst_<dtype>_256_c<0|1>_o<16|32>_v<5|6|7>.hip
+// block count) — tfa_x4_inst_<dtype>_256_c<0|1>_o<16|32>_v<5|6|7>
 template <typename T, bool CAUSAL, bool F32OUT, int DVB>
 hipError_t launch_x4_wide(const KArgs& a, hipStream_t stream, LaunchGeom* geom, bool dry);
 

@@ -131,6 +131,20 @@ def _alibi_window(win, is_causal):
     return win if win is not None else ((-1, 0) if is_causal else (-1, -1))
 
 
+def _call_form(base, p, stream, win, alibi, cap, is_causal):
+    """Calls the entry point of one attention form on the parameter block p: ``base`` (tfa_fwd, tfa_fwd_varlen, tfa_bwd, tfa_bwd_varlen) with the suffix and the
+    extra arguments of the checked softcap / slopes / window — _softcap before _alibi before _local, else ``base`` itself."""
+    if cap:
+        suffix, extra = "_softcap", (cap, *_slopes_arg(alibi), *_alibi_window(win, is_causal))
+    elif alibi is not None:
+        suffix, extra = "_alibi", (alibi[0].data_ptr(), alibi[1], *_alibi_window(win, is_causal))
+    elif win is not None:
+        suffix, extra = "_local", (win[0], win[1])
+    else:
+        suffix, extra = "", ()
+    _lib.check(getattr(_lib.lib(), base + suffix)(C.byref(p), *extra, C.c_void_p(stream)))
+
+
 def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd", out_f32=False,
                    return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), softcap=0.0,
                    alibi_slopes=None):
@@ -217,22 +231,14 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None and not cap) else 1
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if cap:
-            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
-            _lib.check(L.tfa_fwd_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
-        elif alibi is not None:
-            aw = _alibi_window(win, is_causal)
-            _lib.check(L.tfa_fwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
-        elif win is not None:
-            _lib.check(L.tfa_fwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
-        elif splits > 1:
+        if splits > 1:
             need = L.tfa_fwd_splitkv_workspace(C.byref(p), int(splits))
             if need < 0:
                 _lib.check(int(need))
             ws = torch.empty((int(need),), dtype=torch.float32, device=q.device)
             _lib.check(L.tfa_fwd_splitkv(C.byref(p), int(splits), ws.data_ptr(), C.c_void_p(stream)))
         else:
-            _lib.check(L.tfa_fwd(C.byref(p), C.c_void_p(stream)))
+            _call_form("tfa_fwd", p, stream, win, alibi, cap, is_causal)
     return out, lse
 
 
@@ -392,16 +398,7 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         p.workspace_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if cap:
-            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
-            _lib.check(_lib.lib().tfa_bwd_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
-        elif alibi is not None:
-            aw = _alibi_window(win, is_causal)
-            _lib.check(_lib.lib().tfa_bwd_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
-        elif win is not None:
-            _lib.check(_lib.lib().tfa_bwd_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
-        else:
-            _lib.check(_lib.lib().tfa_bwd(C.byref(p), C.c_void_p(stream)))
+        _call_form("tfa_bwd", p, stream, win, alibi, cap, is_causal)
     return dq, dk, dv
 
 
@@ -591,16 +588,7 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if cap:
-            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
-            _lib.check(_lib.lib().tfa_fwd_varlen_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
-        elif alibi is not None:
-            aw = _alibi_window(win, is_causal)
-            _lib.check(_lib.lib().tfa_fwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
-        elif win is not None:
-            _lib.check(_lib.lib().tfa_fwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
-        else:
-            _lib.check(_lib.lib().tfa_fwd_varlen(C.byref(p), C.c_void_p(stream)))
+        _call_form("tfa_fwd_varlen", p, stream, win, alibi, cap, is_causal)
     return out, lse
 
 
@@ -647,16 +635,7 @@ def flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_seqlens_q, cu_seqlens_k, m
     p.grad_dtype = _lib.TFA_F32 if grad_f32 else _DT[q.dtype]
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if cap:
-            aw, (sp, sb) = _alibi_window(win, is_causal), _slopes_arg(alibi)
-            _lib.check(_lib.lib().tfa_bwd_varlen_softcap(C.byref(p), cap, sp, sb, aw[0], aw[1], C.c_void_p(stream)))
-        elif alibi is not None:
-            aw = _alibi_window(win, is_causal)
-            _lib.check(_lib.lib().tfa_bwd_varlen_alibi(C.byref(p), alibi[0].data_ptr(), alibi[1], aw[0], aw[1], C.c_void_p(stream)))
-        elif win is not None:
-            _lib.check(_lib.lib().tfa_bwd_varlen_local(C.byref(p), win[0], win[1], C.c_void_p(stream)))
-        else:
-            _lib.check(_lib.lib().tfa_bwd_varlen(C.byref(p), C.c_void_p(stream)))
+        _call_form("tfa_bwd_varlen", p, stream, win, alibi, cap, is_causal)
     return dq, dk, dv
 
 

@@ -5,11 +5,12 @@ set -e
 cd "$(dirname "$0")/../tiny-flash-attention_amd/csrc"
 NAME=$1; FLAGS=$2; UNITS=${UNITS:-"bf16_128_c0 bf16_128_c1"}
 mkdir -p ../build_$NAME ../lib_$NAME
-objs=$(ls ../build/*.o)
+objs=$(ls ../build/*.o); units=""
 for u in $UNITS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../../include -I. -Wno-unused-function -Wno-inline-asm -fno-gpu-rdc -mllvm -amdgpu-early-inline-all=true $FLAGS -c tfa_fwd_inst_$u.hip -o ../build_$NAME/tfa_fwd_inst_$u.o 2>/dev/null &
+  units="$units ../build_$NAME/tfa_fwd_inst_$u.o"
   objs=$(echo "$objs" | grep -v "tfa_fwd_inst_$u.o")
 done
-wait
+make -j8 EXTRA="$FLAGS" OBJDIR=../build_$NAME OUTDIR=../lib_$NAME $units 2>&1 | grep -E "error|FAILED" || true
+for u in $units; do [ -f $u ] || { echo "build of $NAME failed ($u)"; exit 1; }; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs ../build_$NAME/*.o -o ../lib_$NAME/libtfa_hip.so
 echo "built lib_$NAME"
