@@ -361,8 +361,9 @@ int tfa_fwd_work(const tfa_fwd_params* p, double* flops, double* bytes);
  * narrow twins at those head dims).
  * The backward runs its dQ launch (which also forms delta) and its fused dK/dV launch in varlen form.
  * Out of scope (refused): head dims above 128 (TFA_ERR_HEAD_DIM), fp32 inputs (TFA_ERR_DTYPE), TFA_FWD_EXACT_MAX and any other flag (flags must be 0:
- * TFA_ERR_SHAPE), split-KV, paged K/V, GQA decode row packing, the backward's dS-workspace form, dropout (sliding windows: tfa_fwd_varlen_local below), and sequences whose
- * max_seqlen rows would not fit one buffer descriptor (TFA_ERR_STRIDE: no windowed varlen form).  A NULL cu_seqlens is TFA_ERR_NULL;
+ * TFA_ERR_SHAPE), split-KV, GQA decode row packing, the backward's dS-workspace form, dropout (sliding windows: tfa_fwd_varlen_local below), and sequences whose
+ * max_seqlen rows would not fit one buffer descriptor (TFA_ERR_STRIDE: no windowed varlen form).  Paged K/V — the keys in a page pool behind a block table — is
+ * tfa_fwd_varlen_paged below.  A NULL cu_seqlens is TFA_ERR_NULL;
  * B, H, Hk, max_seqlen or total <= 0 or H % Hk != 0 is TFA_ERR_SHAPE.
  * Measured: profiles/varlen_bench.txt (tools/bench_varlen.py; equal lengths at the speed of tfa_fwd / tfa_bwd, mixed lengths against padding and
  * against one call per sequence), quoted in INTEGRATION.md. */
@@ -431,6 +432,43 @@ int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p);
 int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p);
 /* Launch the packed backward on `stream` (asynchronous): the dQ launch (it writes delta), then the fused dK/dV launch.  Deterministic. */
 int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream);
+
+/* ---- paged K/V for packed variable-length batches (FlashAttention-2's flash_attn_varlen_func(..., block_table=...): chunked prefill) ------------
+ * tfa_fwd_varlen with the keys in a page pool: q / out / lse / cu_seqlens_q as in tfa_fwd_varlen; p->k / p->v point at the pool (num_pages, page_size, Hk, D)
+ * with p->k_stride / v_stride = {head, row} as before and the page strides in *pg; p->total_k is ignored.  Sequence b has Nk_b = cu_seqlens_k[b+1] -
+ * cu_seqlens_k[b] keys (only the difference is used), clamped on the device into [0, min(max_seqlen_k, max_blocks * page_size)]; key j is row j % page_size
+ * of page block_table[b, j / page_size], the entry clamped into [0, num_pages) before use — a bad entry or length can misplace a read but never leaves the
+ * pool.  Nothing is read on the host: no copy, no synchronisation, capturable in a graph and replayable after lengths and table were overwritten in place.
+ * Causal masking per sequence, bottom-right aligned (shift = Nk_b - Nq_b): new tokens see the whole prefix and each other causally; rows that see no key get
+ * out = 0, lse = +inf; Nq_b = 0 and Nk_b = 0 are legal.  Whatever lies behind a sequence's length — the tail of its last page, unreferenced pages, stale keys,
+ * NaN — arrives as zeros: every 64-key tile has a descriptor of its own whose extent ends at the sequence's last key and at the valid head dim.
+ * Strides in elements, unit stride along D, 16-byte aligned rows and pages; page_size a positive multiple of 64 (the kernels' key tile); the pool may be of any
+ * size (2 GiB, 4 GiB and more: page bases are 64-bit pointer arithmetic), only 64 rows at the row stride must fit one descriptor (TFA_ERR_STRIDE otherwise).
+ * Kernels: the paged form of the kernel tfa_fwd_varlen would run (_variant: 30 or 32, the same answer; _plan: the same geometry), 128- or 256-row query blocks —
+ * built for prefill; decode-shaped batches (one row per sequence) are correct but waste the block: tfa_fwd_kvcache is the call for them.  Per-tile descriptors
+ * mean the compiler-scheduled tile bodies (as for slices beyond 2 GiB in tfa_fwd) and so TFA_RULE_LAZY for both types (_rounding_rule) — tfa_fwd_varlen on
+ * the same keys rounds bf16 by TFA_RULE_FIRST_TILE: the two agree within the bounds of "Rounding points", not in bits.
+ * Refused: a NULL pg or block_table (TFA_ERR_NULL); page_size not a positive multiple of 64, max_blocks or num_pages <= 0 (TFA_ERR_SHAPE); flags != 0
+ * (TFA_ERR_SHAPE); a table that is not 4-byte aligned (TFA_ERR_ALIGN); negative or misaligned table / page strides (TFA_ERR_STRIDE); and what tfa_fwd_varlen
+ * refuses (D > 128, fp32 inputs, a variant other than 30 / 32).
+ * Out of scope: a backward; paged K/V combined with windows, softcap or ALiBi; fp8 page pools; seqused_k; an append for packed new rows
+ * (tfa_kvcache_append serves one row count per batch); a hand-scheduled paged tile loop; D > 128.
+ * Measured: profiles/varlen_paged_bench.txt (tools/bench_varlen_paged.py), quoted in README.md and DESIGN.md 8g. */
+typedef struct tfa_paged_kv {
+  const int32_t* block_table;  /* device int32 (B, max_blocks), unit stride along max_blocks */
+  int64_t table_stride;        /* elements between the rows of block_table */
+  int32_t max_blocks;          /* entries per row */
+  int32_t page_size;           /* keys per page, a positive multiple of 64 */
+  int32_t num_pages;           /* pages in the pool */
+  int32_t reserved_;           /* must be 0 */
+  int64_t k_page_stride;       /* elements between the pages of k */
+  int64_t v_page_stride;
+} tfa_paged_kv;
+int tfa_fwd_varlen_paged(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg, void* stream);
+int tfa_fwd_varlen_paged_plan(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg, int* grid, int* block, int* lds_bytes);
+/* The kernel variant (30 or 32: tfa_fwd_varlen_variant's answer for *p) / the rounding rule (TFA_RULE_LAZY) of the paged call, or a negative TFA_ERR_* code. */
+int tfa_fwd_varlen_paged_variant(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg);
+int tfa_fwd_varlen_paged_rounding_rule(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg);
 
 /* ---- local (sliding-window) attention (FlashAttention-2's window_size = (left, right)) ---------------------------------------------------
  * The same params structs as tfa_fwd / tfa_bwd / tfa_fwd_varlen / tfa_bwd_varlen plus the window: with shift = Nk - Nq per sequence (bottom-right

@@ -44,6 +44,10 @@ SYMBOLS = (
     "tfa_fwd_varlen_variant",
     "tfa_fwd_varlen_rounding_rule",
     "tfa_bwd_varlen",
+    "tfa_fwd_varlen_paged",
+    "tfa_fwd_varlen_paged_plan",
+    "tfa_fwd_varlen_paged_variant",
+    "tfa_fwd_varlen_paged_rounding_rule",
     "tfa_fwd_local",
     "tfa_fwd_local_plan",
     "tfa_fwd_local_variant",
@@ -191,6 +195,21 @@ class TfaVarlenFwdParams(C.Structure):
         ("out_dtype", C.c_int32),
         ("flags", C.c_int32),
         ("reserved_", C.c_int32),
+    ]
+
+
+class TfaPagedKv(C.Structure):
+    """struct tfa_paged_kv (include/tfa.h): the page pool and block table of tfa_fwd_varlen_paged, handed over beside TfaVarlenFwdParams."""
+
+    _fields_ = [
+        ("block_table", C.c_void_p),
+        ("table_stride", C.c_int64),
+        ("max_blocks", C.c_int32),
+        ("page_size", C.c_int32),
+        ("num_pages", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("k_page_stride", C.c_int64),
+        ("v_page_stride", C.c_int64),
     ]
 
 
@@ -371,6 +390,12 @@ def lib():
     L.tfa_fwd_varlen_rounding_rule.argtypes = [PV]
     L.tfa_bwd_varlen.restype = C.c_int
     L.tfa_bwd_varlen.argtypes = [C.POINTER(TfaVarlenBwdParams), C.c_void_p]
+    PG = C.POINTER(TfaPagedKv)
+    for name, args in (("tfa_fwd_varlen_paged", [PV, PG, C.c_void_p]),
+                       ("tfa_fwd_varlen_paged_plan", [PV, PG, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+                       ("tfa_fwd_varlen_paged_variant", [PV, PG]), ("tfa_fwd_varlen_paged_rounding_rule", [PV, PG])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
     IP = C.POINTER(C.c_int)
     PF = C.POINTER(TfaFwdParams)
     PB = C.POINTER(TfaBwdParams)

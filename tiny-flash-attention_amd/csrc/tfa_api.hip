@@ -345,8 +345,10 @@ void fill_bhnd(tfa_fwd_params* p, const void* q, const void* k, const void* v, v
 //        its unbounded sides as -1 (set_window).  al->capped: the soft-capping form instead (tfa_fwd_softcap; al->slopes may then be null).
 // Kernel: il8 (30) where tfa_fwd would pick it, il4 (32) for everything else (the key-split kernels, split-KV and decode row packing have no such form); a
 // variant forced by tfa_set_variant must be one of the two.
+//   pg:  the page pool and block table of tfa_fwd_varlen_paged (checked by run_varlen), or nullptr: the paged form of the plain varlen kernels (vl set, no win, no al).
+//        f.Nk is then one tile's rows — what one descriptor has to hold — and the kernels' key limit is set here: the smaller of max_seqlen_k and a table row's capacity
 int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_varlen_fwd_params* vl, const int* win, const tfa::AlibiArg* al, void* stream,
-             tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
+             tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out, const tfa_paged_kv* pg = nullptr) {
   tfa_fwd_params f = f_in;
   int variant;
   if (win) {
@@ -372,15 +374,30 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     a.cu_q = vl->cu_seqlens_q; a.cu_k = vl->cu_seqlens_k;   // (KArgs: in the bytes of the split-KV fields, which the il kernels never read)
     a.total_q = vl->total_q; a.total_k = vl->total_k;       // (Nq / Nk = max_seqlen_q / _k, from validate())
   }
+  if (pg) {
+    // (KArgs: the paged arguments lie in bytes no varlen launch reads — tfa_fwd_kernel.h; behind validate(), which wrote k_bytes, v_bytes, big, grid and trace there)
+    const int64_t cap = (int64_t)pg->max_blocks * pg->page_size;
+    a.Nk = (int)(eq.Nk < cap ? eq.Nk : cap);
+    a.shift = 0;                                     // (per sequence on the device)
+    a.total_k = 0x7fffffff;                          // (varlen_seq: of cu_seqlens_k only the differences count, clamped into [0, Nk])
+    a.ks_b = pg->k_page_stride; a.vs_b = pg->v_page_stride;
+    a.pg_table_stride = pg->table_stride;
+    a.pg_tpp = pg->page_size / 64;
+    a.pg_fd_tpp = tfa::fastdiv_of((unsigned)a.pg_tpp);
+    a.pg_num_pages = pg->num_pages;
+    a.pg_max_blocks = pg->max_blocks;
+    a.block_table = pg->block_table;
+  }
   if (win) tfa::set_window(&a, win[0], win[1], f.Nq, f.Nk);   // (after the last read of a.big: the window shares its bytes)
   if (al) tfa::set_alibi(&a, *al);
   if (variant_out) *variant_out = variant;
-  if (rule_out) *rule_out = rounding_rule(variant, f.dtype, f.D, !win);   // (the local form is not the main instantiation)
+  if (rule_out) *rule_out = rounding_rule(variant, f.dtype, f.D, !win && !pg);   // (the local and paged forms are not the main instantiation)
   const bool causal = f.is_causal != 0, f32out = f.out_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return (int)tfa::by_dtype_width<64, 128>(f.dtype, f.D, [&](auto k) {
     using T = typename decltype(k)::T;
     constexpr int W = decltype(k)::W;
+    if (pg) return tfa::launch_fwd_form<T, W, tfa::FORM_VARLEN | tfa::FORM_PAGED>(a, causal, f32out, variant, s, geom, dry);
     return tfa::by_form(vl != nullptr, win != nullptr, al != nullptr, al && al->capped, [&](auto form) {
       return tfa::launch_fwd_form<T, W, decltype(form)::FORM>(a, causal, f32out, variant, s, geom, dry);
     });
@@ -413,15 +430,23 @@ int run_local(const tfa_fwd_params* p, const int* w, const tfa::AlibiArg* al, vo
 
 // Packed variable-length batches (include/tfa.h: tfa_fwd_varlen, tfa_fwd_varlen_local — w: the window, or nullptr).  The host knows the sequences' bounds only
 // as max_seqlen_q / _k; run_form runs the fixed-length problem of one sequence of that size B times.
+// pg: tfa_fwd_varlen_paged's page pool (no window, no slopes): k / v are the pool, total_k is ignored, and K / V are checked as ONE 64-key tile — all a descriptor
+// ever holds of them — so the pool may be of any size.
 int run_varlen(const tfa_varlen_fwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out,
-               int* rule_out) {
+               int* rule_out, const tfa_paged_kv* pg = nullptr, bool paged = false) {
   if (!p) return TFA_ERR_NULL;
+  if (paged && (!pg || !pg->block_table)) return TFA_ERR_NULL;
   if (!p->q || !p->k || !p->v || !p->out || !p->cu_seqlens_q || !p->cu_seqlens_k) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;             // (fp32 inputs: no varlen form)
   if (p->D < 8 || p->D > 128 || (p->D % 8) != 0) return TFA_ERR_HEAD_DIM;           // (the 256-wide kernel has no varlen form)
-  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || p->total_k <= 0) return TFA_ERR_SHAPE;
+  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->max_seqlen_q <= 0 || p->max_seqlen_k <= 0 || p->total_q <= 0 || (!pg && p->total_k <= 0)) return TFA_ERR_SHAPE;
   if (p->H % p->Hk != 0) return TFA_ERR_SHAPE;
   if (p->flags != 0 || p->reserved_ != 0) return TFA_ERR_SHAPE;                        // (TFA_FWD_EXACT_MAX: no varlen form)
+  if (pg) {
+    if (pg->page_size <= 0 || (pg->page_size % 64) != 0 || pg->max_blocks <= 0 || pg->num_pages <= 0 || pg->reserved_ != 0) return TFA_ERR_SHAPE;
+    if ((uintptr_t)pg->block_table & 3) return TFA_ERR_ALIGN;
+    if (pg->table_stride < 0 || pg->k_page_stride < 0 || pg->v_page_stride < 0 || (pg->k_page_stride * 2) % 16 != 0 || (pg->v_page_stride * 2) % 16 != 0) return TFA_ERR_STRIDE;
+  }
   int win[2] = {-1, -1}, form = p->is_causal ? tfa::WIN_CAUSAL : tfa::WIN_FULL;
   if (w) {
     win[0] = w[0];
@@ -436,14 +461,15 @@ int run_varlen(const tfa_varlen_fwd_params* p, const int* w, const tfa::AlibiArg
   tfa_fwd_params f;
   memset(&f, 0, sizeof(f));
   f.q = p->q; f.k = p->k; f.v = p->v; f.out = p->out; f.lse = p->lse;
-  f.B = 1; f.H = p->H; f.Hk = p->Hk; f.Nq = p->max_seqlen_q; f.Nk = p->max_seqlen_k; f.D = p->D;
+  f.B = 1; f.H = p->H; f.Hk = p->Hk; f.Nq = p->max_seqlen_q; f.Nk = pg ? 64 : p->max_seqlen_k; f.D = p->D;
   const int64_t* src[4] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride};
   int64_t* dst[4] = {f.q_stride, f.k_stride, f.v_stride, f.o_stride};
   for (int t = 0; t < 4; ++t) { dst[t][0] = 0; dst[t][1] = src[t][0]; dst[t][2] = src[t][1]; }
   f.softmax_scale = p->softmax_scale; f.is_causal = form == tfa::WIN_CAUSAL; f.dtype = p->dtype; f.out_dtype = p->out_dtype;
   tfa_fwd_params eq = f;
   eq.B = p->B;
-  return run_form(f, eq, p, (form == tfa::WIN_LOCAL || al) ? win : nullptr, al, stream, geom, dry, variant_out, rule_out);
+  eq.Nk = p->max_seqlen_k;
+  return run_form(f, eq, p, (form == tfa::WIN_LOCAL || al) ? win : nullptr, al, stream, geom, dry, variant_out, rule_out, pg);
 }
 
 // One forward call as an entry point names it: fixed-length (p) or packed variable-length (vp), with the {left, right} window of the _local entry points or
@@ -453,9 +479,11 @@ struct FwdCall {
   const tfa_varlen_fwd_params* vp;
   const int* win;
   const tfa::AlibiArg* alibi = nullptr;
+  const tfa_paged_kv* paged = nullptr;   // tfa_fwd_varlen_paged (is_paged: the entry point was a paged one — a NULL struct is then an error, not "not paged")
+  bool is_paged = false;
 };
 int route(const FwdCall& c, void* stream, tfa::LaunchGeom* geom = nullptr, bool dry = false, int* variant_out = nullptr, int* rule_out = nullptr) {
-  if (c.vp) return run_varlen(c.vp, c.win, c.alibi, stream, geom, dry, variant_out, rule_out);
+  if (c.vp || c.is_paged) return run_varlen(c.vp, c.win, c.alibi, stream, geom, dry, variant_out, rule_out, c.paged, c.is_paged);
   if (c.win) return run_local(c.p, c.win, c.alibi, stream, geom, dry, variant_out, rule_out);
   return run(c.p, stream, geom, dry, variant_out, rule_out);
 }
@@ -912,6 +940,13 @@ int tfa_fwd_varlen(const tfa_varlen_fwd_params* p, void* stream) { return route(
 int tfa_fwd_varlen_plan(const tfa_varlen_fwd_params* p, int* grid, int* block, int* lds_bytes) { return plan({nullptr, p, nullptr}, grid, block, lds_bytes); }
 int tfa_fwd_varlen_variant(const tfa_varlen_fwd_params* p) { return variant_or_rule({nullptr, p, nullptr}, false); }
 int tfa_fwd_varlen_rounding_rule(const tfa_varlen_fwd_params* p) { return variant_or_rule({nullptr, p, nullptr}, true); }
+
+int tfa_fwd_varlen_paged(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg, void* stream) { return route({nullptr, p, nullptr, nullptr, pg, true}, stream); }
+int tfa_fwd_varlen_paged_plan(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg, int* grid, int* block, int* lds_bytes) {
+  return plan({nullptr, p, nullptr, nullptr, pg, true}, grid, block, lds_bytes);
+}
+int tfa_fwd_varlen_paged_variant(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg) { return variant_or_rule({nullptr, p, nullptr, nullptr, pg, true}, false); }
+int tfa_fwd_varlen_paged_rounding_rule(const tfa_varlen_fwd_params* p, const tfa_paged_kv* pg) { return variant_or_rule({nullptr, p, nullptr, nullptr, pg, true}, true); }
 
 int tfa_fwd_local(const tfa_fwd_params* p, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};

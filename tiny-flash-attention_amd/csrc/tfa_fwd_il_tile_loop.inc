@@ -133,7 +133,7 @@
     // exists, needs no mask, has a whole K tile two ahead to request (j + 2 < nt_full) and no row has outgrown its reference; it returns the first tile it did not
     // process (either parity), S of that tile in sA / sB by parity, its half-wave row maximum in mx.  Everything else — masked and last tiles, re-bases,
     // odd entries — stays with the compiler-scheduled bodies below.
-    constexpr bool ASMBASE = (D == 128 || D == 64) && DVB == D / 32 && (AB & ~ILAB_TRACE) == 0 && !WIN && !(VF & VF_IL_IDLE) && !(VF & (VF_IL_DMASTAGGER | VF_IL_SEAM)) &&
+    constexpr bool ASMBASE = (D == 128 || D == 64) && DVB == D / 32 && (AB & ~ILAB_TRACE) == 0 && !WIN && !PAGED && !(VF & VF_IL_IDLE) && !(VF & (VF_IL_DMASTAGGER | VF_IL_SEAM)) &&
                              (PPW == 1 || PPW == 2 || PPW == 4) && (!EXACT || (D == 128 && PPW == 2)) && TFA_IL_USE_ASMLOOP && !SMOD;   // (the statement carries no bias and no cap)
     constexpr bool ASMLOOP = ASMBASE && !EXACT;        // the lazy-reference loop
     constexpr bool ASMLOOPX = ASMBASE && EXACT;        // the exact-running-max loop (variant 38): four bodies — parity x {plain, also re-basing O}

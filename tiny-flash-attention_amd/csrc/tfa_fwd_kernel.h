@@ -90,10 +90,17 @@ struct KArgs {
                     // of alignment padding in front of qs_b: no other field moves and the struct keeps its size (asserted below), so every existing kernel keeps
                     // its argument layout; only the softcap instantiations read it, and the host writes it for them alone (set_softcap)
   long long qs_b, qs_h, qs_n;
+  // (paged varlen — tfa_fwd_varlen_paged, the VF_IL_PAGED instantiations of fwd_kernel_il: k / v are a page pool and a sequence's keys come through a block
+  //  table.  Its arguments lie in bytes no varlen launch reads, so that every existing kernel keeps its argument layout: ks_b / vs_b are the PAGE strides (a varlen
+  //  launch has no batch stride), k_bytes / v_bytes — the varlen kernels form their K / V extents from the sequence's length — carry the table's row stride and the
+  //  magic divisor of t / pg_tpp, and the window, `grid` and `trace` unions below the rest.  The host writes them behind validate(): tfa_api.hip, set_paged)
   long long ks_b, ks_h, ks_n;
   long long vs_b, vs_h, vs_n;
   long long os_b, os_h, os_n;
-  unsigned long long q_bytes, k_bytes, v_bytes, o_bytes;   // extent of one (b,h) slice in bytes.  Kernels use ONE descriptor per slice
+  unsigned long long q_bytes;
+  union { unsigned long long k_bytes; long long pg_table_stride; };
+  union { unsigned long long v_bytes; FastDiv pg_fd_tpp; };
+  unsigned long long o_bytes;   // extent of one (b,h) slice in bytes.  Kernels use ONE descriptor per slice
                     // (< 2 GiB); the il kernels also exist in a WINDOWED instantiation (VF_IL_WINDOWED: rsrc_at, one query
                     // block / one K/V tile per descriptor) that tfa_api.hip launches when a slice is larger
   // (the local-attention window shares its bytes with `big` and `row_mod` — the host reads `big` before it fills the window, and only the idle-wave
@@ -107,6 +114,9 @@ struct KArgs {
     struct {
       int win_left, win_right;   // local: key j is visible to row i iff i + shift - win_left <= j <= i + shift + win_right (both >= 0, clamped by the host)
     };
+    struct {
+      int pg_tpp, pg_num_pages;  // paged varlen: 64-key tiles per page; pages in the pool — block-table entries are clamped into [0, pg_num_pages)
+    };
   };
   float scale;      // softmax_scale
   float scale_log2; // softmax_scale * log2(e)
@@ -116,10 +126,12 @@ struct KArgs {
   union {
     int grid;       // workgroups launched (persistent kernels walk work items with this stride)
     int slopes_bs;  // ALiBi: slopes[b * slopes_bs + h] — 0: one row of H slopes shared by the batch, else H
+    int pg_max_blocks;   // paged varlen: entries per row of the block table (the index of every table load is clamped below it)
   };
   union {
     unsigned long long* trace;  // debug: 8 x u64 per workgroup (cycle stamps), or nullptr
     const float* slopes;        // ALiBi: one fp32 slope per (batch entry / sequence, query head) in device memory, read by the work item; never by the host
+    const int* block_table;     // paged varlen (see pg_* above): device int32 (B, max_blocks) by pg_table_stride, read by the work items; never by the host
   };
   int dv;           // valid head dim (<= the kernel's compile-time D, a multiple of 8): the 16-byte chunks of a row beyond dv are
                     // read as zeros (their LDS-DMA lanes / Q loads are pointed outside the buffer) and never stored
@@ -137,6 +149,7 @@ struct KArgs {
                     // kernels whose K/V tiles no other workgroup reads may stream them with the non-temporal hint (set by the host)
 };
 static_assert(offsetof(KArgs, softcap_cr) == 100 && offsetof(KArgs, qs_b) == 104 && sizeof(KArgs) == 328, "KArgs::softcap_cr lies in former padding: no field moves");
+static_assert(offsetof(KArgs, k_bytes) == 208 && offsetof(KArgs, v_bytes) == 216 && offsetof(KArgs, o_bytes) == 224, "KArgs: the paged varlen arguments share bytes: no field moves");
 
 // One sequence of a packed variable-length batch, read on the device (scalar loads: b is uniform) — the host never reads cu_seqlens.  The bounds are clamped
 // into the packed tensors and the lengths to the host's max_seqlen (the arguments' Nq / Nk), so a bad cu_seqlens can misplace rows but never address outside

@@ -85,6 +85,12 @@ constexpr int VF_IL_SOFTCAP = 512;       // soft-capping (tfa_fwd_softcap): S[i,
                                          // per score), where apply_bias runs and in front of it; mask, row maximum, lazy reference, trigger and LSE work on the capped scores.
                                          // With KArgs::slopes != nullptr the ALiBi bias follows the cap — one launch-uniform scalar branch per tile, so that a call without slopes
                                          // does not pay the bias arithmetic and a second set of instantiations is not needed.  (Bit: the VF_VPRE field again)
+constexpr int VF_IL_PAGED = 128;         // paged K/V of a packed variable-length batch (tfa_fwd_varlen_paged), a form of the VARLEN instantiations: k / v are a page pool, key j of
+                                         // sequence b is row j % page_size of page block_table[b, j / page_size].  Every 64-key tile comes through a descriptor of its own (a tile
+                                         // never straddles pages): based at the tile's first row inside its page, ending at the sequence's last key and the valid width — what lies
+                                         // behind (the page's tail, stale keys, NaN) reads as zeros.  The entries of three consecutive pages are kept in scalars, loaded once per
+                                         // page, the third a tile of compute ahead of its first use (page_of below).  One descriptor per tile: the compiler-scheduled tile bodies
+                                         // only, as in the WINDOWED instantiations, and so the lazily re-based row reference for both types.  (Bit: VF_SWP of another kernel)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -285,6 +291,11 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   constexpr bool VARLEN = (VF & VF_IL_VARLEN) != 0;
   static_assert(!VARLEN || (!(VF & (VF_IL_KSPLIT | VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_EXACT | VF_IL_SEAM | VF_IL_PREF)) && !TFA_IL_USE_EARLY),
                 "varlen: the il8 / il4 main instantiations only");
+  // PAGED: the sequence's keys are its block-table row's pages; of cu_k only the difference counts (the host sets total_k = INT_MAX and Nk = the smaller of
+  // max_seqlen_k and the table row's capacity: varlen_seq's clamps then give nk in [0, Nk] and its k0 is not used)
+  constexpr bool PAGED = (VF & VF_IL_PAGED) != 0;
+  static_assert(!PAGED || (VARLEN && !(VF & (VF_IL_LOCAL | VF_IL_ALIBI | VF_IL_SOFTCAP)) && !(AB & ILAB_TRACE)),
+                "paged: a form of the plain varlen instantiations; KArgs::block_table shares the bytes of trace — no traced twin");
   VarSeq vsq{};
   if constexpr (VARLEN) {
     vsq = varlen_seq(p, b);
@@ -334,8 +345,8 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   }
 
   const T* qbase = reinterpret_cast<const T*>(p.q) + (VARLEN ? (long long)vsq.q0 * p.qs_n : b * p.qs_b) + h * p.qs_h;
-  const T* kbase = reinterpret_cast<const T*>(p.k) + (VARLEN ? (long long)vsq.k0 * p.ks_n : b * p.ks_b) + hk * p.ks_h;
-  const T* vbase = reinterpret_cast<const T*>(p.v) + (VARLEN ? (long long)vsq.k0 * p.vs_n : b * p.vs_b) + hk * p.vs_h;
+  const T* kbase = reinterpret_cast<const T*>(p.k) + (PAGED ? 0ll : VARLEN ? (long long)vsq.k0 * p.ks_n : b * p.ks_b) + hk * p.ks_h;   // (PAGED: the K/V head inside page 0)
+  const T* vbase = reinterpret_cast<const T*>(p.v) + (PAGED ? 0ll : VARLEN ? (long long)vsq.k0 * p.vs_n : b * p.vs_b) + hk * p.vs_h;
   // Q/O: one descriptor per query block (rsrc_at, once per pass).  K/V: one per slice, or — VF_IL_WINDOWED — one per tile.
   constexpr bool WIN = (VF & VF_IL_WINDOWED) != 0;
   // KSPLIT: group g sees the key sequence through a strided view — its tile j is tile 2j+g of the head
@@ -359,8 +370,8 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
     if constexpr (WIN) return rsrc_at(base, bytes, off);
     else return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (unsigned)bytes, 0x00020000);
   };
-  auto k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, WIN ? 0u : (unsigned)k_bytes, 0x00020000);
-  auto v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, WIN ? 0u : (unsigned)v_bytes, 0x00020000);
+  auto k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, (WIN || PAGED) ? 0u : (unsigned)k_bytes, 0x00020000);
+  auto v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, (WIN || PAGED) ? 0u : (unsigned)v_bytes, 0x00020000);
 
   int k_src[PPW], v_src[PPW];
 #pragma unroll
@@ -387,12 +398,57 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   //  cache can keep until the next decode step — the host sets KArgs::kv_stream from 768 MiB on: profiles/r03_decode_nt_ab.txt)
   TP_STAMP(2, (int)(size_t)qbase + (int)(size_t)kbase + (int)(size_t)vbase);   // base pointers
   const bool kv_private = p.H == p.Hk && p.kv_stream != 0;
+  // PAGED: the block-table entries of pages pg_idx, pg_idx + 1, pg_idx + 2 of this sequence, as loaded (clamped into the pool where they are used, so that a load's
+  // wait sits at its first use).  The tile streams ascend and K runs one tile ahead of V: the V stream moves the window on when it enters page pg_idx + 1 and asks
+  // for page pg_idx + 3's entry there — a page the K stream reaches a tile later at the earliest (pages of one tile), so no tile's first DMA waits on the chain
+  // table -> descriptor -> DMA, and every entry is loaded once per page and pass.  A request outside the window (a pass's first tile) reloads all three.
+  int pg_idx = -4, pg_e0 = 0, pg_e1 = 0, pg_e2 = 0;
+  auto pg_load = [&](int pidx) -> int {                // entry pidx of the sequence's table row; the index clamped into the row
+    typedef __attribute__((address_space(4))) const int cint4;
+    const int mx = p.pg_max_blocks - 1;
+    const int ix = pidx < mx ? pidx : mx;
+    return ((const cint4*)(uintptr_t)p.block_table)[(long long)b * p.pg_table_stride + (ix > 0 ? ix : 0)];
+  };
+  auto page_of = [&](int pidx, bool advance) -> int {
+    if ((unsigned)(pidx - pg_idx) > 2u) {
+      pg_idx = pidx;
+      pg_e0 = pg_load(pidx); pg_e1 = pg_load(pidx + 1); pg_e2 = pg_load(pidx + 2);
+    } else if (advance && pidx == pg_idx + 1) {
+      pg_idx = pidx;
+      pg_e0 = pg_e1; pg_e1 = pg_e2; pg_e2 = pg_load(pidx + 2);
+    }
+    const int d = pidx - pg_idx;
+    const int e0 = pg_e0, e1 = pg_e1, e2 = pg_e2;      // (values first: a choice between the variables themselves is a choice between addresses, and they leave their registers)
+    int e = d == 1 ? e1 : e0;
+    e = d == 2 ? e2 : e;
+    return e < 0 ? 0 : (e >= p.pg_num_pages ? p.pg_num_pages - 1 : e);   // (a bad entry can misplace a read, never leave the pool)
+  };
+  // the descriptor of tile t of this sequence in the pool `base` (the K/V head inside page 0): from the tile's first row inside its page to the last valid key of
+  // the tile at the valid width.  64-bit pointer arithmetic: the pool may be of any size
+  auto paged_rsrc = [&](const T* base, long long page_stride, long long row_stride, int t, bool advance) {
+    const int pidx = fd_div(t, p.pg_fd_tpp);
+    const long long page = page_of(pidx, advance);
+    const int row0 = (t - pidx * p.pg_tpp) * BN;
+    int rows = IL_NK - t * BN;
+    rows = rows > BN ? BN : rows;
+    const unsigned bytes = rows > 0 ? (unsigned)(((long long)(rows - 1) * row_stride + p.dv) * 2) : 0u;
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + page * page_stride + (long long)row0 * row_stride), 0, bytes, 0x00020000);
+  };
+  __amdgpu_buffer_rsrc_t k_rs_t = k_rs, v_rs_t = v_rs;  // PAGED: the descriptor of the tile whose pieces are being issued (formed with its first piece)
   auto dma_k1 = [&](int t, int buf, int i) {
+    if constexpr (PAGED) {
+      if (i == 0) k_rs_t = paged_rsrc(kbase, p.ks_b, p.ks_n, t, false);
+      lds_dma16_m0_fresh(k_rs_t, lds_base + buf * TILE_BYTES + (wave * PPW + i) * 1024, k_src[i]);
+    } else
     if constexpr (WIN) lds_dma16_m0_fresh(rsrc_at(kbase, k_bytes, (unsigned long long)t * (unsigned)k_tile_stride), lds_base + buf * TILE_BYTES + (wave * PPW + i) * 1024, k_src[i]);
     else if ((VF & VF_IL_IDLE) && IL_DECODE_NT && kv_private) lds_dma16_m0_nt(k_rs, lds_base + buf * TILE_BYTES + (wave * PPW + i) * 1024, k_src[i] + t * k_tile_stride);
     else lds_dma16_m0(k_rs, lds_base + buf * TILE_BYTES + (wave * PPW + i) * 1024, k_src[i] + t * k_tile_stride);
   };
   auto dma_v1 = [&](int t, int buf, int i) {
+    if constexpr (PAGED) {
+      if (i == 0) v_rs_t = paged_rsrc(vbase, p.vs_b, p.vs_n, t, true);
+      lds_dma16_m0_fresh(v_rs_t, lds_base + (2 + buf) * TILE_BYTES + (wave * PPW + i) * 1024, v_src[i]);
+    } else
     if constexpr (WIN) lds_dma16_m0_fresh(rsrc_at(vbase, v_bytes, (unsigned long long)t * (unsigned)v_tile_stride), lds_base + (2 + buf) * TILE_BYTES + (wave * PPW + i) * 1024, v_src[i]);
     else if ((VF & VF_IL_IDLE) && IL_DECODE_NT && kv_private) lds_dma16_m0_nt(v_rs, lds_base + (2 + buf) * TILE_BYTES + (wave * PPW + i) * 1024, v_src[i] + t * v_tile_stride);
     else lds_dma16_m0(v_rs, lds_base + (2 + buf) * TILE_BYTES + (wave * PPW + i) * 1024, v_src[i] + t * v_tile_stride);
@@ -435,7 +491,7 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   // correct, and no second rule in the tile bodies (a max-tracking twin of every body beside the max-free one made hipcc spill 90 registers).
   // Stated domain: |v| * Nk < 2^63.  fp16 keeps the maximum (its P overflows at 2^16).  oracle/oracle.py: tiled_emulation_first_tile restates the rule.
   constexpr bool MAXFREE_BASE = std::is_same<T, __bf16>::value && !EXACT && !LOCAL && TFA_IL_USE_MAXFREE && TFA_IL_USE_ASMLOOP && (D == 128 || D == 64) && DVB == D / 32 &&
-                                (AB & ~ILAB_TRACE) == 0 && !(VF & (VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_DMASTAGGER | VF_IL_SEAM)) && (PPW == 1 || PPW == 2 || PPW == 4);
+                                (AB & ~ILAB_TRACE) == 0 && !(VF & (VF_IL_WINDOWED | VF_IL_IDLE | VF_IL_DMASTAGGER | VF_IL_SEAM | VF_IL_PAGED)) && (PPW == 1 || PPW == 2 || PPW == 4);
   constexpr bool MAXFREE = MAXFREE_BASE;
   static_assert(!MAXFREE || !((VF & VF_IL_PREF) && !(VF & VF_IL_PREF2)), "max-free: a redone pass re-issues its own first requests (PREF2 or no prefetch)");
   // behind everything else in LDS: one word "some row of this block needs the pass redone", then one float per query row of the block (the seeds of a redone pass)

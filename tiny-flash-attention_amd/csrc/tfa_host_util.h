@@ -54,17 +54,21 @@ static inline auto by_dtype_width(int dtype, int D, F&& f) {
 
 // The form of an il8 / il4 forward or backward dQ / dK/dV launch beyond the plain fixed-length one: a mask of these bits, a template argument of launch_fwd_form
 // and launch_bwd_form.  The ALiBi and softcap kernels are forms of the local ones; softcap's slopes are a run-time choice of its one kernel (no ALIBI bit);
-// the local kernels exist as the causal template only (the window carries the right edge).
-enum : int { FORM_VARLEN = 1, FORM_LOCAL = 2, FORM_ALIBI = 4, FORM_SOFTCAP = 8 };
+// the local kernels exist as the causal template only (the window carries the right edge).  FORM_PAGED (tfa_fwd_varlen_paged: K/V through a block table) is a
+// form of the plain varlen forward alone: no window, no slopes, no cap, no backward.
+enum : int { FORM_VARLEN = 1, FORM_LOCAL = 2, FORM_ALIBI = 4, FORM_SOFTCAP = 8, FORM_PAGED = 16 };
 constexpr bool form_legal(int form, bool causal = true) {
-  return form > 0 && form < 16 && ((form & FORM_LOCAL) ? causal : !(form & (FORM_ALIBI | FORM_SOFTCAP))) && !((form & FORM_ALIBI) && (form & FORM_SOFTCAP));
+  return form > 0 && form < 32 && ((form & FORM_LOCAL) ? causal : !(form & (FORM_ALIBI | FORM_SOFTCAP))) && !((form & FORM_ALIBI) && (form & FORM_SOFTCAP)) &&
+         (!(form & FORM_PAGED) || form == (FORM_VARLEN | FORM_PAGED));
 }
 // THE list of the legal forms, X(mask): each is one instantiation unit per (dtype, width) of the forward (tfa_fwd_inst_<varlen|local|alibi|softcap>_...) and of
 // the backward (tfa_bwd_inst_...), fixed-length (_fx) or varlen (_vl) — the Makefile's words of those names carry the same masks.  The declarations of tfa_launch.h
-// and tfa_bwd_launch.h and by_form's switch come from here
-#define TFA_FORMS(X)                                                                                                        \
+// and tfa_bwd_launch.h and by_form's switch come from here.  TFA_FORMS_BWD: the forms that have a backward (by_form's, which both directions share);
+// TFA_FORMS: every form — those and the forward-only paged varlen form (units tfa_fwd_inst_paged_..., reached by run_form without by_form)
+#define TFA_FORMS_BWD(X)                                                                                                    \
   X(FORM_VARLEN) X(FORM_LOCAL) X(FORM_LOCAL | FORM_VARLEN) X(FORM_LOCAL | FORM_ALIBI) X(FORM_LOCAL | FORM_ALIBI | FORM_VARLEN) \
   X(FORM_LOCAL | FORM_SOFTCAP) X(FORM_LOCAL | FORM_SOFTCAP | FORM_VARLEN)
+#define TFA_FORMS(X) TFA_FORMS_BWD(X) X(FORM_VARLEN | FORM_PAGED)
 // ... and the (dtype, width) pairs each of them is built for: X(T, D, ...)
 #define TFA_FORM_SHAPES(X, ...) X(__bf16, 64, __VA_ARGS__) X(__bf16, 128, __VA_ARGS__) X(_Float16, 64, __VA_ARGS__) X(_Float16, 128, __VA_ARGS__)
 template <int FORM_>
@@ -78,7 +82,7 @@ static inline auto by_form(bool varlen, bool local, bool alibi, bool capped, F&&
   const int form = !local ? FORM_VARLEN : FORM_LOCAL | (varlen ? FORM_VARLEN : 0) | (capped ? FORM_SOFTCAP : alibi ? FORM_ALIBI : 0);
 #define TFA_BY_FORM(mask) \
   if (form == (mask)) return f(Form<(mask)>{});
-  TFA_FORMS(TFA_BY_FORM)
+  TFA_FORMS_BWD(TFA_BY_FORM)
 #undef TFA_BY_FORM
   return f(Form<FORM_VARLEN>{});   // (never: the line above names every value `form` takes)
 }

@@ -130,13 +130,13 @@ static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, in
   return causal ? launch_fwd_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
 // the forms of variants 30 and 32 (tfa_host_util.h: TFA_FORMS — packed variable-length, local, and the local kernels' ALiBi and softcap forms): one translation
-// unit per (dtype, width, form) — the local forms as the CAUSAL template only (units tfa_fwd_inst_<local|alibi|softcap>_<dtype>_<D>_<fx|vl>), plain varlen per
-// causal too (units tfa_fwd_inst_varlen_<dtype>_<D>_c<0|1>) — each specialising launch_fwd_form_c (tfa_fwd_form_inst.inc)
+// unit per (dtype, width, form) — the local forms as the CAUSAL template only (units tfa_fwd_inst_<local|alibi|softcap>_<dtype>_<D>_<fx|vl>), plain varlen and its paged form per
+// causal too (units tfa_fwd_inst_<varlen|paged>_<dtype>_<D>_c<0|1>) — each specialising launch_fwd_form_c (tfa_fwd_form_inst.inc)
 template <typename T, int D, int FORM, bool CAUSAL>
 hipError_t launch_fwd_form_c(const KArgs& a, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry);
 #define TFA_FWD_FORM_UNIT(T, D, FORM, CAUSAL) template <> hipError_t launch_fwd_form_c<T, D, (FORM), CAUSAL>(const KArgs&, bool, int, hipStream_t, LaunchGeom*, bool);
 #define TFA_FWD_FORM_UNITS(FORM) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM, true)
-TFA_FORMS(TFA_FWD_FORM_UNITS) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM_VARLEN, false)
+TFA_FORMS(TFA_FWD_FORM_UNITS) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM_VARLEN, false) TFA_FORM_SHAPES(TFA_FWD_FORM_UNIT, FORM_VARLEN | FORM_PAGED, false)
 #undef TFA_FWD_FORM_UNITS
 #undef TFA_FWD_FORM_UNIT
 template <typename T, int D, int FORM>

@@ -544,25 +544,100 @@ def _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_
     return cu_seqlens_q.numel() - 1
 
 
+def _check_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table, window_size, is_causal, softcap, alibi_slopes):
+    """Host-side checks of a packed call over a page pool (``block_table`` given): everything that needs no device read, refused by name before any library call."""
+    name = "flash_attn_varlen_func(block_table=...)"
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise RuntimeError("q must be a 3-D tensor (total rows, heads, head dim)")
+    for t, n in ((k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be the 4-D page pool (num_pages, page_size, Hk, D)")
+    if q.dtype == torch.float32:
+        raise TypeError("packed variable-length attention: float16 or bfloat16 only (no fp32 varlen path)")
+    if q.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
+    fp8s = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+    if k.dtype in fp8s or v.dtype in fp8s:
+        raise TypeError(f"{name}: fp8 page pools are not supported (got {k.dtype}, {v.dtype}); flash_attn_with_kvcache reads an fp8 cache")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"{name}: k and v must have q's dtype {q.dtype} (got {k.dtype}, {v.dtype})")
+    total_q, H, D = q.shape
+    if D > 128:
+        raise ValueError(f"{name}: head dims up to 128 (got {D})")
+    if D % 8 != 0 or D < 8:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
+    if k.shape != v.shape or k.shape[3] != D:
+        raise ValueError(f"{name}: k and v must have one shape (num_pages, page_size, Hk, {D}) (got {tuple(k.shape)}, {tuple(v.shape)})")
+    num_pages, page_size, Hk, _ = k.shape
+    if num_pages <= 0 or page_size <= 0 or page_size % 64 != 0:
+        raise ValueError(f"{name}: the page size must be a positive multiple of 64 and the pool hold a page (got {page_size}, {num_pages} pages)")
+    if Hk <= 0 or H % Hk != 0:
+        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if t.stride(-1) != 1:
+            raise ValueError(f"{name}: {n} must have unit stride along the head dim")
+    for t, n in ((cu_seqlens_q, "cu_seqlens_q"), (cu_seqlens_k, "cu_seqlens_k")):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{n} must be a tensor")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{n} must be int32 (got {t.dtype})")
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() < 2:
+            raise RuntimeError(f"{n} must be a contiguous 1-D tensor of B + 1 >= 2 entries")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+        raise RuntimeError(f"cu_seqlens_q and cu_seqlens_k must both hold B + 1 entries ({cu_seqlens_q.numel()} vs {cu_seqlens_k.numel()})")
+    B = cu_seqlens_q.numel() - 1
+    for m, n in ((max_seqlen_q, "max_seqlen_q"), (max_seqlen_k, "max_seqlen_k")):
+        if isinstance(m, torch.Tensor) or isinstance(m, bool) or int(m) != m or int(m) <= 0:
+            raise RuntimeError(f"{n} must be a positive host integer (got {m!r})")
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1:
+        raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks)")
+    if block_table.device != q.device or block_table.stride(1) != 1:
+        raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (cu_seqlens_q, "cu_seqlens_q"), (cu_seqlens_k, "cu_seqlens_k")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+        if t.device != q.device:
+            raise RuntimeError(f"{n} must be on q's device")
+    # the combinations that are a follow-up: a true window, a cap, slopes ((-1, -1) and (-1, 0) windows are full / causal attention as everywhere)
+    win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D,
+                  extra=((True, "sliding windows are not implemented over a page pool (block_table)"),))
+    if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
+        raise ValueError(f"{name}: softcap is not implemented over a page pool (block_table)")
+    if alibi_slopes is not None:
+        raise ValueError(f"{name}: alibi_slopes is not implemented over a page pool (block_table)")
+    return B, (True if win == (-1, 0) else bool(is_causal))
+
+
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=False, softmax_scale=None, *,
-                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
+                          out_f32=False, return_lse=True, out=None, window_size=(-1, -1), block_table=None, softcap=0.0, alibi_slopes=None):
     """Packed variable-length forward (tfa_fwd_varlen, include/tfa.h): q (total_q, H, D), k / v (total_k, Hk, D), sequence b is rows
     [cu_seqlens_q[b], cu_seqlens_q[b+1]) of q and [cu_seqlens_k[b], cu_seqlens_k[b+1]) of k, v (device int32, B + 1 entries, never read on the host).
     Causal masking per sequence, bottom-right aligned.  Returns ``(out, lse)``: ``out`` shaped like q (fp32 when ``out_f32``), ``lse`` fp32 (H, total_q).
     Rows outside every sequence are not written (a caller-provided ``out`` keeps them).  ``window_size``: FlashAttention-2's sliding window per
     sequence (tfa_fwd_varlen_local).  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H) with B the number of sequences; the distance is taken per sequence
-    (tfa_fwd_varlen_alibi).  ``softcap``: tanh logit capping of the scaled scores before the bias and the mask, 0.0 = none (tfa_fwd_varlen_softcap)."""
-    _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
-    B = cu_seqlens_q.numel() - 1
-    total_q, H, D = q.shape
-    total_k, Hk, _ = k.shape
+    (tfa_fwd_varlen_alibi).  ``softcap``: tanh logit capping of the scaled scores before the bias and the mask, 0.0 = none (tfa_fwd_varlen_softcap).
+    ``block_table`` (keyword-only; tfa_fwd_varlen_paged): paged K/V — k / v are the page pool (num_pages, page_size, Hk, D), any page / row / head strides, page_size a
+    multiple of 64; ``block_table`` int32 (B, max_blocks) on the device; sequence b has cu_seqlens_k[b+1] - cu_seqlens_k[b] keys (only the difference is used), key j in
+    row j % page_size of page block_table[b, j // page_size].  Not with a true window, softcap or alibi_slopes (ValueError).  ``None``: the call above, unchanged."""
+    if block_table is not None:
+        B, is_causal = _check_varlen_paged(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, block_table, window_size, is_causal, softcap,
+                                           alibi_slopes)
+        total_q, H, D = q.shape
+        total_k, Hk = 0, k.shape[2]
+        win, alibi, cap = None, None, 0.0
+    else:
+        _check_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+        B = cu_seqlens_q.numel() - 1
+        total_q, H, D = q.shape
+        total_k, Hk, _ = k.shape
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
-    win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
-    if win == (-1, 0):
-        win, is_causal = None, True
-    alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
-    cap = _softcap(softcap, q.dtype, D)
+    if block_table is None:
+        win = _window(window_size, is_causal, int(max_seqlen_q), int(max_seqlen_k), q.dtype, D)
+        if win == (-1, 0):
+            win, is_causal = None, True
+        alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D)
+        cap = _softcap(softcap, q.dtype, D)
     if out is None:
         out = torch.empty(q.shape, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
     else:
@@ -579,13 +654,25 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max
     p.cu_seqlens_q, p.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
     p.B, p.H, p.Hk, p.D = B, H, Hk, D
     p.max_seqlen_q, p.max_seqlen_k, p.total_q, p.total_k = int(max_seqlen_q), int(max_seqlen_k), total_q, total_k
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
+    for name, t in (("q_stride", q), ("o_stride", out)) + ((("k_stride", k), ("v_stride", v)) if block_table is None else ()):
         arr = getattr(p, name)
         arr[0], arr[1] = t.stride(1), t.stride(0)
     p.softmax_scale = float(softmax_scale)
     p.is_causal = 1 if is_causal else 0
     p.dtype = _DT[q.dtype]
     p.out_dtype = _lib.TFA_F32 if out.dtype == torch.float32 else _DT[out.dtype]
+    if block_table is not None:
+        for name, t in (("k_stride", k), ("v_stride", v)):          # the pool (num_pages, page_size, Hk, D): head, row — the page strides go into pg
+            arr = getattr(p, name)
+            arr[0], arr[1] = t.stride(2), t.stride(1)
+        pg = _lib.TfaPagedKv()
+        pg.block_table, pg.table_stride, pg.max_blocks = block_table.data_ptr(), block_table.stride(0), block_table.shape[1]
+        pg.page_size, pg.num_pages = k.shape[1], k.shape[0]
+        pg.k_page_stride, pg.v_page_stride = k.stride(0), v.stride(0)
+        with torch.cuda.device(q.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().tfa_fwd_varlen_paged(C.byref(p), C.byref(pg), C.c_void_p(stream)))
+        return out, lse
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
         _call_form("tfa_fwd_varlen", p, stream, win, alibi, cap, is_causal)
@@ -663,17 +750,32 @@ class _FlashAttnVarlen(torch.autograd.Function):
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
-                           window_size=(-1, -1), *extra, softcap=0.0, alibi_slopes=None):
+                           window_size=(-1, -1), *extra, block_table=None, softcap=0.0, alibi_slopes=None):
     """Packed variable-length attention with FlashAttention-2's positional signature (flash_attn_varlen_func): q (total_q, H, D), k / v
     (total_k, Hk, D), cu_seqlens_q / _k device int32 (B + 1), max_seqlen_q / _k host integers.  Differentiable: when an input requires grad the
     backward runs tfa_bwd_varlen.  Dropout is not supported (``dropout_p`` must be 0).  ``window_size=(left, right)``: FlashAttention-2's sliding
     window per sequence, -1 = unbounded, ``causal`` forces right = 0.  ``alibi_slopes``: ALiBi, float32 (H,) or (B, H), B = the number of sequences.
     ``softcap``: tanh logit capping, a host float, 0.0 = none: cap on the scaled scores, then the bias, then the mask (tfa_fwd_varlen_softcap / tfa_bwd_varlen_softcap).
-    ``softcap`` is keyword-only; ``alibi_slopes`` stays the last parameter and may still be passed as the positional argument behind ``window_size``."""
+    ``softcap`` is keyword-only; ``alibi_slopes`` may still be passed as the positional argument behind ``window_size``.
+    ``block_table`` (keyword-only): paged K/V, FlashAttention-2's chunked prefill over a page pool — k / v are (num_pages, page_size, Hk, D) with page_size a
+    multiple of 64 (a (num_pages, Hk, page_size, D) pool works as a permuted view), ``block_table`` int32 (B, max_blocks) on the device; sequence b attends its
+    cu_seqlens_k[b+1] - cu_seqlens_k[b] keys (only the difference is used; clamped on the device to max_seqlen_k and to max_blocks * page_size), key j being row
+    j % page_size of page block_table[b, j // page_size] (entries clamped into the pool).  Neither the lengths nor the table are read on the host: no
+    synchronisation, capturable in a graph.  ``causal`` is bottom-right aligned per sequence — new tokens see the whole prefix and each other causally.  Whatever
+    the pool holds behind a sequence's length (page tails, unreferenced pages, NaN) never reaches a result.  Forward only: an input that requires grad raises
+    RuntimeError.  Not with a true ``window_size``, ``softcap`` or ``alibi_slopes`` (ValueError), nor fp8 pools (TypeError).  The path works on 128- / 256-row
+    query blocks: built for prefill; for decode-shaped batches (one new row per sequence) it is correct but ``flash_attn_with_kvcache`` is the call to use."""
     alibi_slopes = _positional_slopes(extra, alibi_slopes, "flash_attn_varlen_func")
     if dropout_p != 0.0:
         raise NotImplementedError("flash_attn_varlen_func: dropout is not supported (dropout_p must be 0)")
     window_size = tuple(window_size)
+    if block_table is not None:
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (q, k, v)):
+            raise RuntimeError("flash_attn_varlen_func(block_table=...) is not differentiable: an input requires grad (run it under torch.no_grad() or detach "
+                               "the inputs)")
+        out, _ = flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, return_lse=False,
+                                       window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap, block_table=block_table)
+        return out
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal), softmax_scale, window_size,
                                       softcap, alibi_slopes)
