@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -601,6 +601,52 @@ int tfa_bwd_varlen_softcap(const tfa_varlen_bwd_params* p, float softcap, const 
                            int window_right, void* stream);
 int tfa_bwd_varlen_softcap_plan(const tfa_varlen_bwd_params* p, float softcap, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left,
                                 int window_right);
+
+/* ---- Dense additive bias and masks (scaled_dot_product_attention's attn_mask; FlashAttention-2 has no such argument) ------------------------
+ * The same params structs as tfa_fwd / tfa_bwd plus a bias tensor and a window.  With bias broadcast to (B, H, Nq, Nk):
+ *     S[i,j] = softmax_scale * q_i . k_j  +  bias[b, h, i, j]
+ * then the mask (is_causal / the window, exactly as the _local entry points read them; (-1, -1) = none), the softmax and P V.  h is the QUERY head (GQA: the
+ * H / Hk query heads of a K/V head have their own slices).  Everything downstream is defined on these biased scores: lse is the true logsumexp_j S[i,j]
+ * INCLUDING the bias (tfa_bwd_bias and tfa_merge consume it); an entry of -inf masks its (i, j); a row without a finite score gets out = 0 and lse = +inf,
+ * as everywhere else.  +inf and NaN in the bias are undefined (unspecified results, never an access outside the tensors).  The backward recomputes P from
+ * the same biased scores and returns dq, dk, dv; the bias gets NO gradient.
+ * tfa_attn_bias: `bias` points at element [0, 0, 0, 0] in DEVICE memory, dtype TFA_F32 or the dtype of q; stride[] counts ELEMENTS between batch entries,
+ * query heads and query rows, 0 = that dimension is broadcast; the keys of a row are contiguous (unit stride).  The kernels' work items read the tensor
+ * themselves — 8-byte (16-bit bias) or 16-byte (fp32) loads of four consecutive keys through one buffer descriptor per (b, h) slice whose extent is
+ * ((Nq - 1) * stride[2] + Nk) * esize bytes: rows behind the last read as zeros, nothing outside the tensor is touched, elements between Nk and stride[2]
+ * of a row are read and ignored.  The library never reads the tensor on the host: no copy, no synchronisation, a call can be captured in a graph and
+ * replayed after the bias was overwritten in place.
+ * Every call runs the bias form of the fixed-length LOCAL instantiations, whatever the window (full and causal attention carry unbounded sides): il8
+ * (variant 30) or il4 (32) as tfa_fwd_alibi chooses for the same problem, same grid; every tile through the compiler-scheduled bodies, the tile's bias
+ * requested at the top of the body ahead of the QK^T MFMAs and added to the raw scores (bias / softmax_scale) in front of the mask and the row maximum;
+ * rounding rule TFA_RULE_LAZY for both dtypes.  Every tile the mask admits is visited: tiles that the bias masks completely are not skipped.  The backward
+ * is the dQ launch (which forms delta) and the fused dK/dV launch of that form, deterministic; never the dS-workspace form.
+ * Refused, nothing launched: a NULL struct or bias pointer (TFA_ERR_NULL); a dtype that is neither TFA_F32 nor q's (TFA_ERR_DTYPE); reserved_ != 0
+ * (TFA_ERR_SHAPE); a base that is not 16-byte aligned (TFA_ERR_ALIGN); a negative stride, a non-zero stride that is not a multiple of 8 elements, a row
+ * stride below Nk, or a (b, h) slice of 2 GiB or more (TFA_ERR_STRIDE); and what the ALiBi form refuses, with its codes: head dims above 128
+ * (TFA_ERR_HEAD_DIM), fp32 q (TFA_ERR_DTYPE), any flag — TFA_FWD_EXACT_MAX included — (TFA_ERR_SHAPE), a window side below -1, kv_offset / nk_total != 0,
+ * Nq + Nk >= 2^28 (TFA_ERR_SHAPE), q / k / v / out slices that need per-tile descriptors (TFA_ERR_STRIDE), a forced variant other than 30 / 32
+ * (TFA_ERR_VARIANT).  Out of scope: a gradient for the bias; a bias with packed variable-length, KV-cache or paged calls, with alibi_slopes or softcap, with
+ * split-KV; bool or 8-bit masks read by the kernel (convert them to 0 / -inf); skipping fully masked tiles.
+ * Tolerances: the header's "which tolerance each path guarantees", LSE |d| <= 1e-4 * max(1, |lse|) as for ALiBi.
+ * Cost: a full-shape bias is B * H * Nq * Nk * esize bytes that come from HBM once per forward and twice per backward; tools/bench_bias.py prints that
+ * floor beside each measured time (README.md, "Attention bias"). */
+typedef struct tfa_attn_bias {
+  const void* bias;
+  int32_t dtype;       /* TFA_F16 / TFA_BF16 (q's) / TFA_F32 */
+  int32_t reserved_;   /* 0 */
+  int64_t stride[3];   /* batch, head, row in elements; 0 = broadcast */
+} tfa_attn_bias;
+int tfa_fwd_bias(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, void* stream);
+/* Validate and report the launch geometry of tfa_fwd_bias without launching (no GPU needed): tfa_fwd_alibi_plan's for the same problem. */
+int tfa_fwd_bias_plan(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, int* grid, int* block, int* lds_bytes);
+/* The kernel variant tfa_fwd_bias runs for *p (30 or 32), or a negative TFA_ERR_* code. */
+int tfa_fwd_bias_variant(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right);
+/* The row reference P is rounded against: TFA_RULE_LAZY (bf16 and fp16), or a negative TFA_ERR_* code. */
+int tfa_fwd_bias_rounding_rule(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right);
+/* The backward of a biased forward (same bias, window and params as tfa_bwd); _plan validates without launching. */
+int tfa_bwd_bias(const tfa_bwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, void* stream);
+int tfa_bwd_bias_plan(const tfa_bwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right);
 
 /* ---- attention over a K/V cache (FlashAttention-2's flash_attn_with_kvcache: cache_seqlens, paged KV, in-place append) ------------------------
  * The inference step of a serving loop: B sequences, each with its own number of cached keys, the lengths in DEVICE memory.

@@ -12,7 +12,8 @@ Reference-named entry points (same names, argument order and return shapes):
 * ``flash_attn(q, k, v, is_causal, softmax_scale) -> out`` (flash_attention_c/csrc/ops.cu:4-8)
 
 FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen_func`` with ``causal``, ``window_size``, ``alibi_slopes`` and ``softcap``
-(GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.
+(GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.  ``flash_attn_func`` also
+takes ``attn_bias``: a dense additive bias or mask as scaled_dot_product_attention's ``attn_mask`` (fixed-length calls; no gradient for the bias).
 Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append; 16-bit or fp8 e4m3 caches with ``k_descale`` / ``v_descale``).
 """
 from .ops import (  # noqa: F401

@@ -84,6 +84,12 @@ SYMBOLS = (
     "tfa_bwd_softcap_plan",
     "tfa_bwd_varlen_softcap",
     "tfa_bwd_varlen_softcap_plan",
+    "tfa_fwd_bias",
+    "tfa_fwd_bias_plan",
+    "tfa_fwd_bias_variant",
+    "tfa_fwd_bias_rounding_rule",
+    "tfa_bwd_bias",
+    "tfa_bwd_bias_plan",
     "tfa_fwd_kvcache",
     "tfa_fwd_kvcache_workspace",
     "tfa_fwd_kvcache_plan",
@@ -210,6 +216,17 @@ class TfaPagedKv(C.Structure):
         ("reserved_", C.c_int32),
         ("k_page_stride", C.c_int64),
         ("v_page_stride", C.c_int64),
+    ]
+
+
+class TfaAttnBias(C.Structure):
+    """struct tfa_attn_bias (include/tfa.h): the dense additive bias of tfa_fwd_bias / tfa_bwd_bias, handed over beside TfaFwdParams / TfaBwdParams."""
+
+    _fields_ = [
+        ("bias", C.c_void_p),
+        ("dtype", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("stride", C.c_int64 * 3),
     ]
 
 
@@ -426,6 +443,13 @@ def lib():
                        ("tfa_fwd_varlen_softcap_variant", [PV] + SC), ("tfa_fwd_varlen_softcap_rounding_rule", [PV] + SC),
                        ("tfa_bwd_softcap", [PB] + SC + [C.c_void_p]), ("tfa_bwd_softcap_plan", [PB] + SC),
                        ("tfa_bwd_varlen_softcap", [PVB] + SC + [C.c_void_p]), ("tfa_bwd_varlen_softcap_plan", [PVB] + SC)):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
+    # dense bias: the local entry points' arguments with (const tfa_attn_bias* bias) in front of the window
+    BI = [C.POINTER(TfaAttnBias), C.c_int, C.c_int]
+    for name, args in (("tfa_fwd_bias", [PF] + BI + [C.c_void_p]), ("tfa_fwd_bias_plan", [PF] + BI + [IP, IP, IP]),
+                       ("tfa_fwd_bias_variant", [PF] + BI), ("tfa_fwd_bias_rounding_rule", [PF] + BI),
+                       ("tfa_bwd_bias", [PB] + BI + [C.c_void_p]), ("tfa_bwd_bias_plan", [PB] + BI)):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     # attention over a K/V cache (tfa_kvcache_params)

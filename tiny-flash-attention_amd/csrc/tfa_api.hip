@@ -389,7 +389,8 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     a.block_table = pg->block_table;
   }
   if (win) tfa::set_window(&a, win[0], win[1], f.Nq, f.Nk);   // (after the last read of a.big: the window shares its bytes)
-  if (al) tfa::set_alibi(&a, *al);
+  if (al && al->biased) tfa::set_bias(&a, *al->bias, f.Nq, f.Nk);   // (the bias shares the bytes of the slopes and more: the last writer too)
+  else if (al) tfa::set_alibi(&a, *al);
   if (variant_out) *variant_out = variant;
   if (rule_out) *rule_out = rounding_rule(variant, f.dtype, f.D, !win && !pg);   // (the local and paged forms are not the main instantiation)
   const bool causal = f.is_causal != 0, f32out = f.out_dtype == TFA_F32;
@@ -398,7 +399,7 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
     using T = typename decltype(k)::T;
     constexpr int W = decltype(k)::W;
     if (pg) return tfa::launch_fwd_form<T, W, tfa::FORM_VARLEN | tfa::FORM_PAGED>(a, causal, f32out, variant, s, geom, dry);
-    return tfa::by_form(vl != nullptr, win != nullptr, al != nullptr, al && al->capped, [&](auto form) {
+    return tfa::by_form(vl != nullptr, win != nullptr, al != nullptr, al && al->capped, al && al->biased, [&](auto form) {
       return tfa::launch_fwd_form<T, W, decltype(form)::FORM>(a, causal, f32out, variant, s, geom, dry);
     });
   });
@@ -406,6 +407,7 @@ int run_form(const tfa_fwd_params& f_in, const tfa_fwd_params& eq, const tfa_var
 
 // tfa_fwd_local: FULL and CAUSAL windows are tfa_fwd's own problems; a true window covers the whole key sequence (no partial passes)
 // tfa_fwd_alibi (al): every window, FULL and CAUSAL included, is the local form's problem — the ALiBi kernels are instantiations of it
+// tfa_fwd_bias (al->biased): the same, with the dense bias in the slopes' place
 int run_local(const tfa_fwd_params* p, const int* w, const tfa::AlibiArg* al, void* stream, tfa::LaunchGeom* geom, bool dry, int* variant_out, int* rule_out) {
   if (!p) return TFA_ERR_NULL;
   int win[2] = {w[0], w[1]};
@@ -422,7 +424,7 @@ int run_local(const tfa_fwd_params* p, const int* w, const tfa::AlibiArg* al, vo
   if (p->flags != 0) return TFA_ERR_SHAPE;
   if (al) {
     if (p->H <= 0) return TFA_ERR_SHAPE;
-    const int st = tfa::check_alibi(*al, p->H, p->softmax_scale);
+    const int st = al->biased ? tfa::check_bias(al->bias, p->dtype, p->Nq, p->Nk) : tfa::check_alibi(*al, p->H, p->softmax_scale);
     if (st != TFA_OK) return st;
   }
   return run_form(*p, *p, nullptr, win, al, stream, geom, dry, variant_out, rule_out);
@@ -1083,6 +1085,35 @@ int tfa_fwd_varlen_softcap_rounding_rule(const tfa_varlen_fwd_params* p, float s
   return variant_or_rule(call, true);
 }
 #undef TFA_SOFTCAP_CALL
+
+// Dense bias: the fixed-length ALiBi call with the bias tensor in the slopes' place (a NULL struct is refused by check_bias)
+#define TFA_BIAS_CALL(p)                                        \
+  const int w[2] = {window_left, window_right};                 \
+  tfa::AlibiArg al{};                                           \
+  al.bias = bias;                                               \
+  al.biased = true;                                             \
+  const FwdCall call{p, nullptr, w, &al}
+int tfa_fwd_bias(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, void* stream) {
+  TFA_BIAS_CALL(p);
+  if (!p) return TFA_ERR_NULL;
+  return route(call, stream);
+}
+int tfa_fwd_bias_plan(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, int* grid, int* block, int* lds_bytes) {
+  TFA_BIAS_CALL(p);
+  if (!p) return TFA_ERR_NULL;
+  return plan(call, grid, block, lds_bytes);
+}
+int tfa_fwd_bias_variant(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right) {
+  TFA_BIAS_CALL(p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, false);
+}
+int tfa_fwd_bias_rounding_rule(const tfa_fwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right) {
+  TFA_BIAS_CALL(p);
+  if (!p) return TFA_ERR_NULL;
+  return variant_or_rule(call, true);
+}
+#undef TFA_BIAS_CALL
 
 int tfa_fwd_variant(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, false); }   // (run()'s final choice, after GQA packing and its fall-back)
 int tfa_fwd_rounding_rule(const tfa_fwd_params* p) { return variant_or_rule({p, nullptr, nullptr}, true); }

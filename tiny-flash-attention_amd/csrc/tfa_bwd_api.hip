@@ -252,7 +252,7 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
 // tfa_bwd_form_inst.inc).  a holds everything but the gradients; v is the problem as the kernels see it (run_bwd_varlen: one sequence, batch stride 0).
 // alibi: the ALiBi form of the local kernels (a.slopes set; local is then true whatever the window); capped: their soft-capping form instead (a.softcap_cr set,
 // a.slopes set or null)
-int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, bool alibi, bool capped, void* stream, bool dry) {
+int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, bool local, bool alibi, bool capped, void* stream, bool dry, bool biased = false) {
   const int gsz = (v.grad_dtype == TFA_F32) ? 4 : 2;
   const bool causal = v.is_causal != 0, f32 = v.grad_dtype == TFA_F32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -261,7 +261,7 @@ int launch_form_pair(const tfa::BArgs& a, const tfa_bwd_params& v, bool varlen, 
     return (int)tfa::by_dtype_width<64, 128>(v.dtype, v.D, [&](auto k) {
       using T = typename decltype(k)::T;
       constexpr int W = decltype(k)::W;
-      return tfa::by_form(varlen, local, alibi, capped, [&](auto form) {
+      return tfa::by_form(varlen, local, alibi, capped, biased, [&](auto form) {
         return tfa::launch_bwd_form<T, W, decltype(form)::FORM>(m, keys, (int)grid, causal, f32, s, dry);
       });
     });
@@ -298,14 +298,15 @@ int run_bwd_local(const tfa_bwd_params* p, const int* w, const tfa::AlibiArg* al
   }
   int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
   if (st) return st;
-  if (al && (st = tfa::check_alibi(*al, p->H, p->softmax_scale)) != TFA_OK) return st;
+  if (al && (st = al->biased ? tfa::check_bias(al->bias, p->dtype, p->Nq, p->Nk) : tfa::check_alibi(*al, p->H, p->softmax_scale)) != TFA_OK) return st;
   tfa::BArgs a;
   st = fill_args(*p, nullptr, &a);
   if (st) return st;
   a.fuse_delta = 1;                                  // (the dQ launch forms delta)
   tfa::set_window(&a, win[0], win[1], p->Nq, p->Nk);
-  if (al) tfa::set_alibi(&a, *al);
-  return launch_form_pair(a, *p, false, true, al != nullptr, al && al->capped, stream, dry);
+  if (al && al->biased) tfa::set_bias(&a, *al->bias, p->Nq, p->Nk);   // (tfa_bwd_bias: in bytes no local launch reads, the slopes' among them)
+  else if (al) tfa::set_alibi(&a, *al);
+  return launch_form_pair(a, *p, false, true, al != nullptr, al && al->capped, stream, dry, al && al->biased);
 }
 
 // Packed variable-length batches (include/tfa.h: tfa_bwd_varlen, tfa_bwd_varlen_local — w: the window, or nullptr): as in the forward (tfa_api.hip: run_varlen)
@@ -367,6 +368,18 @@ int tfa_bwd_varlen_local(const tfa_varlen_bwd_params* p, int window_left, int wi
 int tfa_bwd_varlen_local_plan(const tfa_varlen_bwd_params* p, int window_left, int window_right) {
   const int w[2] = {window_left, window_right};
   return run_bwd_varlen(p, w, nullptr, nullptr, true);
+}
+int tfa_bwd_bias(const tfa_bwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right, void* stream) {
+  const int w[2] = {window_left, window_right};
+  tfa::AlibiArg al{};
+  al.bias = bias; al.biased = true;
+  return run_bwd_local(p, w, &al, stream, false);
+}
+int tfa_bwd_bias_plan(const tfa_bwd_params* p, const tfa_attn_bias* bias, int window_left, int window_right) {
+  const int w[2] = {window_left, window_right};
+  tfa::AlibiArg al{};
+  al.bias = bias; al.biased = true;
+  return run_bwd_local(p, w, &al, nullptr, true);
 }
 int tfa_bwd_alibi(const tfa_bwd_params* p, const float* alibi_slopes, int64_t slopes_batch_stride, int window_left, int window_right, void* stream) {
   const int w[2] = {window_left, window_right};

@@ -52,7 +52,7 @@ hipError_t launch_bwd_kv(const BArgs& a, int grid, bool causal, bool f32out, hip
 // dQ = scale * dS . K from the workspace (tfa_bwd_dq_kernel.h): grid = B * H * ceil(Nq / 256)
 template <typename T, int D>
 hipError_t launch_bwd_dq_ws(const BArgs& a, int grid, bool causal, bool f32out, hipStream_t stream, bool dry);
-// the forms of the two-launch backward (tfa_host_util.h: TFA_FORMS_BWD — packed variable-length, local, and the local kernels' ALiBi and softcap forms): keys = false
+// the forms of the two-launch backward (tfa_host_util.h: TFA_FORMS_BWD — packed variable-length, local, and the local kernels' ALiBi, softcap and (fixed-length only) dense-bias forms): keys = false
 // the dQ launch (grid = B * H * ceil(Nq / 256)), keys = true the fused dK/dV launch (grid = B * Hk * ceil(Nk / 128)) — Nq / Nk = max_seqlen_q / _k for varlen.
 // The local kernels are the causal template only (`causal` is ignored).  One unit per (dtype, width, form): tfa_bwd_inst_varlen_<dtype>_<D> and
 // tfa_bwd_inst_<local|alibi|softcap>_<dtype>_<D>_<fx|vl>, each specialising launch_bwd_form (tfa_bwd_form_inst.inc)

@@ -8,6 +8,7 @@
 // alibi: the ALiBi form of the local instantiations (VF_IL_ALIBI) — full, causal and windowed attention with slopes are this one kernel per (dtype, width,
 // fixed / varlen), the window's missing sides carried as unbounded.
 // softcap: the soft-capping form of the local instantiations (VF_IL_SOFTCAP), with or without slopes (a run-time choice of the one kernel), every mask.
+// bias: the dense-bias form of the fixed-length local instantiations (VF_IL_BIAS; units tfa_fwd_inst_bias_<dtype>_<D>_fx): every mask, the bias loaded in the tile bodies.
 // paged: the paged-K/V form of the plain varlen instantiations (VF_IL_PAGED; units tfa_fwd_inst_paged_<dtype>_<D>_c<0|1>): per-tile descriptors, so the
 // compiler-scheduled tile bodies and the lazy row reference for both types.
 #include "tfa_launch.h"
@@ -26,7 +27,7 @@ hipError_t launch_fwd_form_c<TFA_T, TFA_D, (TFA_FORM) | TFA_FORM_VL, TFA_CAUSAL>
   static_assert(form_legal(F, TFA_CAUSAL), "not a form of the il kernels (tfa_host_util.h: form_legal)");
   constexpr bool LOCAL = (F & FORM_LOCAL) != 0;
   constexpr int FORM = ((F & FORM_VARLEN) ? VF_IL_VARLEN : 0) | (LOCAL ? VF_IL_LOCAL : 0) | ((F & FORM_ALIBI) ? VF_IL_ALIBI : 0) | ((F & FORM_SOFTCAP) ? VF_IL_SOFTCAP : 0) |
-                       ((F & FORM_PAGED) ? VF_IL_PAGED : 0);
+                       ((F & FORM_PAGED) ? VF_IL_PAGED : 0) | ((F & FORM_BIAS) ? VF_IL_BIAS : 0);
   constexpr int PAIR = LOCAL ? 0 : VF_PAIR;   // (the local form: one query block per work item, no causal pairs — and so no PREF2)
   constexpr int VF30 = PAIR | (LOCAL ? 0 : VF_IL_PREF2) | VF_IL_DMASPREAD | VF_IL_EPI | VF_IL_QLDS | FORM;   // variant 30's main instantiation (tfa_fwd_inst.inc)
   constexpr int VF32 = PAIR | VF_IL_EPI | VF_IL_EPI_INPLACE | FORM;                                              // variant 32's

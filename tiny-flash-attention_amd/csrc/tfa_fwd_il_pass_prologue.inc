@@ -66,9 +66,12 @@
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[tt][r] = 0.f;
       const unsigned kb = kbuf * TILE_BYTES;
+      u32x4 bq[4];                                       // BIAS: the tile's bias, requested ahead of the MFMAs
+      if constexpr (BIAS) bias_issue(t, bq);
 #pragma unroll
       for (int i = 0; i < N1; ++i) s[KT(i)] = E::mfma(k_frag_rt(kb, i), qf[KS(i)], s[KT(i)]);
-      if constexpr (SMOD) apply_bias(t, s);
+      if constexpr (BIAS) bias_add(t, s, bq);
+      else if constexpr (SMOD) apply_bias(t, s);
       if (needs_mask(t)) apply_mask(t, s);
       float mx = s[0][0];
 #pragma unroll

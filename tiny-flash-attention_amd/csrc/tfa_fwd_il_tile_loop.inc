@@ -19,6 +19,8 @@
         if (issue_k) dma_k(tk, PAR);
         dma_v(j + 1, PAR ^ 1);
       }
+      u32x4 bq[4];                                    // BIAS: tile j+1's bias, requested ahead of the QK^T MFMAs
+      if constexpr (BIAS) bias_issue(j + 1, bq);
       const float msc = mref;
       constexpr int KB = PAR ^ 1;
       const char* vbp = vl + PAR * TILE_BYTES;
@@ -68,7 +70,8 @@
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (SMOD) {                           // the cap and / or the bias in front of the mask and of the row maximum, on every tile
-        apply_bias(j + 1, snext);
+        if constexpr (BIAS) bias_add(j + 1, snext, bq);
+        else apply_bias(j + 1, snext);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (MASK) {                                     // S(j+1) is complete (MFMA results: the s_nop covers the read distance)

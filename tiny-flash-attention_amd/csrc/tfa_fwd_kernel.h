@@ -73,6 +73,12 @@ struct KArgs {
     struct {
       int total_q, total_k;   // varlen: rows of the packed tensors — every sequence bound read from cu_q / cu_k is clamped into them
     };
+    // (the dense bias — tfa_fwd_bias, the VF_IL_BIAS instantiations: a fixed-length local launch, so neither split-KV, varlen, slopes, `grid` nor `trace` — lies in
+    //  those fields' bytes, here and in the unions below: every existing kernel keeps its argument layout and size.  set_bias fills them after everything else)
+    struct {
+      int bias_sn;            // bias: BYTES between consecutive query rows of a (b, h) slice (0: one row for all)
+      unsigned bias_bytes;    // bias: extent of a (b, h) slice in bytes, ((Nq - 1) * row stride + Nk) * esize < 2 GiB — one descriptor, everything beyond reads as zeros
+    };
   };
   union {
     struct {
@@ -81,6 +87,9 @@ struct KArgs {
     struct {
       const int* cu_q;   // varlen: sequence b is rows [cu_q[b], cu_q[b+1]) of q / out and [cu_k[b], cu_k[b+1]) of k / v (device int32, B + 1 entries);
       const int* cu_k;   // B is then the sequence count and Nq / Nk = max_seqlen_q / _k: a sequence of that many rows sizes nmb, nwork and *_bytes (the grid)
+    };
+    struct {
+      long long bias_sb, bias_sh;   // bias: ELEMENTS between batch entries / query heads (0: broadcast)
     };
   };
   int nmb;          // number of query blocks per (b,h)
@@ -127,11 +136,13 @@ struct KArgs {
     int grid;       // workgroups launched (persistent kernels walk work items with this stride)
     int slopes_bs;  // ALiBi: slopes[b * slopes_bs + h] — 0: one row of H slopes shared by the batch, else H
     int pg_max_blocks;   // paged varlen: entries per row of the block table (the index of every table load is clamped below it)
+    int bias_f32;        // bias: its elements are fp32 (else q's 16-bit type)
   };
   union {
     unsigned long long* trace;  // debug: 8 x u64 per workgroup (cycle stamps), or nullptr
     const float* slopes;        // ALiBi: one fp32 slope per (batch entry / sequence, query head) in device memory, read by the work item; never by the host
     const int* block_table;     // paged varlen (see pg_* above): device int32 (B, max_blocks) by pg_table_stride, read by the work items; never by the host
+    const void* bias;           // bias: element [0, 0, 0, 0] of the dense bias in device memory, read by the work items; never by the host
   };
   int dv;           // valid head dim (<= the kernel's compile-time D, a multiple of 8): the 16-byte chunks of a row beyond dv are
                     // read as zeros (their LDS-DMA lanes / Q loads are pointed outside the buffer) and never stored

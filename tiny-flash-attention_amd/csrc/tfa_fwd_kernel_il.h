@@ -91,6 +91,13 @@ constexpr int VF_IL_PAGED = 128;         // paged K/V of a packed variable-lengt
                                          // behind (the page's tail, stale keys, NaN) reads as zeros.  The entries of three consecutive pages are kept in scalars, loaded once per
                                          // page, the third a tile of compute ahead of its first use (page_of below).  One descriptor per tile: the compiler-scheduled tile bodies
                                          // only, as in the WINDOWED instantiations, and so the lazily re-based row reference for both types.  (Bit: VF_SWP of another kernel)
+constexpr int VF_IL_BIAS = 1024;         // a dense additive bias (tfa_fwd_bias): S[i,j] = scale * q_i . k_j + bias[b,h,i,j], a form of the fixed-length LOCAL instantiations on the ALiBi
+                                         // hook — and the first that LOADS inside the tile loop.  In the S^T = K Q^T layout a lane holds, for its row, the keys key0 + 4 hi + 32 tt + 8 g
+                                         // + {0..3}: eight runs of four consecutive keys per tile, one 8-byte load each for a 16-bit bias, 16-byte loads for fp32 (a launch-uniform
+                                         // branch), through ONE descriptor per (b, h) slice whose extent ends behind the last row's last key — rows behind Nq read as zeros and
+                                         // nothing outside the tensor is touched.  The requests go out at the top of the tile body, ahead of the QK^T MFMAs (fp32: key block 0's
+                                         // there, block 1's at the hook — 16 registers in flight either way); bias / scale goes onto the raw scores where apply_bias runs, so
+                                         // -inf entries are a mask and the lazy reference, its trigger and the LSE work on biased scores.  (Bit: VF_PRIO of the LDS-DMA kernel)
 
 }  // namespace tfa
 #include "tfa_fwd_il_regs.h"
@@ -314,7 +321,10 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   static_assert(!ALIBI || !(AB & ILAB_TRACE), "alibi: KArgs::slopes / slopes_bs share the bytes of trace / grid — no traced twin");
   constexpr bool SOFTCAP = (VF & VF_IL_SOFTCAP) != 0;
   static_assert(!SOFTCAP || (LOCAL && !ALIBI && !(AB & ILAB_TRACE)), "softcap: a form of the local instantiations; its slopes are a run-time choice (KArgs::slopes may be null)");
-  constexpr bool SMOD = ALIBI || SOFTCAP;            // the raw scores of every tile are modified in front of the mask: compiler-scheduled bodies only
+  constexpr bool BIAS = (VF & VF_IL_BIAS) != 0;
+  static_assert(!BIAS || (LOCAL && !VARLEN && !ALIBI && !SOFTCAP && !(AB & ILAB_TRACE)),
+                "bias: a form of the fixed-length local instantiations; its arguments share the bytes of the split-KV / varlen fields, grid and trace — no traced twin");
+  constexpr bool SMOD = ALIBI || SOFTCAP || BIAS;    // the raw scores of every tile are modified in front of the mask: compiler-scheduled bodies only
   int kofs = 0, wlen = 0;
   if constexpr (LOCAL) {
     const int nk_s = VARLEN ? vsq.nk : p.Nk;
@@ -372,6 +382,16 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
   };
   auto k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, (WIN || PAGED) ? 0u : (unsigned)k_bytes, 0x00020000);
   auto v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, (WIN || PAGED) ? 0u : (unsigned)v_bytes, 0x00020000);
+  // BIAS: the (b, query head) slice of the bias through one descriptor (broadcast dimensions: stride 0); 1 / scale takes a bias into the raw-score domain
+  auto bias_rs = k_rs;
+  float bias_inv = 0.f;
+  bool bias_f32 = false;
+  if constexpr (BIAS) {
+    bias_f32 = p.bias_f32 != 0;
+    const char* bb = reinterpret_cast<const char*>(p.bias) + ((long long)b * p.bias_sb + (long long)h * p.bias_sh) * (bias_f32 ? 4 : 2);
+    bias_rs = __builtin_amdgcn_make_buffer_rsrc((void*)bb, 0, p.bias_bytes, 0x00020000);
+    bias_inv = 1.f / p.scale;
+  }
 
   int k_src[PPW], v_src[PPW];
 #pragma unroll
@@ -730,6 +750,64 @@ __global__ __launch_bounds__(NW * 64, 2) __attribute__((amdgpu_num_vgpr(96))) vo
       for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[tt][r] = fmaf(alibi_a, fabsf(cf - (float)(32 * tt + (r & 3) + 8 * (r >> 2))), s[tt][r]);
+    };
+    // BIAS: the lane's row of the slice and its first key (a row behind the last one: outside the descriptor — zeros); bias_issue requests tile t's bias
+    // (16-bit: all eight runs, two dwords each; fp32: the four runs of key block 0), bias_add puts it onto the raw scores (fp32: and fetches block 1 in between).
+    // Every offset is the VECTOR offset, which the descriptor checks.  A 16-bit bias with an odd Nk ends inside a dword: the tile that holds the last key
+    // fetches that element once more by itself, whatever the range check made of the dword
+    int bias_off = 0;
+    if constexpr (BIAS) bias_off = my_pos < p.Nq ? my_pos * p.bias_sn + ((kofs + 4 * hi) << (bias_f32 ? 2 : 1)) : (int)TFA_OOB;
+    auto bias_issue = [&](int t, u32x4 (&bq)[4]) {
+      if (bias_f32) {
+        const int o = bias_off + (key0_of(t) << 2);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(bias_rs, o + g * 32, 0, 0);
+      } else {
+        const int o = bias_off + (key0_of(t) << 1);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(bias_rs, o + u * 16, 0, 0);   // run u: key block u >> 2, group u & 3
+          bq[u >> 1][2 * (u & 1)] = w[0];
+          bq[u >> 1][2 * (u & 1) + 1] = w[1];
+        }
+      }
+    };
+    auto bias_add = [&](int t, f32x16 (&s)[2], u32x4 (&bq)[4]) {
+      if (bias_f32) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          if (tt == 1) {
+            const int o = bias_off + (key0_of(t) << 2) + 128;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bq[g] = __builtin_amdgcn_raw_buffer_load_b128(bias_rs, o + g * 32, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const unsigned w = bq[r >> 2][r & 3];      // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0)
+            s[tt][r] = fmaf(__builtin_bit_cast(float, w), bias_inv, s[tt][r]);
+          }
+        }
+      } else {
+        typedef __attribute__((ext_vector_type(2))) T bt2;
+        const int kl = p.Nk - 1 - kofs - key0_of(t) - 4 * hi;       // the last key's offset among the lane's keys of this tile
+        const bool fix = (p.Nk & 1) && p.Nk - 1 - kofs - key0_of(t) >= 0 && p.Nk - 1 - kofs - key0_of(t) < BN;
+        float last = 0.f;
+        if (fix) {
+          const unsigned short w = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(bias_rs, my_pos < p.Nq ? my_pos * p.bias_sn + (p.Nk - 1) * 2 : (int)TFA_OOB, 0, 0);
+          last = (float)__builtin_bit_cast(T, w);
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int u = 4 * tt + (r >> 2);
+            const unsigned d = bq[u >> 1][2 * (u & 1) + ((r & 3) >> 1)];
+            const bt2 w = __builtin_bit_cast(bt2, d);
+            float x = (float)w[r & 1];
+            if (fix && 32 * tt + (r & 3) + 8 * (r >> 2) == kl) x = last;
+            s[tt][r] = fmaf(x, bias_inv, s[tt][r]);
+          }
+      }
     };
     // Reference exponent of the row ("mref", log2 domain) instead of the exact running max: P = exp2(s*sc - mref)
     // where mref is the row's scaled running max as of the last re-base.  A wave re-bases (every row takes its current

@@ -55,11 +55,12 @@ static inline auto by_dtype_width(int dtype, int D, F&& f) {
 // The form of an il8 / il4 forward or backward dQ / dK/dV launch beyond the plain fixed-length one: a mask of these bits, a template argument of launch_fwd_form
 // and launch_bwd_form.  The ALiBi and softcap kernels are forms of the local ones; softcap's slopes are a run-time choice of its one kernel (no ALIBI bit);
 // the local kernels exist as the causal template only (the window carries the right edge).  FORM_PAGED (tfa_fwd_varlen_paged: K/V through a block table) is a
-// form of the plain varlen forward alone: no window, no slopes, no cap, no backward.
-enum : int { FORM_VARLEN = 1, FORM_LOCAL = 2, FORM_ALIBI = 4, FORM_SOFTCAP = 8, FORM_PAGED = 16 };
+// form of the plain varlen forward alone: no window, no slopes, no cap, no backward.  FORM_BIAS (tfa_fwd_bias / tfa_bwd_bias: a dense additive bias read from
+// memory inside the tile loop) is a form of the fixed-length local kernels alone: no varlen, no slopes, no cap.
+enum : int { FORM_VARLEN = 1, FORM_LOCAL = 2, FORM_ALIBI = 4, FORM_SOFTCAP = 8, FORM_PAGED = 16, FORM_BIAS = 32 };
 constexpr bool form_legal(int form, bool causal = true) {
-  return form > 0 && form < 32 && ((form & FORM_LOCAL) ? causal : !(form & (FORM_ALIBI | FORM_SOFTCAP))) && !((form & FORM_ALIBI) && (form & FORM_SOFTCAP)) &&
-         (!(form & FORM_PAGED) || form == (FORM_VARLEN | FORM_PAGED));
+  return form > 0 && form < 64 && ((form & FORM_LOCAL) ? causal : !(form & (FORM_ALIBI | FORM_SOFTCAP))) && !((form & FORM_ALIBI) && (form & FORM_SOFTCAP)) &&
+         (!(form & FORM_PAGED) || form == (FORM_VARLEN | FORM_PAGED)) && (!(form & FORM_BIAS) || form == (FORM_LOCAL | FORM_BIAS));
 }
 // THE list of the legal forms, X(mask): each is one instantiation unit per (dtype, width) of the forward (tfa_fwd_inst_<varlen|local|alibi|softcap>_...) and of
 // the backward (tfa_bwd_inst_...), fixed-length (_fx) or varlen (_vl) — the Makefile's words of those names carry the same masks.  The declarations of tfa_launch.h
@@ -67,7 +68,7 @@ constexpr bool form_legal(int form, bool causal = true) {
 // TFA_FORMS: every form — those and the forward-only paged varlen form (units tfa_fwd_inst_paged_..., reached by run_form without by_form)
 #define TFA_FORMS_BWD(X)                                                                                                    \
   X(FORM_VARLEN) X(FORM_LOCAL) X(FORM_LOCAL | FORM_VARLEN) X(FORM_LOCAL | FORM_ALIBI) X(FORM_LOCAL | FORM_ALIBI | FORM_VARLEN) \
-  X(FORM_LOCAL | FORM_SOFTCAP) X(FORM_LOCAL | FORM_SOFTCAP | FORM_VARLEN)
+  X(FORM_LOCAL | FORM_SOFTCAP) X(FORM_LOCAL | FORM_SOFTCAP | FORM_VARLEN) X(FORM_LOCAL | FORM_BIAS)
 #define TFA_FORMS(X) TFA_FORMS_BWD(X) X(FORM_VARLEN | FORM_PAGED)
 // ... and the (dtype, width) pairs each of them is built for: X(T, D, ...)
 #define TFA_FORM_SHAPES(X, ...) X(__bf16, 64, __VA_ARGS__) X(__bf16, 128, __VA_ARGS__) X(_Float16, 64, __VA_ARGS__) X(_Float16, 128, __VA_ARGS__)
@@ -76,10 +77,10 @@ struct Form {
   static constexpr int FORM = FORM_;
 };
 // The one run-time -> compile-time switch of the form: calls f(Form<mask>{}).  No window: the plain varlen form (the only caller without one); else the local
-// form or, with slopes, its ALiBi form or, capped (slopes or not), its softcap form — fixed-length or varlen.
+// form or, with slopes, its ALiBi form or, capped (slopes or not), its softcap form — fixed-length or varlen — or, biased (fixed-length only), its dense-bias form.
 template <typename F>
-static inline auto by_form(bool varlen, bool local, bool alibi, bool capped, F&& f) {
-  const int form = !local ? FORM_VARLEN : FORM_LOCAL | (varlen ? FORM_VARLEN : 0) | (capped ? FORM_SOFTCAP : alibi ? FORM_ALIBI : 0);
+static inline auto by_form(bool varlen, bool local, bool alibi, bool capped, bool biased, F&& f) {
+  const int form = !local ? FORM_VARLEN : biased ? FORM_LOCAL | FORM_BIAS : FORM_LOCAL | (varlen ? FORM_VARLEN : 0) | (capped ? FORM_SOFTCAP : alibi ? FORM_ALIBI : 0);
 #define TFA_BY_FORM(mask) \
   if (form == (mask)) return f(Form<(mask)>{});
   TFA_FORMS_BWD(TFA_BY_FORM)
@@ -116,7 +117,36 @@ struct AlibiArg {
   // wants softcap > 0 and finite and takes slopes == nullptr as "no bias".  A host scalar, folded into the raw-score domain here (softcap_cr = softcap / scale)
   bool capped = false;
   float softcap = 0.f;
+  // the dense bias (tfa_fwd_bias / tfa_bwd_bias) rides on it too: bias != nullptr = the call came through a _bias entry point (no slopes, no cap then)
+  const tfa_attn_bias* bias = nullptr;
+  bool biased = false;
 };
+// The dense bias of tfa_fwd_bias / tfa_bwd_bias, checked without reading it: a (b, h) slice is rows of Nk elements at stride[2], through ONE buffer descriptor of
+// ((Nq - 1) * stride[2] + Nk) * esize bytes — below 2 GiB — and 8- / 16-byte loads: the base 16-byte aligned, every non-zero stride a multiple of 8 elements.
+static inline int check_bias(const tfa_attn_bias* bi, int q_dtype, int Nq, int Nk) {
+  if (!bi || !bi->bias) return TFA_ERR_NULL;
+  if (bi->dtype != TFA_F32 && bi->dtype != q_dtype) return TFA_ERR_DTYPE;
+  if (bi->reserved_ != 0) return TFA_ERR_SHAPE;
+  if ((uintptr_t)bi->bias & 15) return TFA_ERR_ALIGN;
+  for (int i = 0; i < 3; ++i)
+    if (bi->stride[i] < 0 || (bi->stride[i] % 8) != 0) return TFA_ERR_STRIDE;
+  if (bi->stride[2] != 0 && bi->stride[2] < Nk) return TFA_ERR_STRIDE;              // (rows that overlap)
+  const int esize = bi->dtype == TFA_F32 ? 4 : 2;
+  if (bi->stride[2] > (int64_t)0x7fffffff / esize) return TFA_ERR_STRIDE;
+  if (((int64_t)(Nq - 1) * bi->stride[2] + Nk) * esize >= ((int64_t)1 << 31)) return TFA_ERR_STRIDE;
+  return TFA_OK;
+}
+// ... and into the kernel arguments (KArgs / BArgs: bytes no bias launch reads — after everything else has been written)
+template <typename Args>
+static inline void set_bias(Args* a, const tfa_attn_bias& bi, int Nq, int Nk) {
+  const int esize = bi.dtype == TFA_F32 ? 4 : 2;
+  a->bias = bi.bias;
+  a->bias_sb = bi.stride[0];
+  a->bias_sh = bi.stride[1];
+  a->bias_sn = (int)bi.stride[2] * esize;                                           // (bytes)
+  a->bias_bytes = (unsigned)(((int64_t)(Nq - 1) * bi.stride[2] + Nk) * esize);
+  a->bias_f32 = bi.dtype == TFA_F32;
+}
 static inline int check_alibi(const AlibiArg& al, int H, float scale) {
   if (al.capped) {
     const float cr = al.softcap / scale;

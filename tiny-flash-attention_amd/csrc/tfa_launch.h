@@ -129,7 +129,7 @@ template <typename T, int D>
 static inline hipError_t launch_fwd(const KArgs& a, bool causal, bool f32out, int variant, hipStream_t stream, LaunchGeom* geom, bool dry) {
   return causal ? launch_fwd_c<T, D, true>(a, f32out, variant, stream, geom, dry) : launch_fwd_c<T, D, false>(a, f32out, variant, stream, geom, dry);
 }
-// the forms of variants 30 and 32 (tfa_host_util.h: TFA_FORMS — packed variable-length, local, and the local kernels' ALiBi and softcap forms): one translation
+// the forms of variants 30 and 32 (tfa_host_util.h: TFA_FORMS — packed variable-length, local, and the local kernels' ALiBi, softcap and (fixed-length only) dense-bias forms): one translation
 // unit per (dtype, width, form) — the local forms as the CAUSAL template only (units tfa_fwd_inst_<local|alibi|softcap>_<dtype>_<D>_<fx|vl>), plain varlen and its paged form per
 // causal too (units tfa_fwd_inst_<varlen|paged>_<dtype>_<D>_c<0|1>) — each specialising launch_fwd_form_c (tfa_fwd_form_inst.inc)
 template <typename T, int D, int FORM, bool CAUSAL>

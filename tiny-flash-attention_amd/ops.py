@@ -121,6 +121,62 @@ def _softcap(softcap, dtype, D, extra=()):
     return cap
 
 
+def _attn_bias(attn_bias, B, H, Nq, Nk, device, dtype, D, alibi_slopes=None, softcap=0.0, extra=()):
+    """``attn_bias`` checked and prepared as the C ABI needs it (include/tfa.h, dense bias) without reading its values: a 4-D tensor broadcastable to
+    ``(B, H, Nq, Nk)`` — each of the first two dims 1 or full — on ``device``, of q's dtype, float32, or ``torch.bool`` under
+    scaled_dot_product_attention's convention (True = attend).  Returns ``None`` for ``None``, else ``(tensor, TfaAttnBias)``: the tensor the kernels read
+    (kept alive by the caller) and its struct, broadcast dims as stride 0.  A bool mask becomes 0 / -inf in q's dtype (one elementwise op); a tensor whose
+    base or strides miss the kernels' alignment (16-byte base, unit stride along keys, other strides multiples of 8 elements) is copied once into a buffer
+    whose row stride is Nk rounded up to 8 — a prepared tensor passes through unchanged.  Everything else raises by name before any launch."""
+    if attn_bias is None:
+        return None
+    if not isinstance(attn_bias, torch.Tensor):
+        raise TypeError(f"attn_bias must be a tensor (got {type(attn_bias).__name__})")
+    if attn_bias.dtype not in (torch.bool, torch.float32, dtype):
+        raise TypeError(f"attn_bias must be torch.bool, float32 or q's dtype {dtype} (got {attn_bias.dtype})")
+    if attn_bias.dim() != 4 or attn_bias.shape[0] not in (1, B) or attn_bias.shape[1] not in (1, H) or tuple(attn_bias.shape[2:]) != (Nq, Nk):
+        raise ValueError(f"attn_bias must have shape ({B} or 1, {H} or 1, {Nq}, {Nk}): 4-D, broadcastable over batch and query heads "
+                         f"(got {tuple(attn_bias.shape)})")
+    if attn_bias.device != device:
+        raise ValueError(f"attn_bias must be on q's device ({device}; got {attn_bias.device})")
+    if attn_bias.requires_grad:
+        raise RuntimeError("attn_bias requires grad, but the bias gets no gradient (a learned bias would silently stop training): detach it")
+    if alibi_slopes is not None:
+        raise ValueError("attn_bias: not together with alibi_slopes (add the ALiBi term to the bias instead)")
+    if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
+        raise ValueError("attn_bias: not together with softcap")
+    if dtype == torch.float32:
+        raise ValueError("attn_bias: the bias runs on float16 / bfloat16 inputs only (no fp32 bias path)")
+    if D > 128:
+        raise ValueError(f"attn_bias: the bias supports head dims up to 128 (got {D})")
+    for cond, msg in extra:
+        if cond:
+            raise ValueError(f"attn_bias: {msg}")
+    t = attn_bias
+    if t.dtype == torch.bool:
+        t = torch.where(t, torch.zeros((), dtype=dtype, device=device), torch.full((), float("-inf"), dtype=dtype, device=device))
+    for d in (0, 1):                                     # (an expanded dim is a broadcast one)
+        if t.shape[d] > 1 and t.stride(d) == 0:
+            t = t.narrow(d, 0, 1)
+    sizes, st = t.shape, t.stride()
+    aligned = (t.data_ptr() % 16 == 0 and (Nk == 1 or st[3] == 1) and (Nq == 1 or (st[2] % 8 == 0 and st[2] >= Nk)) and
+               all(sizes[d] == 1 or (st[d] >= 0 and st[d] % 8 == 0) for d in (0, 1)))
+    if not aligned:
+        rs = (Nk + 7) // 8 * 8
+        buf = torch.zeros((sizes[0], sizes[1], Nq, rs), dtype=t.dtype, device=device)
+        buf[..., :Nk].copy_(t)
+        t = buf[..., :Nk]
+        st = t.stride()
+    bi = _lib.TfaAttnBias()
+    bi.bias = t.data_ptr()
+    bi.dtype = _lib.TFA_F32 if t.dtype == torch.float32 else _DT[t.dtype]
+    bi.reserved_ = 0
+    bi.stride[0] = 0 if sizes[0] == 1 else st[0]
+    bi.stride[1] = 0 if sizes[1] == 1 else st[1]
+    bi.stride[2] = 0 if Nq == 1 else st[2]
+    return t, bi
+
+
 def _slopes_arg(alibi):
     """(pointer or None, batch stride) of checked slopes for a _softcap entry point, which takes NULL as "no bias"."""
     return (None, 0) if alibi is None else (alibi[0].data_ptr(), alibi[1])
@@ -131,10 +187,12 @@ def _alibi_window(win, is_causal):
     return win if win is not None else ((-1, 0) if is_causal else (-1, -1))
 
 
-def _call_form(base, p, stream, win, alibi, cap, is_causal):
+def _call_form(base, p, stream, win, alibi, cap, is_causal, bias=None):
     """Calls the entry point of one attention form on the parameter block p: ``base`` (tfa_fwd, tfa_fwd_varlen, tfa_bwd, tfa_bwd_varlen) with the suffix and the
-    extra arguments of the checked softcap / slopes / window — _softcap before _alibi before _local, else ``base`` itself."""
-    if cap:
+    extra arguments of the checked bias / softcap / slopes / window — _bias (never with a cap or slopes), _softcap before _alibi before _local, else ``base`` itself."""
+    if bias is not None:
+        suffix, extra = "_bias", (C.byref(bias[1]), *_alibi_window(win, is_causal))
+    elif cap:
         suffix, extra = "_softcap", (cap, *_slopes_arg(alibi), *_alibi_window(win, is_causal))
     elif alibi is not None:
         suffix, extra = "_alibi", (alibi[0].data_ptr(), alibi[1], *_alibi_window(win, is_causal))
@@ -146,8 +204,8 @@ def _call_form(base, p, stream, win, alibi, cap, is_causal):
 
 
 def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd", out_f32=False,
-                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), softcap=0.0,
-                   alibi_slopes=None):
+                   return_lse=True, out=None, kv_offset=0, nk_total=None, auto_split=False, exact_max=False, window_size=(-1, -1), attn_bias=None,
+                   softcap=0.0, alibi_slopes=None):
     """General forward: q (B,H,Nq,D) / k,v (B,Hk,Nk,D) for ``layout='bhnd'`` or
     (B,N,H,D) for ``layout='bnhd'``; any batch/head/row strides, unit stride along D.
     Returns ``(out, lse)``; ``out`` has q's shape (fp32 when ``out_f32``), ``lse`` is (B,H,Nq) fp32.
@@ -163,7 +221,15 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     or window; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored).
     ``softcap``: FlashAttention-2's tanh logit capping, a host float, 0.0 = none: the scaled scores x become ``softcap * tanh(x / softcap)`` FIRST, then the
     ALiBi bias is added, then the mask applies; the LSE is that of the capped scores (tfa_fwd_softcap; tanh within 2^-20; float16 / bfloat16, head dims up to
-    128, any mask or window, with or without slopes; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored; negative / NaN / inf: ValueError)."""
+    128, any mask or window, with or without slopes; not with ``exact_max`` or split-KV arguments, ``auto_split`` is ignored; negative / NaN / inf: ValueError).
+    ``attn_bias``: a dense additive bias / mask, scaled_dot_product_attention's ``attn_mask`` — a 4-D tensor broadcastable to (B, H, Nq, Nk) (each of the first
+    two dims 1 or full; indexed by the QUERY head under GQA) of q's dtype or float32, added to the scaled scores before the mask and the softmax; the LSE
+    includes it; ``-inf`` entries mask, a row without a finite score gives out = 0 and lse = +inf; ``+inf`` and NaN are undefined.  A ``torch.bool`` tensor
+    is a mask (True = attend) and is converted to 0 / -inf in q's dtype with one elementwise op; a tensor whose base or strides miss the kernels' alignment
+    (16-byte base, unit stride along keys, other strides multiples of 8 elements) is copied once into a padded buffer.  The values are read by the kernels
+    only (tfa_fwd_bias): no host copy, no synchronisation.  float16 / bfloat16, head dims up to 128, any mask or window; not with ``alibi_slopes``,
+    ``softcap``, ``exact_max`` or split-KV arguments (ValueError), ``auto_split`` is ignored; a bias that requires grad is refused (RuntimeError): it gets
+    no gradient."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -191,6 +257,8 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
                   extra=((exact_max, "no exact_max form of the local kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
     if win == (-1, 0):                               # (the causal mask itself: tfa_fwd with is_causal)
         win, is_causal = None, True
+    bias = _attn_bias(attn_bias, B, H, Nq, Nk, q.device, q.dtype, D, alibi_slopes, softcap,
+                      extra=((exact_max, "no exact_max form of the bias kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
     alibi = _alibi(alibi_slopes, B, H, q.device, q.dtype, D,
                    extra=((exact_max, "no exact_max form of the ALiBi kernels"), (kv_offset != 0 or nk_total is not None, "no split-KV / partial passes")))
     cap = _softcap(softcap, q.dtype, D,
@@ -228,7 +296,8 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
     # tfa_fwd_splitkv's merge writes a dense (B,H,Nq,D) result: gate on the exact strides it checks (is_contiguous() ignores the
     # strides of size-1 dims, and Nq == 1 is the very shape auto-split targets)
     dense_out = (out.stride(3) == 1 and out.stride(2) == D and out.stride(1) == Nq * D and out.stride(0) == H * Nq * D)
-    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None and not cap) else 1
+    splits = L.tfa_fwd_suggest_splits(C.byref(p)) if (auto_split and layout == "bhnd" and dense_out and win is None and alibi is None and not cap and
+                                                       bias is None) else 1
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
         if splits > 1:
@@ -238,7 +307,7 @@ def flash_attn_fwd(q, k, v, is_causal=False, softmax_scale=None, *, layout="bhnd
             ws = torch.empty((int(need),), dtype=torch.float32, device=q.device)
             _lib.check(L.tfa_fwd_splitkv(C.byref(p), int(splits), ws.data_ptr(), C.c_void_p(stream)))
         else:
-            _call_form("tfa_fwd", p, stream, win, alibi, cap, is_causal)
+            _call_form("tfa_fwd", p, stream, win, alibi, cap, is_causal, bias)
     return out, lse
 
 
@@ -346,7 +415,7 @@ def make_bwd_params(q, k, v, out, lse, dout, dq, dk, dv, delta, is_causal, softm
 
 
 def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None, *, layout="bhnd", grad_f32=False, workspace=None, window_size=(-1, -1),
-                   softcap=0.0, alibi_slopes=None):
+                   attn_bias=None, softcap=0.0, alibi_slopes=None):
     """Backward of ``flash_attn_fwd``: returns ``(dq, dk, dv)`` shaped like q, k, v (fp32 when ``grad_f32``).
     ``out`` and ``lse`` are the forward's results for the same q, k, v; ``dout`` is the upstream gradient
     (shape/dtype of ``out``).  The reference has no backward — it only saves the LSE for one
@@ -355,7 +424,8 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
     or a caller-owned uint8 / any-dtype CUDA tensor of at least that many bytes: tfa_bwd then keeps dS and executes 5 GEMMs.
     ``window_size``: the forward's sliding window (tfa_bwd_local; no workspace form).
     ``alibi_slopes``: the forward's ALiBi slopes (tfa_bwd_alibi; no workspace form); they receive no gradient.
-    ``softcap``: the forward's soft cap (tfa_bwd_softcap; no workspace form): dS is multiplied by 1 - tanh^2 on its way to dq and dk; no gradient for it."""
+    ``softcap``: the forward's soft cap (tfa_bwd_softcap; no workspace form): dS is multiplied by 1 - tanh^2 on its way to dq and dk; no gradient for it.
+    ``attn_bias``: the forward's dense bias / mask (tfa_bwd_bias; no workspace form; checked and prepared as in ``flash_attn_fwd``); it receives no gradient."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (dout, "dout")):
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
@@ -378,6 +448,8 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
     win = _window(window_size, is_causal, nq, nk, q.dtype, D, extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     if win == (-1, 0):
         win, is_causal = None, True
+    bias = _attn_bias(attn_bias, q.shape[0], lse_shape[1], nq, nk, q.device, q.dtype, D, alibi_slopes, softcap,
+                      extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     alibi = _alibi(alibi_slopes, q.shape[0], lse_shape[1], q.device, q.dtype, D,
                    extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
     cap = _softcap(softcap, q.dtype, D, extra=((workspace is not None and workspace is not False, "no dS-workspace form"),))
@@ -398,7 +470,7 @@ def flash_attn_bwd(q, k, v, out, lse, dout, is_causal=False, softmax_scale=None,
         p.workspace_bytes = workspace.numel() * workspace.element_size()
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _call_form("tfa_bwd", p, stream, win, alibi, cap, is_causal)
+        _call_form("tfa_bwd", p, stream, win, alibi, cap, is_causal, bias)
     return dq, dk, dv
 
 
@@ -463,20 +535,23 @@ class _FlashAttnBNHD(torch.autograd.Function):
     """autograd glue for ``flash_attn_func``: forward = tfa_fwd, backward = tfa_bwd, both on (B,N,H,D) views."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1), softcap=0.0, alibi_slopes=None):
-        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
-        ctx.save_for_backward(q, k, v, out, lse, alibi_slopes)   # (the slopes, or None: they get no gradient)
+    def forward(ctx, q, k, v, causal, softmax_scale, window_size=(-1, -1), attn_bias=None, softcap=0.0, alibi_slopes=None):
+        if attn_bias is not None:                        # (checked and prepared once: the backward reads the tensor the forward read)
+            attn_bias = _attn_bias(attn_bias, q.shape[0], q.shape[2], q.shape[1], k.shape[1], q.device, q.dtype, q.shape[3], alibi_slopes, softcap)[0]
+        out, lse = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", window_size=window_size, attn_bias=attn_bias, alibi_slopes=alibi_slopes,
+                                  softcap=softcap)
+        ctx.save_for_backward(q, k, v, out, lse, alibi_slopes, attn_bias)   # (the slopes and the bias, or None: they get no gradient)
         ctx.causal, ctx.scale, ctx.window, ctx.softcap = causal, softmax_scale, window_size, softcap
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse, slopes = ctx.saved_tensors
+        q, k, v, out, lse, slopes, bias = ctx.saved_tensors
         if dout.stride(3) != 1:
             dout = dout.contiguous()
-        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, alibi_slopes=slopes,
-                                    softcap=ctx.softcap)
-        return dq, dk, dv, None, None, None, None, None   # (causal, scale, window, softcap, slopes: no gradient)
+        dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, attn_bias=bias,
+                                    alibi_slopes=slopes, softcap=ctx.softcap)
+        return dq, dk, dv, None, None, None, None, None, None   # (causal, scale, window, bias, softcap, slopes: no gradient)
 
 
 def _positional_slopes(extra, alibi_slopes, name):
@@ -486,7 +561,7 @@ def _positional_slopes(extra, alibi_slopes, name):
     return extra[0] if extra else alibi_slopes
 
 
-def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1), *extra, softcap=0.0, alibi_slopes=None):
+def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, -1), *extra, attn_bias=None, softcap=0.0, alibi_slopes=None):
     """(B,N,H,D)-layout entry with the signature the reference's scripts use for comparison
     (flash_attention_cutlass/test.py:71-76, flash_attention_py/main_torch_only.py:304);
     supports GQA/MQA (fewer K/V heads).  Differentiable (like the official function the reference
@@ -495,12 +570,19 @@ def flash_attn_func(q, k, v, causal=False, softmax_scale=None, window_size=(-1, 
     ALiBi, float32 (H,) or (B, H): ``-slope * |i + (Nk - Nq) - j|`` added to the scaled scores (tfa_fwd_alibi / tfa_bwd_alibi); no gradient for them.
     ``softcap``: FlashAttention-2's tanh logit capping (Gemma-2 style), a host float, 0.0 = none: scaled scores x become ``softcap * tanh(x / softcap)`` before
     the ALiBi bias and the mask (cap, then bias, then mask); differentiable through the cap (tfa_fwd_softcap / tfa_bwd_softcap), no gradient for the value itself.
-    ``softcap`` is keyword-only; ``alibi_slopes`` stays the last parameter and may still be passed as the positional argument behind ``window_size``."""
+    ``softcap`` is keyword-only; ``alibi_slopes`` stays the last parameter and may still be passed as the positional argument behind ``window_size``.
+    ``attn_bias`` (keyword-only): a dense additive bias / mask as scaled_dot_product_attention's ``attn_mask`` — 4-D, broadcastable to (B, H, Nq, Nk) with each
+    of the first two dims 1 or full (the QUERY head under GQA), of q's dtype or float32, added to the scaled scores before ``causal`` / ``window_size``;
+    ``-inf`` masks, a fully masked row gives 0; ``+inf`` / NaN are undefined.  A ``torch.bool`` tensor (True = attend) is converted to 0 / -inf in q's dtype
+    with one elementwise op, and a tensor that misses the kernels' alignment (16-byte base, strides multiples of 8 elements, unit stride along keys) is
+    copied once into a padded buffer.  Differentiable in q, k, v (tfa_fwd_bias / tfa_bwd_bias); the bias itself gets no gradient and one that requires
+    grad is refused (RuntimeError).  Not with ``alibi_slopes`` or ``softcap`` (ValueError).  ``None``: the call above, unchanged."""
     alibi_slopes = _positional_slopes(extra, alibi_slopes, "flash_attn_func")
     window_size = tuple(window_size)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size, softcap, alibi_slopes)
-    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size, alibi_slopes=alibi_slopes, softcap=softcap)
+        return _FlashAttnBNHD.apply(q, k, v, bool(causal), softmax_scale, window_size, attn_bias, softcap, alibi_slopes)
+    out, _ = flash_attn_fwd(q, k, v, causal, softmax_scale, layout="bnhd", return_lse=False, window_size=window_size, attn_bias=attn_bias,
+                            alibi_slopes=alibi_slopes, softcap=softcap)
     return out
 
 
