@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -451,8 +451,8 @@ int tfa_bwd_varlen(const tfa_varlen_bwd_params* p, void* stream);
  * Refused: a NULL pg or block_table (TFA_ERR_NULL); page_size not a positive multiple of 64, max_blocks or num_pages <= 0 (TFA_ERR_SHAPE); flags != 0
  * (TFA_ERR_SHAPE); a table that is not 4-byte aligned (TFA_ERR_ALIGN); negative or misaligned table / page strides (TFA_ERR_STRIDE); and what tfa_fwd_varlen
  * refuses (D > 128, fp32 inputs, a variant other than 30 / 32).
- * Out of scope: a backward; paged K/V combined with windows, softcap or ALiBi; fp8 page pools; seqused_k; an append for packed new rows
- * (tfa_kvcache_append serves one row count per batch); a hand-scheduled paged tile loop; D > 128.
+ * Out of scope: a backward; paged K/V combined with windows, softcap or ALiBi; fp8 page pools; seqused_k; a hand-scheduled paged tile loop; D > 128.
+ * (The append for packed new rows is tfa_kvcache_append_varlen, below; tfa_kvcache_append serves one row count per batch.)
  * Measured: profiles/varlen_paged_bench.txt (tools/bench_varlen_paged.py), quoted in README.md and DESIGN.md 8g. */
 typedef struct tfa_paged_kv {
   const int32_t* block_table;  /* device int32 (B, max_blocks), unit stride along max_blocks */
@@ -680,7 +680,8 @@ int tfa_bwd_bias_plan(const tfa_bwd_params* p, const tfa_attn_bias* bias, int wi
  * contiguous (b, h) slice — or a page — that does not fit one 2 GiB descriptor, out not contiguous (B, H, Nq, D) with splits >= 2 (TFA_ERR_STRIDE); base
  * pointers not 16-byte aligned, block_table / cache_seqlens / lse not 4-byte aligned, a misaligned workspace (TFA_ERR_ALIGN); a NULL workspace with
  * splits >= 2 (TFA_ERR_NULL); softmax_scale not finite or <= 0 (TFA_ERR_SCALE).
- * Out of scope: rotary embedding, cache_batch_idx, cache_leftpad, windows, softcap, ALiBi, head dims above 128, fp32 inputs, TFA_FWD_EXACT_MAX, a backward.
+ * Out of scope: rotary embedding inside the call (done by composition: tfa_rotary on q and k_new with seqlen_offsets = cache_seqlens, then this call), cache_batch_idx,
+ * cache_leftpad, windows, softcap, ALiBi, head dims above 128, fp32 inputs, TFA_FWD_EXACT_MAX, a backward.
  * Tolerances: the header's "which tolerance each path guarantees".  Measured: profiles/kvcache_bench.txt (tools/bench_kvcache.py), quoted in README.md. */
 typedef struct tfa_kvcache_params {
   const void* q;                 /* (B, H, Nq, D) by q_stride */
@@ -767,6 +768,111 @@ int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, 
 long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits);
 int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes);
 int tfa_kvcache_append_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
+
+/* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
+ * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the
+ * same launch (q and k of one step).  16-bit elements, any batch / head / row strides (elements), unit stride along D: a slice of a packed QKV projection works.
+ *   Position: row t of sequence b has pos = seqlen_offsets[b] + t (device int32, B entries — cache_seqlens is the intended argument) or seqlen_offset + t when
+ *     seqlen_offsets is NULL.  Packed: t = row - cu_seqlens[b], b found on the device by a binary search of cu_seqlens (B + 1 entries) whose answer is verified.
+ *     Nothing is read on the host: no copy, no synchronisation, capturable in a graph and replayable after the offsets were overwritten in place.
+ *   Definition, in fp32, every output element rounded once (to nearest even): with (x1, x2) = elements (i, i + rotary_dim / 2) (interleaved = 0, GPT-NeoX) or
+ *     (2i, 2i + 1) (interleaved = 1, GPT-J), c = cos[pos, i], s = sin[pos, i] (s = -sin[pos, i] with conjugate = 1: the backward of the rotation):
+ *       o1 = x1 * c - x2 * s,   o2 = x1 * s + x2 * c      computed as fma(x1, c, -(x2 * s)) and fma(x1, s, x2 * c);
+ *     elements [rotary_dim, D) are copied.  Copied bit for bit as well: a row whose pos lies outside [0, seqlen_ro); a packed row outside every sequence (rows behind
+ *     cu_seqlens[B]); a row whose search fails because cu_seqlens is not monotonic.  No value of cu_seqlens or seqlen_offsets causes an access outside x, out, cos, sin.
+ *   cos / sin: (seqlen_ro, rotary_dim / 2) of x's dtype or fp32 (cs_dtype), rows cos_stride / sin_stride elements apart, 16-byte aligned rows and bases.
+ *   In place (out == x with the same strides; likewise out2 == x2): the thread that stores a chunk loaded it, so there is nothing to order; the chunks behind
+ *     rotary_dim and the unrotated rows are then not touched.  x and out must otherwise not overlap.
+ * Kernel (csrc/tfa_rotary.hip): one work item per (row, head, pair of 16-byte chunks) — two loads and two stores (GPT-NeoX), one each (GPT-J) —, 256 threads a block,
+ * items of one row adjacent so its heads share the cos / sin reads; no LDS, no trigonometry.  _plan reports ceil(rows * (H + H2) * items / 256) blocks, items =
+ * rotary_dim / 16 + (D - rotary_dim) / 8 (GPT-NeoX) or D / 8 (GPT-J).  The pair arithmetic is csrc/tfa_rotary.h's, shared with tfa_kvcache_append_varlen.
+ * Refused, nothing launched: a NULL params / x / out / cos / sin, one of x2 / out2 without the other (TFA_ERR_NULL); dtype not TFA_F16 / TFA_BF16, cs_dtype neither
+ * dtype nor TFA_F32 (TFA_ERR_DTYPE); D not a positive multiple of 8, rotary_dim not a multiple of 16 in [16, D] (TFA_ERR_HEAD_DIM); B, N, H, seqlen_ro <= 0, H2 < 0, H2 > 0
+ * without x2 or x2 with H2 = 0, interleaved / conjugate not 0 or 1, a grid of 2^31 blocks or more (TFA_ERR_SHAPE); a stride negative or not a multiple of 16 bytes,
+ * a table row stride below rotary_dim / 2, out == x with other strides (TFA_ERR_STRIDE); a tensor or table base not 16-byte aligned, seqlen_offsets / cu_seqlens not
+ * 4-byte aligned (TFA_ERR_ALIGN).
+ * Out of scope: fp32 / fp8 x, rotary_dim not a multiple of 16, gradients of cos / sin, trigonometry on the device, a rotation fused into an attention kernel.
+ * Tolerance (tests/test_rotary_gpu.py): |out - exact| <= ulp(exact) / 2 + 2^-21 * (|x1| + |x2|).  Measured: profiles/rotary_append_bench.txt (tools/bench_rotary_append.py), quoted in README.md. */
+typedef struct tfa_rotary_params {
+  const void* x;                  /* (B, N, H, D) by x_stride, or packed (N, H, D) with cu_seqlens: N = total rows, x_stride[0] ignored */
+  void* out;                      /* same shape by o_stride; may be x */
+  const void* x2;                 /* optional second tensor, H2 heads, or NULL */
+  void* out2;
+  const void* cos;                /* (seqlen_ro, rotary_dim / 2) of cs_dtype */
+  const void* sin;
+  const int32_t* seqlen_offsets;  /* device, B entries, or NULL: seqlen_offset for every sequence */
+  const int32_t* cu_seqlens;      /* device, B + 1 entries, or NULL */
+  int32_t B;
+  int32_t N;                      /* rows per sequence; packed: rows in all */
+  int32_t H, H2, D, rotary_dim, seqlen_ro;
+  int32_t seqlen_offset;          /* host offset, used when seqlen_offsets is NULL */
+  int64_t x_stride[3];            /* batch, head, row (elements) */
+  int64_t o_stride[3];
+  int64_t x2_stride[3];
+  int64_t o2_stride[3];
+  int64_t cos_stride;             /* elements between the rows of cos */
+  int64_t sin_stride;
+  int32_t dtype;                  /* TFA_F16 or TFA_BF16: x, out, x2, out2 */
+  int32_t cs_dtype;               /* dtype, or TFA_F32 */
+  int32_t interleaved;            /* 0: GPT-NeoX pairs (i, i + rotary_dim / 2); 1: GPT-J pairs (2i, 2i + 1) */
+  int32_t conjugate;              /* 1: rotate by -angle (sin negated) */
+} tfa_rotary_params;
+/* On `stream`, asynchronous, never allocates, never reads device memory on the host. */
+int tfa_rotary(const tfa_rotary_params* p, void* stream);
+/* Validate *p without launching (no GPU needed); on success optionally reports the launch's geometry. */
+int tfa_rotary_plan(const tfa_rotary_params* p, int* grid, int* block);
+
+/* ---- packed new K/V rows into a paged or contiguous cache (the append of a unified batch: chunked prefill and decode rows in one call) ---------------
+ * k / v: (total_new, Hk, D) packed, strides {head, row} in elements, unit stride along D; sequence b owns rows [cu_seqlens[b], cu_seqlens[b+1]); row t of
+ * sequence b goes to key position pos = cache_seqlens[b] + t of the cache — paged (num_pages, page_size, Hk, D) through block_table, or contiguous
+ * (B, capacity, Hk, D) with block_table NULL; cache strides {page or batch, head, row} as in tfa_kvcache_params, capacity = max_blocks * page_size when paged.
+ * cu_seqlens (B + 1), cache_seqlens (B) and block_table are device int32 and read on the device only: no copy, no synchronisation, capturable in a graph.
+ * The row's sequence is found by a binary search of cu_seqlens whose answer is verified.  Dropped, exactly as tfa_kvcache_append drops: a position below 0 or at /
+ * beyond the capacity; a block-table entry outside [0, num_pages); and a packed row outside every sequence (padding behind cu_seqlens[B], a cu_seqlens that is not
+ * monotonic).  Nothing is ever stored outside the cache tensors, whatever the three arrays hold.  cache_seqlens is not advanced.  Two rows that map to one slot
+ * leave either one there.  k / v must not overlap the caches.
+ * rotary_cos / rotary_sin (both or neither; tfa_rotary's tables, cs_dtype, strides, rotary_dim, seqlen_ro, rotary_interleaved): K is rotated at its key position pos
+ * on the way in — FlashAttention-2's rule for the cache — by the device functions tfa_rotary runs, V is copied: the cache holds the bits that tfa_rotary(k,
+ * cu_seqlens, seqlen_offsets = cache_seqlens) followed by the plain append leaves (a pos at or beyond seqlen_ro: stored unrotated).
+ * Kernel (csrc/tfa_kvcache_append_varlen.hip): one thread per (row, K/V head, 16-byte chunk), one K and one V store; a thread of K's rotated part loads its
+ * partner chunk too.  _plan reports ceil(total_new * Hk * D / 8 / 256) blocks of 256 threads.
+ * Refused, nothing launched — tfa_kvcache_append's codes: a NULL params / k / v / cache / cu_seqlens / cache_seqlens, one rotary table without the other
+ * (TFA_ERR_NULL); dtype not TFA_F16 / TFA_BF16, cs_dtype neither dtype nor TFA_F32 (TFA_ERR_DTYPE); D not a multiple of 8 in [8, 128], rotary_dim not a multiple of
+ * 16 in [16, D] (TFA_ERR_HEAD_DIM); B, total_new, Hk, capacity <= 0, paged: page_size not a positive multiple of 64, capacity not a multiple of it, num_pages <= 0,
+ * with tables seqlen_ro <= 0, rotary_interleaved not 0 or 1, reserved_ != 0 (TFA_ERR_SHAPE); strides negative or not multiples of 16 bytes, row strides below D,
+ * block_table_stride < capacity / page_size, a table row stride below rotary_dim / 2 (TFA_ERR_STRIDE); bases not 16-byte aligned, the int32 arrays not 4-byte aligned
+ * (TFA_ERR_ALIGN).
+ * Out of scope: fp8 caches (tfa_fwd_varlen_paged reads 16-bit pools only), a rotation of anything but K, advancing cache_seqlens.
+ * Measured: profiles/rotary_append_bench.txt (tools/bench_rotary_append.py), quoted in README.md. */
+typedef struct tfa_kvcache_append_varlen_params {
+  const void* k;                  /* (total_new, Hk, D) by k_stride */
+  const void* v;
+  void* k_cache;
+  void* v_cache;
+  const int32_t* cu_seqlens;      /* device, B + 1 entries */
+  const int32_t* cache_seqlens;   /* device, B entries */
+  const int32_t* block_table;     /* device (B, max_blocks) int32, or NULL: contiguous cache */
+  const void* rotary_cos;         /* (seqlen_ro, rotary_dim / 2) of cs_dtype, or NULL */
+  const void* rotary_sin;
+  int32_t B, total_new, Hk, D;
+  int32_t capacity;               /* keys a sequence can hold: the contiguous cache's rows, or max_blocks * page_size */
+  int32_t page_size;              /* paged: keys per page, a positive multiple of 64; contiguous: ignored */
+  int32_t num_pages;              /* paged: pages in the caches; contiguous: ignored */
+  int32_t rotary_dim, seqlen_ro;  /* with tables only */
+  int32_t rotary_interleaved;
+  int32_t dtype;                  /* TFA_F16 or TFA_BF16: k, v, caches */
+  int32_t cs_dtype;               /* with tables: dtype, or TFA_F32 */
+  int64_t k_stride[2];            /* head, row (elements) */
+  int64_t v_stride[2];
+  int64_t kc_stride[3];           /* batch (contiguous) or page (paged), head, row */
+  int64_t vc_stride[3];
+  int64_t block_table_stride;     /* elements between the rows of block_table */
+  int64_t cos_stride;             /* elements between the rows of rotary_cos */
+  int64_t sin_stride;
+  int64_t reserved_;              /* must be 0 */
+} tfa_kvcache_append_varlen_params;
+int tfa_kvcache_append_varlen(const tfa_kvcache_append_varlen_params* p, void* stream);
+int tfa_kvcache_append_varlen_plan(const tfa_kvcache_append_varlen_params* p, int* grid, int* block);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen
 (GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.  ``flash_attn_func`` also
 takes ``attn_bias``: a dense additive bias or mask as scaled_dot_product_attention's ``attn_mask`` (fixed-length calls; no gradient for the bias).
 Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append; 16-bit or fp8 e4m3 caches with ``k_descale`` / ``v_descale``).
+Around attention: ``apply_rotary_emb`` / ``apply_rotary_emb_qk_`` (rotary embedding at device-side positions) and ``kvcache_append_varlen`` (a unified batch's
+new K/V rows into a paged or contiguous cache, K optionally rotated on the way in) — with the two attention calls a whole decode or chunked-prefill step.
 """
 from .ops import (  # noqa: F401
     flash_attention_v2_cutlass,
@@ -32,6 +34,9 @@ from .ops import (  # noqa: F401
     flash_attn_varlen_fwd,
     flash_attn_varlen_bwd,
     flash_attn_with_kvcache,
+    apply_rotary_emb,
+    apply_rotary_emb_qk_,
+    kvcache_append_varlen,
 )
 from . import _lib  # noqa: F401
 
@@ -51,4 +56,7 @@ __all__ = [
     "flash_attn_varlen_fwd",
     "flash_attn_varlen_bwd",
     "flash_attn_with_kvcache",
+    "apply_rotary_emb",
+    "apply_rotary_emb_qk_",
+    "kvcache_append_varlen",
 ]

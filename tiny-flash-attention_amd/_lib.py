@@ -99,6 +99,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_fp8_workspace",
     "tfa_fwd_kvcache_fp8_plan",
     "tfa_kvcache_append_fp8",
+    "tfa_rotary",
+    "tfa_rotary_plan",
+    "tfa_kvcache_append_varlen",
+    "tfa_kvcache_append_varlen_plan",
 )
 
 
@@ -324,6 +328,75 @@ class TfaKvcacheFp8(C.Structure):
     ]
 
 
+class TfaRotaryParams(C.Structure):
+    """struct tfa_rotary_params (include/tfa.h): rotary embedding of one tensor, or of two (q and k) in one launch."""
+
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("out", C.c_void_p),
+        ("x2", C.c_void_p),
+        ("out2", C.c_void_p),
+        ("cos", C.c_void_p),
+        ("sin", C.c_void_p),
+        ("seqlen_offsets", C.c_void_p),
+        ("cu_seqlens", C.c_void_p),
+        ("B", C.c_int32),
+        ("N", C.c_int32),
+        ("H", C.c_int32),
+        ("H2", C.c_int32),
+        ("D", C.c_int32),
+        ("rotary_dim", C.c_int32),
+        ("seqlen_ro", C.c_int32),
+        ("seqlen_offset", C.c_int32),
+        ("x_stride", C.c_int64 * 3),
+        ("o_stride", C.c_int64 * 3),
+        ("x2_stride", C.c_int64 * 3),
+        ("o2_stride", C.c_int64 * 3),
+        ("cos_stride", C.c_int64),
+        ("sin_stride", C.c_int64),
+        ("dtype", C.c_int32),
+        ("cs_dtype", C.c_int32),
+        ("interleaved", C.c_int32),
+        ("conjugate", C.c_int32),
+    ]
+
+
+class TfaKvcacheAppendVarlenParams(C.Structure):
+    """struct tfa_kvcache_append_varlen_params (include/tfa.h): packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in."""
+
+    _fields_ = [
+        ("k", C.c_void_p),
+        ("v", C.c_void_p),
+        ("k_cache", C.c_void_p),
+        ("v_cache", C.c_void_p),
+        ("cu_seqlens", C.c_void_p),
+        ("cache_seqlens", C.c_void_p),
+        ("block_table", C.c_void_p),
+        ("rotary_cos", C.c_void_p),
+        ("rotary_sin", C.c_void_p),
+        ("B", C.c_int32),
+        ("total_new", C.c_int32),
+        ("Hk", C.c_int32),
+        ("D", C.c_int32),
+        ("capacity", C.c_int32),
+        ("page_size", C.c_int32),
+        ("num_pages", C.c_int32),
+        ("rotary_dim", C.c_int32),
+        ("seqlen_ro", C.c_int32),
+        ("rotary_interleaved", C.c_int32),
+        ("dtype", C.c_int32),
+        ("cs_dtype", C.c_int32),
+        ("k_stride", C.c_int64 * 2),
+        ("v_stride", C.c_int64 * 2),
+        ("kc_stride", C.c_int64 * 3),
+        ("vc_stride", C.c_int64 * 3),
+        ("block_table_stride", C.c_int64),
+        ("cos_stride", C.c_int64),
+        ("sin_stride", C.c_int64),
+        ("reserved_", C.c_int64),
+    ]
+
+
 class TfaError(RuntimeError):
     def __init__(self, status, text):
         super().__init__(f"tfa status {status}: {text}")
@@ -474,6 +547,12 @@ def lib():
     L.tfa_fwd_kvcache_fp8_plan.argtypes = [PK, P8, C.c_int, IP, IP, IP]
     L.tfa_kvcache_append_fp8.restype = C.c_int
     L.tfa_kvcache_append_fp8.argtypes = [PK, P8, C.c_void_p]
+    # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
+    PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
+    for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),
+                       ("tfa_kvcache_append_varlen", [PA, C.c_void_p]), ("tfa_kvcache_append_varlen_plan", [PA, IP, IP])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
     _lib = L
     return L
 

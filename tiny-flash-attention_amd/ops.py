@@ -1036,3 +1036,278 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
             _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
     out = dense.transpose(1, 2)
     return (out, lse) if return_softmax_lse else out
+
+
+# ---- the serving step's parts around attention: rotary embedding and the packed append (tfa_rotary, tfa_kvcache_append_varlen) ------------------------------
+def _rotary_tables(name, cos, sin, dtype, D, device, cos_name="cos", sin_name="sin"):
+    """Checks of a (seqlen_ro, rotary_dim / 2) table pair against a tensor of `dtype` and head dim D; returns the pair with 16-byte aligned rows and bases
+    (made contiguous once if a row stride or base misses that) and rotary_dim, seqlen_ro."""
+    for n, t in ((cos_name, cos), (sin_name, sin)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {n} must be a tensor (got {type(t).__name__})")
+    if cos.dim() != 2 or sin.dim() != 2:
+        raise ValueError(f"{name}: {cos_name} / {sin_name} must be 2-D (seqlen_ro, rotary_dim / 2) (got {tuple(cos.shape)}, {tuple(sin.shape)})")
+    if cos.shape != sin.shape or cos.dtype != sin.dtype:
+        raise ValueError(f"{name}: {cos_name} and {sin_name} must have one shape and dtype (got {tuple(cos.shape)} {cos.dtype}, {tuple(sin.shape)} {sin.dtype})")
+    if cos.dtype != dtype and cos.dtype != torch.float32:
+        raise ValueError(f"{name}: {cos_name} / {sin_name} must have x's dtype {dtype} or float32 (got {cos.dtype})")
+    if cos.device != device or sin.device != device:
+        raise ValueError(f"{name}: {cos_name} / {sin_name} must be on x's device")
+    seqlen_ro, rotary_dim = cos.shape[0], 2 * cos.shape[1]
+    if rotary_dim % 16 != 0 or rotary_dim < 16:
+        raise ValueError(f"{name}: rotary_dim must be a positive multiple of 16 (got {rotary_dim})")
+    if rotary_dim > D:
+        raise ValueError(f"{name}: rotary_dim must not exceed the head dim {D} (got {rotary_dim})")
+    if seqlen_ro < 1:
+        raise ValueError(f"{name}: {cos_name} / {sin_name} hold no position")
+    fixed = []
+    for t in (cos, sin):
+        if t.stride(1) != 1 or (t.stride(0) * t.element_size()) % 16 != 0 or t.data_ptr() % 16 != 0:
+            t = t.contiguous()
+        fixed.append(t)
+    return fixed[0], fixed[1], rotary_dim, seqlen_ro
+
+
+def _int32_vector(name, what, t, n, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name}: {what} must be a contiguous int32 tensor of shape ({n},) on x's device")
+
+
+def _check_rotary_x(name, n, x, cu_seqlens):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: {n} must be a tensor (got {type(x).__name__})")
+    if x.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {x.dtype} for {n}; no fp32 / fp8 rotary path)")
+    want = 3 if cu_seqlens is not None else 4
+    if x.dim() != want:
+        raise ValueError(f"{name}: {n} must be " + ("3-D (total, H, D) with cu_seqlens" if want == 3 else "4-D (B, N, H, D) (packed (total, H, D) takes cu_seqlens)")
+                         + f" (got {tuple(x.shape)})")
+    if not x.is_cuda:
+        raise RuntimeError(f"{n} must be a CUDA tensor")
+    D = x.shape[-1]
+    if D % 8 != 0 or D < 8:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
+    if x.stride(-1) != 1 or any(s % 8 != 0 for s in x.stride()[:-1]):
+        raise ValueError(f"{name}: {n} must have unit stride along the head dim and 16-byte aligned rows (strides multiples of 8 elements; got {x.stride()})")
+    if min(x.shape) < 1:
+        raise ValueError(f"{name}: {n} is empty (got {tuple(x.shape)})")
+
+
+def _rotary_params(name, xs, outs, cos, sin, interleaved, conjugate, seqlen_offsets, cu_seqlens):
+    """A TfaRotaryParams for one or two (x, out) pairs that passed _check_rotary_x; checks the tables, the offsets and cu_seqlens."""
+    x = xs[0]
+    D = x.shape[-1]
+    cos, sin, rotary_dim, seqlen_ro = _rotary_tables(name, cos, sin, x.dtype, D, x.device)
+    if cu_seqlens is not None:
+        if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2 \
+                or not cu_seqlens.is_contiguous() or cu_seqlens.device != x.device:
+            raise ValueError(f"{name}: cu_seqlens must be a contiguous int32 tensor of B + 1 entries on x's device")
+        B, N = cu_seqlens.shape[0] - 1, x.shape[0]
+    else:
+        B, N = x.shape[0], x.shape[1]
+    p = _lib.TfaRotaryParams()
+    if isinstance(seqlen_offsets, torch.Tensor):
+        _int32_vector(name, "seqlen_offsets", seqlen_offsets, B, x.device)
+        p.seqlen_offsets = seqlen_offsets.data_ptr()
+    elif isinstance(seqlen_offsets, int) and not isinstance(seqlen_offsets, bool) and -2 ** 31 <= seqlen_offsets < 2 ** 31:
+        p.seqlen_offsets, p.seqlen_offset = None, seqlen_offsets
+    else:
+        raise ValueError(f"{name}: seqlen_offsets must be a host int or a contiguous int32 tensor of shape ({B},) on x's device")
+    p.x, p.out = x.data_ptr(), outs[0].data_ptr()
+    p.cos, p.sin = cos.data_ptr(), sin.data_ptr()
+    p.cu_seqlens = cu_seqlens.data_ptr() if cu_seqlens is not None else None
+    p.B, p.N, p.H, p.D, p.rotary_dim, p.seqlen_ro = B, N, x.shape[-2], D, rotary_dim, seqlen_ro
+    p.cos_stride, p.sin_stride = cos.stride(0), sin.stride(0)
+    pairs = [("x_stride", x), ("o_stride", outs[0])]
+    if len(xs) == 2:
+        p.x2, p.out2, p.H2 = xs[1].data_ptr(), outs[1].data_ptr(), xs[1].shape[-2]
+        pairs += [("x2_stride", xs[1]), ("o2_stride", outs[1])]
+    for field, t in pairs:
+        arr = getattr(p, field)
+        if cu_seqlens is not None:
+            arr[0], arr[1], arr[2] = 0, t.stride(1), t.stride(0)                 # (total, H, D): head, row
+        else:
+            arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)      # (B, N, H, D): batch, head, row
+    p.dtype = _DT[x.dtype]
+    p.cs_dtype = _lib.TFA_F32 if cos.dtype == torch.float32 else p.dtype
+    p.interleaved, p.conjugate = (1 if interleaved else 0), (1 if conjugate else 0)
+    return p, (cos, sin)
+
+
+def _rotary_launch(p, device):
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().tfa_rotary(C.byref(p), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+
+class _ApplyRotaryEmb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cos, sin, interleaved, inplace, seqlen_offsets, cu_seqlens):
+        out = x if inplace else torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        p, keep = _rotary_params("apply_rotary_emb", (x,), (out,), cos, sin, interleaved, False, seqlen_offsets, cu_seqlens)
+        _rotary_launch(p, x.device)
+        tensors = [keep[0], keep[1]]
+        ctx.has_cu, ctx.offsets = cu_seqlens is not None, seqlen_offsets
+        if cu_seqlens is not None:
+            tensors.append(cu_seqlens)
+        if isinstance(seqlen_offsets, torch.Tensor):
+            tensors.append(seqlen_offsets)
+            ctx.offsets = None
+        ctx.save_for_backward(*tensors)
+        ctx.interleaved = interleaved
+        if inplace:
+            ctx.mark_dirty(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = list(ctx.saved_tensors)
+        cos, sin = saved[0], saved[1]
+        cu = saved[2] if ctx.has_cu else None
+        offsets = ctx.offsets if ctx.offsets is not None else saved[-1]
+        # the conjugate rotation of the incoming gradient.  In place only on a buffer this function owns — the copy it had to make of a gradient whose layout the
+        # kernel does not take; a gradient autograd hands over may be shared with other consumers and is read, never written
+        if dout.stride(-1) != 1 or any(s % 8 != 0 for s in dout.stride()[:-1]) or dout.data_ptr() % 16 != 0:
+            dout = dout.contiguous() if not dout.is_contiguous() else dout.clone()
+            dx = dout
+        else:
+            dx = torch.empty(dout.shape, dtype=dout.dtype, device=dout.device)
+        p, _ = _rotary_params("apply_rotary_emb (backward)", (dout,), (dx,), cos, sin, ctx.interleaved, True, offsets, cu)
+        _rotary_launch(p, dout.device)
+        return dx, None, None, None, None, None, None
+
+
+def apply_rotary_emb(x, cos, sin, interleaved=False, inplace=False, seqlen_offsets=0, cu_seqlens=None, max_seqlen=None):
+    """FlashAttention-2's ``apply_rotary_emb`` as a HIP kernel (tfa_rotary): rotary position embedding of ``x``.
+
+    ``x`` (B, N, H, D), or packed (total, H, D) with ``cu_seqlens`` (int32, B + 1 entries, on the device); float16 / bfloat16, any strides with unit stride along D and
+    16-byte aligned rows — ``qkv[:, :, 0]`` of a packed projection works without a copy.  ``cos`` / ``sin`` (seqlen_ro, rotary_dim / 2) of x's dtype or float32,
+    rotary_dim a multiple of 16 and at most D, D a multiple of 8.  ``seqlen_offsets``: a host int or an int32 device tensor (B,) — ``cache_seqlens`` is the intended
+    argument; row t of sequence b is rotated at position ``seqlen_offsets[b] + t``.  Nothing is read on the host: the call does not synchronise and replays
+    correctly in a captured graph after the offsets were overwritten in place.  ``max_seqlen`` is accepted for signature compatibility and not needed.
+    fp32 arithmetic, one rounding per output element; pairs (i, i + rotary_dim / 2) (GPT-NeoX) or (2i, 2i + 1) with ``interleaved`` (GPT-J); elements behind
+    rotary_dim are copied, and so — bit for bit — are rows whose position lies outside [0, seqlen_ro) and packed rows that belong to no sequence.
+    ``inplace=True`` writes into x and returns it.  Differentiable in x (the backward is the conjugate rotation of the incoming gradient; cos, sin and the offsets
+    get no gradient)."""
+    name = "apply_rotary_emb"
+    _check_rotary_x(name, "x", x, cu_seqlens)
+    return _ApplyRotaryEmb.apply(x, cos, sin, bool(interleaved), bool(inplace), seqlen_offsets, cu_seqlens)
+
+
+def apply_rotary_emb_qk_(q, k, cos, sin, interleaved=False, seqlen_offsets=0, cu_seqlens=None):
+    """``apply_rotary_emb`` of q and k IN PLACE in ONE launch (tfa_rotary with its second tensor): q (B, N, H, D) and k (B, N, Hk, D) — or packed (total, H, D) /
+    (total, Hk, D) with ``cu_seqlens`` — rotated at the same positions, the bits two ``apply_rotary_emb(..., inplace=True)`` calls leave.  Returns (q, k).
+    Inference only: an input that requires grad raises."""
+    name = "apply_rotary_emb_qk_"
+    _check_rotary_x(name, "q", q, cu_seqlens)
+    _check_rotary_x(name, "k", k, cu_seqlens)
+    if k.dtype != q.dtype or k.device != q.device:
+        raise ValueError(f"{name}: q and k must share one dtype and device (got {q.dtype} on {q.device}, {k.dtype} on {k.device})")
+    if k.shape[:-2] != q.shape[:-2] or k.shape[-1] != q.shape[-1]:
+        raise ValueError(f"{name}: q and k must agree in everything but the head count (got {tuple(q.shape)}, {tuple(k.shape)})")
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad):
+        raise RuntimeError(f"{name} is inference-only: an input requires grad (use apply_rotary_emb, or run it under torch.no_grad())")
+    p, _ = _rotary_params(name, (q, k), (q, k), cos, sin, interleaved, False, seqlen_offsets, cu_seqlens)
+    _rotary_launch(p, q.device)
+    return q, k
+
+
+def _append_varlen_params(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved):
+    """A TfaKvcacheAppendVarlenParams for checked arguments: k / v (total, Hk, D), the caches (B | num_pages, rows, Hk, D), tables with aligned rows or None."""
+    total, Hk, D = k.shape
+    B = cu_seqlens.shape[0] - 1
+    capacity = block_table.shape[1] * k_cache.shape[1] if block_table is not None else k_cache.shape[1]
+    p = _lib.TfaKvcacheAppendVarlenParams()
+    p.k, p.v, p.k_cache, p.v_cache = k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+    p.cu_seqlens, p.cache_seqlens = cu_seqlens.data_ptr(), cache_seqlens.data_ptr()
+    p.B, p.total_new, p.Hk, p.D, p.capacity = B, total, Hk, D, capacity
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_size, p.num_pages = k_cache.shape[1], k_cache.shape[0]
+    else:
+        p.block_table = None
+    for field, t in (("k_stride", k), ("v_stride", v)):
+        arr = getattr(p, field)
+        arr[0], arr[1] = t.stride(1), t.stride(0)                               # (total, Hk, D): head, row
+    for field, t in (("kc_stride", k_cache), ("vc_stride", v_cache)):
+        arr = getattr(p, field)
+        arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)          # (B | pages, rows, Hk, D): batch / page, head, row
+    p.dtype = _DT[k.dtype]
+    if rotary_cos is not None:
+        p.rotary_cos, p.rotary_sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
+        p.cos_stride, p.sin_stride = rotary_cos.stride(0), rotary_sin.stride(0)
+        p.rotary_dim, p.seqlen_ro = 2 * rotary_cos.shape[1], rotary_cos.shape[0]
+        p.rotary_interleaved = 1 if rotary_interleaved else 0
+        p.cs_dtype = _lib.TFA_F32 if rotary_cos.dtype == torch.float32 else p.dtype
+    return p
+
+
+def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table=None, *, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+    """A unified batch's new K/V rows into a paged or contiguous cache (tfa_kvcache_append_varlen) — the append ``flash_attn_varlen_func(..., block_table=)`` needs.
+
+    ``k`` / ``v`` (total_new, Hk, D) packed, of the caches' 16-bit dtype, any strides with unit stride along D; ``cu_seqlens`` (B + 1,) and ``cache_seqlens`` (B,)
+    int32 on the device: sequence b owns rows [cu[b], cu[b+1]) and its row t goes to key position ``cache_seqlens[b] + t``.  The caches: paged
+    (num_pages, page_size, Hk, D) with ``block_table`` (B, max_blocks) int32 (page_size a multiple of 64), or contiguous (B, capacity, Hk, D).  Dropped: a position
+    below 0 or at / beyond the capacity, a row whose block-table entry is not a page of the pool, a packed row outside every sequence; nothing is stored outside
+    the caches.  ``cache_seqlens`` is not advanced.  Nothing is read on the host: no synchronisation, capturable in a graph.
+    ``rotary_cos`` / ``rotary_sin``: K is rotated at its key position on the way in (V is copied) — the bits ``apply_rotary_emb(k, cos, sin, cu_seqlens=cu_seqlens,
+    seqlen_offsets=cache_seqlens)`` followed by the plain append leaves; the query side is ``apply_rotary_emb(q, ..., cu_seqlens=cu_q, seqlen_offsets=cache_seqlens)``.
+    Not differentiable; fp8 caches are not served (the paged varlen attention reads 16-bit pools)."""
+    name = "kvcache_append_varlen"
+    for n, t in (("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens", cu_seqlens), ("cache_seqlens", cache_seqlens)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {n} must be a tensor (got {type(t).__name__})")
+    if k.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {k.dtype} for k)")
+    for n, t in (("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dtype != k.dtype:
+            raise TypeError(f"{name}: {n} must have k's dtype {k.dtype} (got {t.dtype}; fp8 caches are not served by the packed append)")
+    for n, t in (("k", k), ("v", v)):
+        if t.dim() != 3:
+            raise ValueError(f"{name}: {n} must be 3-D (total_new, Hk, D) (got {tuple(t.shape)})")
+    for n, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be a 4-D tensor (got {tuple(t.shape)})")
+    for n, t in (("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+    total, Hk, D = k.shape
+    if k.shape != v.shape or total < 1 or Hk < 1:
+        raise ValueError(f"{name}: k and v must have one non-empty shape (got {tuple(k.shape)}, {tuple(v.shape)})")
+    if D % 8 != 0 or D < 8 or D > 128:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 up to 128 (got {D})")
+    if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hk or k_cache.shape[3] != D:
+        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., {Hk}, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    for n, t in (("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.stride(-1) != 1 or any(s % 8 != 0 for s in t.stride()[:-1]) or t.device != k.device:
+            raise ValueError(f"{name}: {n} must be on k's device with unit stride along the head dim and 16-byte aligned rows (got strides {t.stride()})")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2 or not cu_seqlens.is_contiguous() or cu_seqlens.device != k.device:
+        raise ValueError(f"{name}: cu_seqlens must be a contiguous int32 tensor of B + 1 entries on k's device")
+    B = cu_seqlens.shape[0] - 1
+    if cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,) or not cache_seqlens.is_contiguous() or cache_seqlens.device != k.device:
+        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},) on k's device")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B \
+                or block_table.shape[1] < 1:
+            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks)")
+        if block_table.device != k.device or block_table.stride(1) != 1:
+            raise ValueError(f"{name}: block_table must be on k's device with unit stride along max_blocks")
+        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0 or k_cache.shape[0] < 1:
+            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
+        capacity = block_table.shape[1] * k_cache.shape[1]
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"{name}: a contiguous cache must have one slice per sequence ({B}; got {k_cache.shape[0]})")
+        capacity = k_cache.shape[1]
+    if capacity <= 0 or capacity >= 2 ** 31:
+        raise ValueError(f"{name}: the cache must hold between 1 and 2^31 - 1 keys per sequence (got {capacity})")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{name}: rotary_cos and rotary_sin must be given together")
+    if rotary_cos is not None:
+        rotary_cos, rotary_sin, rotary_dim, seqlen_ro = _rotary_tables(name, rotary_cos, rotary_sin, k.dtype, D, k.device, "rotary_cos", "rotary_sin")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (k, v, k_cache, v_cache)):
+        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
+
+    p = _append_varlen_params(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved)
+    with torch.cuda.device(k.device):
+        _lib.check(_lib.lib().tfa_kvcache_append_varlen(C.byref(p), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return None
