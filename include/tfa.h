@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -671,7 +671,7 @@ int tfa_bwd_bias_plan(const tfa_bwd_params* p, const tfa_attn_bias* bias, int wi
  * balanced; chunks behind a sequence's end give empty partials, which tfa_merge skips.  splits == 1 writes out / lse directly (any out strides, no workspace);
  * splits >= 2 writes fp32 partials to `workspace` and tfa_merge writes out, which must then be contiguous (B, H, Nq, D).  lse: (B, H, Nq) fp32 or NULL.
  * GQA / MQA decode (Nq == 1, Hk < H, H / Hk <= 128): the H / Hk query heads of a K/V head run as rows of one problem, K and V stream once per K/V head.
- * Nq > 1 runs unpacked: K and V are streamed once per QUERY head (position-aware packing for this form is future work).
+ * Nq > 1 runs unpacked here — K and V are streamed once per QUERY head — and packed on request: tfa_fwd_kvcache_pack(…, TFA_PACK_GQA_ON, …) below.
  * Everything is enqueued on `stream` alone — append, attention, merge, in that order; no side streams, no events: a captured step is a straight line.
  * Refused, nothing launched: a NULL params / q / out / k_cache / v_cache / cache_seqlens, one of k_new / v_new without the other or with n_new <= 0
  * (TFA_ERR_NULL / TFA_ERR_SHAPE); dtype other than TFA_F16 / TFA_BF16 (TFA_ERR_DTYPE); D not a multiple of 8 in [8, 128] (TFA_ERR_HEAD_DIM); B, H, Hk, Nq,
@@ -768,6 +768,34 @@ int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, 
 long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits);
 int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes);
 int tfa_kvcache_append_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
+
+/* ---- the same calls with the GQA packing chosen by the caller (FlashAttention-3's pack_gqa) ------------------------------------------------------
+ * pack_gqa is a scheduling choice: it never changes the definition of out or lse, the append, the refusals, the alignment rules or the workspace size.
+ *   TFA_PACK_GQA_AUTO  what tfa_fwd_kvcache / tfa_fwd_kvcache_fp8 run — the same launches, the same bits: packed iff Nq == 1 (Hk < H, H / Hk <= 128).
+ *   TFA_PACK_GQA_OFF   unpacked, also at Nq == 1: K and V stream once per query head (the A/B arm).
+ *   TFA_PACK_GQA_ON    packed whenever Hk < H and G = H / Hk <= 128.  Nq == 1: AUTO's packed call, the same bits.  Nq > 1: the packed form of the KV-cache
+ *     kernel — the Nq * G rows (position t, head g) of K/V head hk run as rows of one problem over sequence b's keys in POSITION-MAJOR order, row = t * G + g, so
+ *     head hk * G + g at position t = row / G.  Causal visibility stays per position — key j is visible iff j <= t + (len_b - Nq) — and, the last visible key still
+ *     growing with the row index, so do the kernel's causal tile bounds (one magic division per row).  Q rows are loaded by two strides (t * row stride + g * head
+ *     stride, any q strides the unpacked call takes), out / lse / the fp32 partials are written to their unpacked (b, h, t) places: workspace layout, tfa_merge and
+ *     every tensor layout are the unpacked call's.  K and V stream once per K/V head while Nq * G <= 128; beyond, ceil(Nq * G / 128) query blocks per (b, hk)
+ *     (causal: paired heavy / light on the packed block index) — still fewer passes than unpacked.  With H == Hk, or G > 128, or a head group of q / out whose rows
+ *     do not fit the 32-bit byte offsets of one 2 GiB descriptor, ON runs the unpacked call: packing is an optimisation, never a requirement and never an error.
+ *   any other value: TFA_ERR_SHAPE.
+ * q8 == NULL: the 16-bit cache (tfa_fwd_kvcache's); else the e4m3 cache (tfa_fwd_kvcache_fp8's).  Lengths on the device, per-sequence chunks, paged caches, descales,
+ * empty rows (out = 0, lse = +inf), descriptors that end at the last valid key, launches on `stream` alone, graph capture: as in the unpacked calls.
+ * _workspace: the same number of floats whatever pack_gqa.  _plan: the attention launch's geometry — packed, B * Hk * work items * chunks workgroups, work items =
+ * query blocks nmb = ceil(Nq * G / 128), or ceil(nmb / 2) causal.  _suggest_splits: tfa_fwd_kvcache_suggest_splits' rule with the workgroups counted from the
+ * geometry the mode runs (packed: B * Hk * ceil(Nq * G / 128)); AUTO equals tfa_fwd_kvcache_suggest_splits.
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcPacked, fwd_kernel_dma_kvc_pack / _kvc8_pack) — instantiations of their own, so every other kernel keeps its instructions
+ * (profiles/kvcache_packgqa_isa_unchanged.txt).  Measured: profiles/kvcache_packgqa_bench.txt (tools/bench_kvcache_packgqa.py), quoted in README.md. */
+#define TFA_PACK_GQA_AUTO 0
+#define TFA_PACK_GQA_ON   1
+#define TFA_PACK_GQA_OFF  2
+int tfa_fwd_kvcache_pack(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int splits, float* workspace, void* stream);
+long long tfa_fwd_kvcache_pack_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits);
+int tfa_fwd_kvcache_pack_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa);
 
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the

@@ -99,6 +99,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_fp8_workspace",
     "tfa_fwd_kvcache_fp8_plan",
     "tfa_kvcache_append_fp8",
+    "tfa_fwd_kvcache_pack",
+    "tfa_fwd_kvcache_pack_workspace",
+    "tfa_fwd_kvcache_pack_plan",
+    "tfa_fwd_kvcache_pack_suggest_splits",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -313,6 +317,7 @@ class TfaKvcacheParams(C.Structure):
 
 
 TFA_KV_E4M3 = 1
+TFA_PACK_GQA_AUTO, TFA_PACK_GQA_ON, TFA_PACK_GQA_OFF = 0, 1, 2   # tfa_fwd_kvcache_pack's pack_gqa
 
 
 class TfaKvcacheFp8(C.Structure):
@@ -547,6 +552,15 @@ def lib():
     L.tfa_fwd_kvcache_fp8_plan.argtypes = [PK, P8, C.c_int, IP, IP, IP]
     L.tfa_kvcache_append_fp8.restype = C.c_int
     L.tfa_kvcache_append_fp8.argtypes = [PK, P8, C.c_void_p]
+    # ... with the GQA packing chosen by the caller (TFA_PACK_GQA_*; P8 may be None: the 16-bit cache)
+    L.tfa_fwd_kvcache_pack.restype = C.c_int
+    L.tfa_fwd_kvcache_pack.argtypes = [PK, P8, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_pack_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_pack_workspace.argtypes = [PK, P8, C.c_int, C.c_int]
+    L.tfa_fwd_kvcache_pack_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_pack_plan.argtypes = [PK, P8, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_pack_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_pack_suggest_splits.argtypes = [PK, C.c_int]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

@@ -775,15 +775,52 @@ static int kvcache_chunks(const tfa_kvcache_params* p, int splits) {
 
 // GQA / MQA decode runs packed (pack_gqa_rows: one query row per head, the H / Hk heads of a K/V head as rows of one non-causal problem)
 static bool kvcache_packs(const tfa_kvcache_params* p) { return p->Nq == 1 && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128; }
+// ... and, asked for (tfa_fwd_kvcache_pack: TFA_PACK_GQA_ON), so do several rows per sequence — the Nq * G rows (position t, head g) of a K/V head as position-major
+// rows of one problem, by the packed form of the kernel (tfa_fwd_kernel_dma.h: KvcPacked).  More than 128 heads per K/V head run unpacked, as at Nq == 1
+static bool kvcache_packs_positions(const tfa_kvcache_params* p, int pack) {
+  return pack == TFA_PACK_GQA_ON && p->Nq > 1 && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128;
+}
+// The packed description of a validated launch: *a (the caller's problem, validate()) becomes the problem of B * Hk head groups of Nq * G rows; *pk receives what only
+// the packed kernels read.  False — *a untouched, the call runs unpacked — when a group's rows do not fit the 32-bit byte offsets of one descriptor
+// (o_esize: 4 for the fp32 partials of a split call, else 2)
+static bool kvcache_pack_args(const tfa_kvcache_params* p, bool causal, int o_esize, tfa::KArgs* a, tfa::KvcPacked<tfa::Kvc8Args>* pk) {
+  const int G = p->H / p->Hk;
+  const long long rows = (long long)p->Nq * G;
+  const long long q_hs = a->qs_h, o_hs = a->os_h;
+  const long long q_ext = ((long long)(p->Nq - 1) * a->qs_n + (long long)(G - 1) * q_hs + p->D) * 2;
+  const long long o_ext = ((long long)(p->Nq - 1) * a->os_n + (long long)(G - 1) * o_hs + p->D) * o_esize;
+  if (rows >= 0x3fffffffll || q_ext >= 0x7fffffffll || o_ext >= 0x7fffffffll) return false;
+  const int bm = tfa::block_m_of(tfa::kSplitVariant);
+  const long long nmb = (rows + bm - 1) / bm;
+  const long long nwork = (causal && tfa::pairs_causal(tfa::kSplitVariant)) ? (nmb + 1) / 2 : nmb;
+  if ((long long)p->B * p->Hk * nwork >= 0x7fffffffll) return false;
+  a->H = p->Hk;
+  a->Nq = (int)rows;
+  a->qs_h = G * q_hs;
+  a->os_h = G * o_hs;
+  a->q_bytes = (unsigned long long)q_ext;
+  a->o_bytes = (unsigned long long)o_ext;
+  a->nmb = (int)nmb;
+  a->nwork = (int)nwork;
+  a->nbh = p->B * p->Hk;
+  pk->pk_g = G;
+  pk->pk_fd_g = tfa::fastdiv_of((unsigned)G);
+  pk->pk_pad_ = 0;
+  pk->q_hs = q_hs;
+  pk->o_hs = o_hs;
+  return true;
+}
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
 
 // one host path for the 16-bit cache (q8 == nullptr: tfa_fwd_kvcache) and the e4m3 cache (tfa_fwd_kvcache_fp8): validation, chunking, packing and the three launches
-static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+// pack: TFA_PACK_GQA_AUTO — what tfa_fwd_kvcache runs, ON / OFF — tfa_fwd_kvcache_pack's choices
+static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
   int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   if (!p->q || !p->out) return TFA_ERR_NULL;
   if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
+  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
   const bool paged = p->block_table != nullptr;
   const int ns = kvcache_chunks(p, splits);
   const long long rows = (long long)p->B * p->H * p->Nq;
@@ -815,15 +852,17 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   {
     tfa_fwd_params fp;
     st = TFA_ERR_SHAPE;
-    if (kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
+    if (pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
       st = validate(&fp, &a, tfa::kSplitVariant);
       if (st == TFA_OK) f = fp;
     }
     if (st != TFA_OK) st = validate(&f, &a, tfa::kSplitVariant);
   }
   if (st != TFA_OK) return st;
-  tfa::Kvc8Args ka;                                         // (the 16-bit launch takes its KvcArgs base)
+  tfa::KvcPacked<tfa::Kvc8Args> ka;                         // (the 16-bit launch takes its KvcArgs base; the unpacked launches theirs, without the packed form's tail)
   memset(&ka, 0, sizeof(ka));
+  // several rows per sequence, packed: the validated problem is the caller's own — its packed description replaces the geometry only
+  const bool packed_rows = kvcache_packs_positions(p, pack) && kvcache_pack_args(p, f.is_causal != 0, ns > 1 ? 4 : 2, &a, &ka);
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
   ka.chunk = 0;                                            // (formed per sequence on the device)
@@ -856,6 +895,13 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   }
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
     using T = typename decltype(k)::T;
+    if (packed_rows) {
+      if (q8) return tfa::launch_kvc8_pack<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
+      tfa::KvcPacked<tfa::KvcArgs> k16;
+      static_cast<tfa::KvcArgs&>(k16) = ka;
+      k16.pk_g = ka.pk_g; k16.pk_fd_g = ka.pk_fd_g; k16.pk_pad_ = 0; k16.q_hs = ka.q_hs; k16.o_hs = ka.o_hs;
+      return tfa::launch_kvc_pack<T, decltype(k)::W>(k16, causal, ns > 1, nt, s, geom, dry);
+    }
     if (q8) return tfa::launch_kvc8<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
     return tfa::launch_kvc<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
   });
@@ -864,9 +910,9 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
 }
 
-static int kvcache_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
+static int kvcache_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, int* grid, int* block, int* lds_bytes) {
   tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_run(p, q8, splits, nullptr, nullptr, &g, true);
+  const int st = kvcache_run(p, q8, pack, splits, nullptr, nullptr, &g, true);
   if (st != TFA_OK) return st;
   if (grid) *grid = g.grid;
   if (block) *block = g.block;
@@ -874,31 +920,43 @@ static int kvcache_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, 
   return TFA_OK;
 }
 
-static long long kvcache_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) {
-  const int st = kvcache_run(p, q8, splits, nullptr, nullptr, nullptr, true);
+static long long kvcache_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits) {
+  const int st = kvcache_run(p, q8, pack, splits, nullptr, nullptr, nullptr, true);
   if (st != TFA_OK) return st;
   const int ns = kvcache_chunks(p, splits);
   return ns > 1 ? (long long)ns * p->B * p->H * p->Nq * (p->D + 1) : 0;
 }
 
-int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, nullptr, splits, workspace, stream, nullptr, false); }
-int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) { return kvcache_plan(p, nullptr, splits, grid, block, lds_bytes); }
-long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) { return kvcache_workspace(p, nullptr, splits); }
+int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, nullptr, TFA_PACK_GQA_AUTO, splits, workspace, stream, nullptr, false); }
+int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) { return kvcache_plan(p, nullptr, TFA_PACK_GQA_AUTO, splits, grid, block, lds_bytes); }
+long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) { return kvcache_workspace(p, nullptr, TFA_PACK_GQA_AUTO, splits); }
 
 // the e4m3 cache: the second struct is required (its NULL descale pointers mean 1.0)
 int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream) {
-  return q8 ? kvcache_run(p, q8, splits, workspace, stream, nullptr, false) : TFA_ERR_NULL;
+  return q8 ? kvcache_run(p, q8, TFA_PACK_GQA_AUTO, splits, workspace, stream, nullptr, false) : TFA_ERR_NULL;
 }
 int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
-  return q8 ? kvcache_plan(p, q8, splits, grid, block, lds_bytes) : TFA_ERR_NULL;
+  return q8 ? kvcache_plan(p, q8, TFA_PACK_GQA_AUTO, splits, grid, block, lds_bytes) : TFA_ERR_NULL;
 }
-long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) { return q8 ? kvcache_workspace(p, q8, splits) : (long long)TFA_ERR_NULL; }
+long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) { return q8 ? kvcache_workspace(p, q8, TFA_PACK_GQA_AUTO, splits) : (long long)TFA_ERR_NULL; }
 
-int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) {
+// the same calls with the GQA packing chosen by the caller (q8 == NULL: the 16-bit cache)
+int tfa_fwd_kvcache_pack(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
+  return kvcache_run(p, q8, pack_gqa, splits, workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_pack_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
+  return kvcache_plan(p, q8, pack_gqa, splits, grid, block, lds_bytes);
+}
+long long tfa_fwd_kvcache_pack_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) { return kvcache_workspace(p, q8, pack_gqa, splits); }
+
+static int kvcache_suggest_splits(const tfa_kvcache_params* p, int pack) {
   if (!p || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->capacity <= 0 || p->H % p->Hk != 0) return 1;
+  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return 1;
   // tfa_fwd_suggest_splits' rule on host-known sizes: the capacity stands in for the lengths (which live on the device)
-  const bool packed = kvcache_packs(p);
-  const long long blocks = (long long)p->B * (packed ? p->Hk : p->H) * (((packed ? p->H / p->Hk : p->Nq) + 127) / 128);
+  const bool packed = pack != TFA_PACK_GQA_OFF && kvcache_packs(p);     // one row per sequence: a non-causal problem
+  const bool packed_rows = kvcache_packs_positions(p, pack);            // several: workgroups counted from the packed geometry
+  const long long blocks = (packed || packed_rows) ? (long long)p->B * p->Hk * (((long long)p->Nq * (p->H / p->Hk) + 127) / 128)
+                                                   : (long long)p->B * p->H * ((p->Nq + 127) / 128);
   const int cus = num_cus();
   if (blocks * 2 > cus || p->capacity < 4096) return 1;
   if (p->is_causal && !packed && (long long)p->Nq * 4 > p->capacity) return 1;
@@ -907,6 +965,8 @@ int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) {
   if (s > 32) s = 32;
   return s >= 2 ? (int)s : 1;
 }
+int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) { return kvcache_suggest_splits(p, TFA_PACK_GQA_AUTO); }
+int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa) { return kvcache_suggest_splits(p, pack_gqa); }
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {
   const int st = kvcache_check_cache(p, q8);

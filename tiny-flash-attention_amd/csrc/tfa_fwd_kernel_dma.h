@@ -138,6 +138,26 @@ template <bool KV8>
 struct Kvc8View {
   template <typename A> static __device__ __forceinline__ const Kvc8Args& of(const A& a) { return a; }
 };
+// The packed form of the KV-cache form (tfa_fwd_kvcache_pack, TFA_PACK_GQA_ON with Nq > 1): the Nq * G rows (position t, head g) of the G = H / Hk query heads that share
+// K/V head hk are rows of ONE problem over sequence b's keys, position-major — row = t * G + g — so that the last visible key still grows with the row index and the
+// causal tile bounds of the body (kv_end, wave_last_tile, need_mask, the heavy / light pairing) hold with t = row / G in the place of the row.  In such a launch KArgs
+// describes the PACKED problem: H = Hk, Nq = Nq * G rows, nmb / nwork / nbh from them, qs_h / os_h the stride of a whole group of G heads, q_bytes / o_bytes the extent
+// of a group's rows; KvcArgs::nq_pos stays the caller's Nq.  Q rows are addressed by two strides (t * qs_n + g * q_hs), O and LSE are written to the caller's
+// (b, h, t) addresses, rows at or beyond Nq * G are pointed at TFA_OOB.  The arguments ride BEHIND the form's struct, not inside KvcArgs: Kvc8Args derives from
+// it, and a KvcArgs that grows moves the descales' kernel-argument offsets — the unpacked e4m3 kernels would no longer compile to the instructions they had.
+template <typename Base>
+struct KvcPacked : Base {
+  int pk_g;                 // G = H / Hk, 2..128
+  FastDiv pk_fd_g;          // row / G
+  int pk_pad_;
+  long long q_hs, o_hs;     // ELEMENTS between consecutive query heads of q / out (out: of the fp32 partials when split)
+};
+template <typename A> struct KvcPack { static constexpr bool value = false; };
+template <typename B> struct KvcPack<const KvcPacked<B>> { static constexpr bool value = true; };
+template <bool PACK>
+struct KvcPackView {
+  template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
+};
 template <bool KV8, typename T> struct KvElem { using type = T; };
 template <typename T> struct KvElem<true, T> { using type = unsigned char; };
 
@@ -194,6 +214,18 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc(const KvcArgs p) {
 // The e4m3 form of the KV-cache form (tfa_fwd_kvcache_fp8): T is the type of q, out and of the decoded tiles
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8(const Kvc8Args p) {
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+
+// The packed forms of the two (GQA query heads as position-major rows: KvcPacked above)
+template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_pack(const KvcPacked<KvcArgs> p) {
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (NT ? VF_DMA_NT : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8_pack(const KvcPacked<Kvc8Args> p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
 #include "tfa_fwd_kernel_dma_body.inc"
 }

@@ -3,6 +3,9 @@
   using E = Elem<T>;
   constexpr bool KVC = (VF & VF_KVCACHE) != 0;
   constexpr bool KV8 = (VF & VF_KV_E4M3) != 0;     // the K/V cache holds e4m3 bytes (tfa_fwd_kvcache_fp8): tiles are staged through registers and decoded to T on the way into LDS
+  // the packed form of the KV-cache form (KvcPacked: GQA query heads as position-major rows, row = t * G + g); its arguments are read through KvcPackView<PACK>::of(p),
+  // a dependent expression every other entry point never instantiates
+  constexpr bool PACK = KVC && KvcPack<decltype(p)>::value;
   constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
   using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
@@ -124,7 +127,11 @@
     else k.mb = CAUSAL ? (p.nmb - 1 - k.wi) : k.wi;
     int kv_end = k.nk;
     if (CAUSAL) {
-      const int lim = k.mb * BM + BM + k.shift;                  // one past the last key any row of the block sees
+      int lim = k.mb * BM + BM + k.shift;                        // one past the last key any row of the block sees
+      if constexpr (PACK) {                                      // ... the position of the block's last valid row sees
+        const int last = k.mb * BM + BM - 1 < p.Nq - 1 ? k.mb * BM + BM - 1 : p.Nq - 1;
+        lim = fd_div(last, KvcPackView<PACK>::of(p).pk_fd_g) + 1 + k.shift;
+      }
       kv_end = lim < kv_end ? lim : kv_end;
     }
     k.nt = kv_end > 0 ? (kv_end + BN - 1) / BN : 0;
@@ -249,7 +256,14 @@
     if (k.nt > 0) dma_issue(k, 0, 0);
     if (PD > 1 && k.nt > 1) dma_issue(k, 1, 1);
     const int row = k.mb * BM + wave * 32 + qi;
-    const int qoff = row * (int)p.qs_n * 2 + hi * 16;
+    int qoff = row * (int)p.qs_n * 2 + hi * 16;
+    if constexpr (PACK) {
+      // row = t * G + g lies at t * qs_n + g * q_hs behind the head group's base: the descriptor's extent bounds the group, not the rows — the rows behind the
+      // last one (which would alias rows of the next positions' heads) are sent out of range here
+      const auto& pp = KvcPackView<PACK>::of(p);
+      const int t = fd_div(row, pp.pk_fd_g), g = row - t * pp.pk_g;
+      qoff = row < p.Nq ? (t * (int)p.qs_n + g * (int)pp.q_hs) * 2 + hi * 16 : (int)TFA_OOB;
+    }
 #pragma unroll
     for (int s = 0; s < DS; ++s) {
       u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(k.q_rs, (2 * s + hi) * 8 < p.dv ? qoff + s * 32 : (int)TFA_OOB, 0, 0);
@@ -269,6 +283,15 @@
     nt_total += nt;
     const int wave_row0 = cur.mb * BM + wave * 32;
     const int my_row = wave_row0 + qi;
+    // the query POSITIONS the causal bounds below are formed from: the row's own, the wave's first row's and its last valid row's.  Packed: t = row / G
+    int my_t = my_row, my_g = 0, wave_t0 = wave_row0, wave_t1 = wave_row0 + 31;
+    if constexpr (PACK) {
+      const auto& pp = KvcPackView<PACK>::of(p);
+      my_t = fd_div(my_row, pp.pk_fd_g);
+      my_g = my_row - my_t * pp.pk_g;
+      wave_t0 = fd_div(wave_row0, pp.pk_fd_g);
+      wave_t1 = fd_div(wave_row0 + 31 < p.Nq - 1 ? wave_row0 + 31 : p.Nq - 1, pp.pk_fd_g);
+    }
 
     f32x16 oacc[WIDE ? 1 : DT];
     if constexpr (WIDE) g_zero();
@@ -295,7 +318,7 @@
     if (p.trace && first) t_pro = __builtin_amdgcn_s_memtime();
 
     const int shift = cur.shift;
-    const int wave_last_tile = CAUSAL ? ((wave_row0 + 31 + shift) >= 0 ? (wave_row0 + 31 + shift) / BN : -1) : (nt - 1);
+    const int wave_last_tile = CAUSAL ? ((wave_t1 + shift) >= 0 ? (wave_t1 + shift) / BN : -1) : (nt - 1);
 
     auto tile_body = [&](int j, int buf) {
       // tile j+2 goes into the buffer tile j-1 just vacated
@@ -384,10 +407,10 @@
 
         const int key0 = j * BN;
         bool need_mask = (key0 + BN > cur.nk);
-        if (CAUSAL) need_mask = need_mask || (key0 + BN - 1 > wave_row0 + shift);
+        if (CAUSAL) need_mask = need_mask || (key0 + BN - 1 > wave_t0 + shift);
         if (need_mask) {
           int lim = cur.nk - 1;
-          if (CAUSAL) { const int c = my_row + shift; lim = c < lim ? c : lim; }
+          if (CAUSAL) { const int c = my_t + shift; lim = c < lim ? c : lim; }
           lim -= key0 + 4 * hi;
 #pragma unroll
           for (int t = 0; t < 2; ++t)
@@ -525,12 +548,15 @@
     const float inv = KV8 ? (empty ? 1.f : 1.f / l_tot) * cur_vd : (empty ? 1.f : 1.f / l_tot);   // e4m3 form: v_descale in fp32, in front of the one rounding of O
     if (p.lse != nullptr && hi == 0 && my_row < p.Nq) {
       const float lse = empty ? INFINITY : (m_run * (KV8 ? cur_scale_lse : p.scale) + __builtin_amdgcn_logf(l_tot) * 0.6931471805599453f);
-      p.lse[lse_part + (long long)cur_bh * p.Nq + my_row] = lse;
+      // (packed: cur_bh = b * Hk + hk and p.Nq = Nq * G, so the first two terms are the caller's (b * H + hk * G) * Nq; head g, position t follow)
+      if constexpr (PACK) p.lse[lse_part + (long long)cur_bh * p.Nq + my_g * KvcPackView<PACK>::of(p).nq_pos + my_t] = lse;
+      else p.lse[lse_part + (long long)cur_bh * p.Nq + my_row] = lse;
     }
     if (F32OUT) {
       float* obase = reinterpret_cast<float*>(p.o) + o_part + ob * p.os_b + oh * p.os_h;
       auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, (unsigned)p.o_bytes, 0x00020000);
-      const int ooff = my_row * (int)p.os_n * 4 + hi * 16;
+      int ooff = my_row * (int)p.os_n * 4 + hi * 16;
+      if constexpr (PACK) ooff = my_row < p.Nq ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 4 + hi * 16 : (int)TFA_OOB;   // the caller's (b, h, t) row
 #pragma unroll
       for (int d = 0; d < DT; ++d)
 #pragma unroll
@@ -575,7 +601,8 @@
     } else {
       T* obase = reinterpret_cast<T*>(p.o) + o_part + ob * p.os_b + oh * p.os_h;
       auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, (unsigned)p.o_bytes, 0x00020000);
-      const int ooff = my_row * (int)p.os_n * 2 + hi * 8;
+      int ooff = my_row * (int)p.os_n * 2 + hi * 8;
+      if constexpr (PACK) ooff = my_row < p.Nq ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 2 + hi * 8 : (int)TFA_OOB;
       typedef __attribute__((ext_vector_type(4))) T t4;
 #pragma unroll
       for (int d = 0; d < DT; ++d)

@@ -2,17 +2,24 @@
 // fp32 partials (split) with and without the non-temporal hint, and the 16-bit direct output of a single chunk.  Compiled as the units tfa_kvc_inst_<dtype>_<W>.
 #include "tfa_launch.h"
 #include "tfa_kvcache.h"
+#ifndef TFA_KVC_PACK
+#define TFA_KVC_PACK 0       // 1: the unit of the packed form (tfa_kvc_inst_pack_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc_pack and its arguments
+#endif
 
 namespace tfa {
 
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-static hipError_t launch_kvc_one(const KvcArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
+static hipError_t launch_kvc_one(const std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<KvcArgs>, KvcArgs>& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
   constexpr int lds = 4 * 64 * D * 2;                          // two K and two V tile buffers
+#if TFA_KVC_PACK
+  auto kern = fwd_kernel_dma_kvc_pack<T, D, CAUSAL, F32OUT, NT>;
+#else
   auto kern = fwd_kernel_dma_kvc<T, D, CAUSAL, F32OUT, NT>;
+#endif
   const int grid = a_in.nbh * a_in.nwork * (a_in.nsplit > 1 ? a_in.nsplit : 1);
   if (geom) { geom->grid = grid; geom->block = 256; geom->lds = lds; }
   if (dry) return hipSuccess;
-  KvcArgs a = a_in;
+  auto a = a_in;
   fill_decode(&a);
   static std::atomic<unsigned long long> attr_mask{0};         // one per instantiation, one bit per device
   hipError_t e = set_dyn_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
@@ -23,7 +30,12 @@ static hipError_t launch_kvc_one(const KvcArgs& a_in, hipStream_t stream, Launch
 }
 
 template <>
-hipError_t launch_kvc<TFA_T, TFA_D>(const KvcArgs& a, bool causal, bool f32out, bool nt, hipStream_t s, LaunchGeom* g, bool dry) {
+#if TFA_KVC_PACK
+hipError_t launch_kvc_pack<TFA_T, TFA_D>(const KvcPacked<KvcArgs>& a,
+#else
+hipError_t launch_kvc<TFA_T, TFA_D>(const KvcArgs& a,
+#endif
+                                        bool causal, bool f32out, bool nt, hipStream_t s, LaunchGeom* g, bool dry) {
   if (!f32out) return causal ? launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, false, false>(a, s, g, dry);
   if (nt) return causal ? launch_kvc_one<TFA_T, TFA_D, true, true, true>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, true, true>(a, s, g, dry);
   return causal ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, true, false>(a, s, g, dry);

@@ -206,6 +206,17 @@ hipError_t launch_kvc8(const Kvc8Args& a, bool causal, bool f32out, bool nt, hip
 #define TFA_KVC8_UNITS(T, D) template <> hipError_t launch_kvc8<T, D>(const Kvc8Args&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
 TFA_KVC8_UNITS(__bf16, 64) TFA_KVC8_UNITS(__bf16, 128) TFA_KVC8_UNITS(_Float16, 64) TFA_KVC8_UNITS(_Float16, 128)
 #undef TFA_KVC8_UNITS
+// ... and the packed forms of both (tfa_fwd_kvcache_pack; fwd_kernel_dma_kvc_pack / _kvc8_pack): units of their own, tfa_kvc_inst_pack_<dtype>_<W> and
+// tfa_kvc8_inst_pack_<dtype>_<W> — the same .inc files compiled with TFA_KVC_PACK
+template <typename T, int D>
+hipError_t launch_kvc_pack(const KvcPacked<KvcArgs>& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+template <typename T, int D>
+hipError_t launch_kvc8_pack(const KvcPacked<Kvc8Args>& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVCP_UNITS(T, D)                                                                                                          \
+  template <> hipError_t launch_kvc_pack<T, D>(const KvcPacked<KvcArgs>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);          \
+  template <> hipError_t launch_kvc8_pack<T, D>(const KvcPacked<Kvc8Args>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+TFA_KVCP_UNITS(__bf16, 64) TFA_KVCP_UNITS(__bf16, 128) TFA_KVCP_UNITS(_Float16, 64) TFA_KVCP_UNITS(_Float16, 128)
+#undef TFA_KVCP_UNITS
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).
