@@ -16,6 +16,8 @@ import math
 import pytest
 import torch
 
+import form_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -118,8 +120,10 @@ def check_fwd(out, lse, q, k, v, slopes, left, right, sc, dtype, f32, out16=True
     assert bool((o[inf.unsqueeze(-1).expand_as(o)] == 0).all()), "rows that see no key must be 0"
 
 
-def check_bwd(g32, g16, q, k, v, dout, slopes, left, right, sc, dtype):
+def check_bwd(g32, g16, q, k, v, dout, slopes, left, right, sc, dtype, out=None):
     ref = ref_grads(q, k, v, dout, slopes, left, right, sc)
+    if out is not None:     # element by element: (B1) / (B2) with the bound of tests/form_ref.py (out: the 16-bit O the forward stored)
+        form_ref.check_grads(g32, g16, ref, form_ref.bwd_bounds(q, k, v, out, dout, sc, slopes=slopes, window=(left, right)), dtype, f"alibi {(left, right)}")
     eps = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     for name, a32, a16, r in zip(("dq", "dk", "dv"), g32, g16, ref):
         a32c, a16c = a32.double().cpu(), a16.double().cpu()
@@ -294,7 +298,7 @@ def run_bwd_vs_fp64(dev, dtype, window, causal, Nq, Nk, D, H, Hk, B):
     g16 = ops.flash_attn_bwd(q, k, v, o, l, dout, causal, sc, window_size=window, alibi_slopes=slopes)
     g32 = ops.flash_attn_bwd(q, k, v, o, l, dout, causal, sc, window_size=window, alibi_slopes=slopes, grad_f32=True)
     torch.cuda.synchronize()
-    check_bwd(g32, g16, q, k, v, dout, slopes, w[0], w[1], sc, dtype)
+    check_bwd(g32, g16, q, k, v, dout, slopes, w[0], w[1], sc, dtype, out=o)
     seen = window_mask(Nq, Nk, *w).any(dim=0)                # keys that no row sees: zero dk / dv
     if (~seen).any():
         for g in g16[1:]:
@@ -326,6 +330,8 @@ def test_flash_attn_func_alibi_grads(lib, dev, causal):
     for g, r in zip((q.grad, k.grad, v.grad), ref):
         assert bool(torch.isfinite(g).all())
         assert (t(g).double().cpu() - r).abs().max().item() <= 1e-2 * max(1.0, r.abs().max().item())
+    form_ref.check_grads(None, (t(q.grad), t(k.grad), t(v.grad)), ref, form_ref.bwd_bounds(t(q), t(k), t(v), t(out), t(dout), sc, slopes=slopes, window=w), dtype,
+                         "flash_attn_func")
     # slopes that require grad get none
     s2 = slopes.clone().requires_grad_(True)
     q2 = q.detach().clone().requires_grad_(True)
@@ -382,6 +388,10 @@ def test_varlen_alibi_vs_per_sequence(lib, dev, variant, window, causal):
         w = eff_window(causal, window)
         ref, _, _ = ref64(qs, ks, vs, slopes[b], *w, sc)
         assert (ov.double().cpu() - ref).abs().max().item() <= 1e-2
+        dos = dout[q0:q1].transpose(0, 1).unsqueeze(0)
+        form_ref.check_grads(None, tuple(g[a:z].transpose(0, 1).unsqueeze(0) for g, a, z in ((q.grad, q0, q1), (k.grad, k0, k1), (v.grad, k0, k1))),
+                             form_ref.ref_grads(qs, ks, vs, dos, sc, slopes=slopes[b], window=w),
+                             form_ref.bwd_bounds(qs, ks, vs, ov, dos, sc, slopes=slopes[b], window=w), dtype, f"varlen seq {b}")
     for g, n in ((q.grad, int(cq[-1])), (k.grad, int(ck[-1])), (v.grad, int(ck[-1]))):
         assert bool((g[n:] == 0).all())
 

@@ -16,6 +16,8 @@ import math
 import pytest
 import torch
 
+import form_ref
+
 pytestmark = pytest.mark.gpu
 
 B, H, HK = 2, 4, 2
@@ -106,8 +108,10 @@ def check_fwd(out, lse, ref, dtype, f32, out16=True):
     assert bool((o[inf.unsqueeze(-1).expand_as(o)] == 0).all()), "rows without a finite score must be exactly 0"
 
 
-def check_bwd(g32, g16, ref, dtype):
+def check_bwd(g32, g16, ref, dtype, bounds=None):
     eps = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+    if bounds is not None:  # element by element: (B1) / (B2) with form_ref.bwd_bounds
+        form_ref.check_grads(g32, g16, ref, bounds, dtype, "bias")
     for name, a32, a16, r in zip(("dq", "dk", "dv"), g32, g16, ref):
         a32c, a16c = a32.double().cpu(), a16.double().cpu()
         assert bool(torch.isfinite(a16c).all()) and bool(torch.isfinite(a32c).all()), name
@@ -274,7 +278,7 @@ def test_bwd_vs_fp64(lib, dev, causal, Nq, Nk, dtype, D, bshape, bias_f32):
     g32 = ops.flash_attn_bwd(qd, kd, vd, o, l, dd, causal, sc, grad_f32=True, attn_bias=bd)
     again = ops.flash_attn_bwd(qd, kd, vd, o, l, dd, causal, sc, attn_bias=bd)
     torch.cuda.synchronize()
-    check_bwd(g32, g16, ref, dtype)
+    check_bwd(g32, g16, ref, dtype, bounds=form_ref.bwd_bounds(q, k, v, o, dout, sc, bias=bias, window=w))
     for a, b in zip(g16, again):
         assert torch.equal(a, b), "the backward must be deterministic"
     # fully masked rows get no dq, keys nobody sees get no dk / dv: exactly 0

@@ -19,6 +19,8 @@ import math
 import pytest
 import torch
 
+import form_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -159,7 +161,9 @@ def check_fwd(out, lse, q, k, v, cap, slopes, left, right, sc, dtype, f32, out16
     assert bool((o[inf.unsqueeze(-1).expand_as(o)] == 0).all()), "rows that see no key must be 0"
 
 
-def check_bwd(g32, g16, ref, dtype):
+def check_bwd(g32, g16, ref, dtype, bounds=None):
+    if bounds is not None:  # element by element: (B1) / (B2) with form_ref.bwd_bounds
+        form_ref.check_grads(g32, g16, ref, bounds, dtype, "softcap")
     for name, a32, a16, r in zip(("dq", "dk", "dv"), g32, g16, ref):
         a32c, a16c = a32.double().cpu(), a16.double().cpu()
         assert bool(torch.isfinite(a16c).all()) and bool(torch.isfinite(a32c).all()), name
@@ -328,7 +332,7 @@ def test_saturation(lib, dev, dtype, D, causal, window):
     torch.cuda.synchronize()
     for g in tuple(g16) + tuple(g32):
         assert not bool(torch.isnan(g).any()) and bool(torch.isfinite(g).all())
-    check_bwd(g32, g16, ref_grads(q, k, v, dout, cap, None, w[0], w[1], sc), dtype)
+    check_bwd(g32, g16, ref_grads(q, k, v, dout, cap, None, w[0], w[1], sc), dtype, bounds=form_ref.bwd_bounds(q, k, v, o, dout, sc, softcap=cap, window=w))
 
 
 # ---- 5. with alibi_slopes, with windows, with both ------------------------------------------------------------------------------------------
@@ -391,7 +395,7 @@ def run_bwd(dev, dtype, std, cap, window, causal, Nq, Nk, D, H, Hk, B, slopes, d
     g16 = ops.flash_attn_bwd(q, k, v, o, l, dout, causal, sc, window_size=window, alibi_slopes=slopes, softcap=cap)
     g32 = ops.flash_attn_bwd(q, k, v, o, l, dout, causal, sc, window_size=window, alibi_slopes=slopes, softcap=cap, grad_f32=True)
     torch.cuda.synchronize()
-    check_bwd(g32, g16, ref, dtype)
+    check_bwd(g32, g16, ref, dtype, bounds=form_ref.bwd_bounds(q, k, v, o, dout, sc, softcap=cap, slopes=slopes, window=w))
     seen = window_mask(Nq, Nk, *w).any(dim=0)                # keys that no row sees: zero dk / dv
     if (~seen).any():
         for g in g16[1:]:
@@ -450,6 +454,8 @@ def test_flash_attn_func_softcap_grads(lib, dev, causal, with_slopes):
     for g, r in zip((q.grad, k.grad, v.grad), ref):
         assert bool(torch.isfinite(g).all())
         assert (t(g).double().cpu() - r).abs().max().item() <= 1e-2 * max(1.0, r.abs().max().item())
+    form_ref.check_grads(None, (t(q.grad), t(k.grad), t(v.grad)), ref,
+                         form_ref.bwd_bounds(t(q), t(k), t(v), t(out), t(dout), sc, softcap=cap, slopes=slopes, window=w), dtype, "flash_attn_func")
     # no grad mode: the same forward bits
     with torch.no_grad():
         out2 = tfa.flash_attn_func(q, k, v, causal=causal, alibi_slopes=slopes, softcap=cap)
@@ -508,6 +514,10 @@ def test_varlen_softcap_vs_per_sequence(lib, dev, variant, window, causal, with_
         w = eff_window(causal, window)
         ref, _, _ = ref64(qs, ks, vs, cap, sl, *w, sc)
         assert (ov.double().cpu() - ref).abs().max().item() <= 1e-2
+        dos = dout[q0:q1].transpose(0, 1).unsqueeze(0)
+        form_ref.check_grads(None, tuple(g[a:z].transpose(0, 1).unsqueeze(0) for g, a, z in ((q.grad, q0, q1), (k.grad, k0, k1), (v.grad, k0, k1))),
+                             form_ref.ref_grads(qs, ks, vs, dos, sc, softcap=cap, slopes=sl, window=w),
+                             form_ref.bwd_bounds(qs, ks, vs, ov, dos, sc, softcap=cap, slopes=sl, window=w), dtype, f"varlen seq {b}")
         if q1 - q0 >= 300:
             un, _, _ = ref64(qs, ks, vs, 0.0, sl, *w, sc)
             assert (un - ref).abs().max().item() >= 10 * 1e-2

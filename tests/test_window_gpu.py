@@ -16,6 +16,8 @@ import math
 import pytest
 import torch
 
+import form_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -196,8 +198,10 @@ def test_fwd_peaked_row_outside_first_tile(lib, dev):
 
 
 # ---- 4. backward ------------------------------------------------------------------------------------------------------------------------
-def check_bwd(g32, g16, q, k, v, dout, left, right, sc, dtype):
+def check_bwd(g32, g16, q, k, v, dout, left, right, sc, dtype, out=None):
     ref = ref_grads(q, k, v, dout, left, right, sc)
+    if out is not None:     # element by element: (B1) / (B2) with the bound of tests/form_ref.py (out: the 16-bit O the forward stored)
+        form_ref.check_grads(g32, g16, ref, form_ref.bwd_bounds(q, k, v, out, dout, sc, window=(left, right)), dtype, f"window {(left, right)}")
     for name, a32, a16, r in zip(("dq", "dk", "dv"), g32, g16, ref):
         a32c, a16c = a32.double().cpu(), a16.double().cpu()
         assert bool(torch.isfinite(a16c).all()), name
@@ -221,7 +225,7 @@ def test_bwd_windows_vs_fp64(lib, dev, dtype, window, Nq, Nk, D, H, Hk):
     g16 = ops.flash_attn_bwd(q, k, v, o, l, dout, False, sc, window_size=window)
     g32 = ops.flash_attn_bwd(q, k, v, o, l, dout, False, sc, window_size=window, grad_f32=True)
     torch.cuda.synchronize()
-    check_bwd(g32, g16, q, k, v, dout, window[0], window[1], sc, dtype)
+    check_bwd(g32, g16, q, k, v, dout, window[0], window[1], sc, dtype, out=o)
     # keys that no row sees: zero dk / dv; determinism: a second run gives the same bits
     seen = window_mask(Nq, Nk, *window).any(dim=0)
     if (~seen).any():
@@ -248,6 +252,7 @@ def test_flash_attn_func_window_grads(lib, dev):
     ref = ref_grads(t(q), t(k), t(v), t(dout), *window, sc)
     for g, r in zip((q.grad, k.grad, v.grad), ref):
         assert (t(g).double().cpu() - r).abs().max().item() <= 1e-2 * max(1.0, r.abs().max().item())
+    form_ref.check_grads(None, (t(q.grad), t(k.grad), t(v.grad)), ref, form_ref.bwd_bounds(t(q), t(k), t(v), t(out), t(dout), sc, window=window), dtype, "flash_attn_func")
 
 
 def cu_of(lens):
@@ -296,6 +301,9 @@ def test_varlen_window_vs_per_sequence(lib, dev, variant, window):
         for g, r, a, z in ((q.grad, rg[0], q0, q1), (k.grad, rg[1], k0, k1), (v.grad, rg[2], k0, k1)):
             gg = g[a:z].transpose(0, 1).unsqueeze(0).double().cpu()
             assert (gg - r).abs().max().item() <= 1e-2 * max(1.0, r.abs().max().item())
+        dos = dout[q0:q1].transpose(0, 1).unsqueeze(0)
+        form_ref.check_grads(None, tuple(g[a:z].transpose(0, 1).unsqueeze(0) for g, a, z in ((q.grad, q0, q1), (k.grad, k0, k1), (v.grad, k0, k1))), rg,
+                             form_ref.bwd_bounds(qs, ks, vs, out.detach()[q0:q1].transpose(0, 1).unsqueeze(0), dos, sc, window=window), dtype, f"varlen seq {b}")
     for g, n in ((q.grad, int(cq[-1])), (k.grad, int(ck[-1])), (v.grad, int(ck[-1]))):
         assert bool((g[n:] == 0).all())
 
