@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + packed ragged query rows over a K/V cache — tfa_fwd_kvcache_varlen and its _workspace / _plan / _suggest_splits companions (struct tfa_kvcache_varlen_q: cu_seqlens_q in device memory, max_seqlen_q, total_q; q packed (total_q, H, D), every sequence's rows read and clamped on the device: the varlen-q form of the KV-cache kernel, packed GQA rows by default); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -796,6 +796,40 @@ int tfa_fwd_kvcache_pack(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8 
 long long tfa_fwd_kvcache_pack_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits);
 int tfa_fwd_kvcache_pack_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
 int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa);
+
+/* ---- the same attention for PACKED RAGGED query rows (FlashAttention-3's flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=), the interface this mirrors) ------------
+ * One call for a unified batch — decode rows, chunked-prefill rows, any mix — whose row counts live on the device.  q is packed (total_q, H, D); sequence b owns the
+ * query rows [q0_b, q0_b + nq_b), q0_b = clamp(cu_seqlens_q[b], 0, total_q), nq_b = clamp(cu_seqlens_q[b + 1] - cu_seqlens_q[b], 0, min(max_seqlen_q, total_q - q0_b)):
+ * every work item reads and clamps them itself, as it reads cache_seqlens; nothing is read on the host, a captured launch follows in-place updates of all three arrays.
+ * Sequence b attends keys [0, len_b), len_b = clamp(cache_seqlens[b], 0, capacity) — the length INCLUDING the rows appended for this step (tfa_kvcache_append_varlen
+ * is the append for packed rows; k_new / v_new must be NULL and n_new 0 here: TFA_ERR_SHAPE).  Causal: bottom-right aligned per sequence, key j visible to row t of
+ * sequence b iff j <= t + (len_b - nq_b).  A row that sees no key (len_b == 0, or len_b < nq_b under causal) gives out = 0, lse = +inf; nq_b == 0 is legal.  Rows of
+ * out / lse that belong to no sequence are not written; nothing outside the tensors is read or written whatever the three device arrays hold.
+ * In *p: B = the sequences (cu_seqlens_q has B + 1 entries; the batch of a contiguous cache, the rows of block_table, cache_seqlens and the descales); Nq is not looked
+ * at; q_stride / o_stride are {ignored, head, row}; lse is (H, total_q) fp32 contiguous or NULL.  splits == 1: out by any o_stride; splits >= 2: out must be the
+ * contiguous (H, total_q, D) (TFA_ERR_STRIDE) and tfa_merge runs unchanged over H * total_q rows.  Paged and contiguous caches, q8 (NULL: 16-bit cache; else e4m3 with
+ * descales by sequence), per-sequence chunks, zero fill behind the lengths, launches on `stream` alone: as in tfa_fwd_kvcache_pack.
+ * pack_gqa: TFA_PACK_GQA_AUTO = ON here — packed (position-major rows t * G + g of a K/V head) whenever Hk < H and G = H / Hk <= 128 — or OFF; H == Hk and G > 128 run
+ * unpacked (KvcPacked serves G = 2..128; MHA is why the unpacked varlen-q instantiations exist).  A scheduling choice: it never changes the result's definition.
+ * Geometry: work item = (sequence, K/V head or head, query block, chunk); the launch carries nmb = ceil(max_seqlen_q * G' / 128) blocks per (sequence, head), G' = G
+ * packed, 1 unpacked; causal blocks pair heavy / light on that launch-level index; _plan's grid = B * heads * work items * chunks.  A block with no row of its sequence
+ * issues no Q, K or V request and no store.  KNOWN COST: the grid is sized by max_seqlen_q — one 2048-row prefill chunk in a batch of decode rows makes most work
+ * items empty, each costing its scalar loads and an exit.
+ * _workspace: 0 for one chunk, else chunks * H * total_q * (D + 1) floats.  _suggest_splits: tfa_fwd_kvcache_pack_suggest_splits' rule with the workgroups counted as
+ * heads * min(B * nmb, ceil(total_q * G' / 128) + B) — the second term bounds the non-empty blocks from what the host knows.
+ * Refused, nothing launched: a NULL vq or cu_seqlens_q (TFA_ERR_NULL); max_seqlen_q <= 0, total_q <= 0, a nonzero reserved field (TFA_ERR_SHAPE); a cu_seqlens_q that
+ * is not 4-byte aligned (TFA_ERR_ALIGN); everything tfa_fwd_kvcache_pack refuses.
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcVarlenQ, fwd_kernel_dma_kvc_vq) — instantiations and units of their own, so every other kernel keeps its instructions
+ * (profiles/kvcache_varlenq_isa_unchanged.txt). */
+typedef struct tfa_kvcache_varlen_q {
+  const int32_t* cu_seqlens_q;   /* device, B + 1 entries */
+  int32_t max_seqlen_q, total_q;
+  int32_t reserved_[2];          /* must be 0 */
+} tfa_kvcache_varlen_q;
+int tfa_fwd_kvcache_varlen(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int splits, float* workspace, void* stream);
+long long tfa_fwd_kvcache_varlen_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits);
+int tfa_fwd_kvcache_varlen_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa);
 
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the

@@ -103,6 +103,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_pack_workspace",
     "tfa_fwd_kvcache_pack_plan",
     "tfa_fwd_kvcache_pack_suggest_splits",
+    "tfa_fwd_kvcache_varlen",
+    "tfa_fwd_kvcache_varlen_workspace",
+    "tfa_fwd_kvcache_varlen_plan",
+    "tfa_fwd_kvcache_varlen_suggest_splits",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -330,6 +334,17 @@ class TfaKvcacheFp8(C.Structure):
         ("v_descale_stride", C.c_int64 * 2),
         ("format", C.c_int32),
         ("reserved_", C.c_int32),
+    ]
+
+
+class TfaKvcacheVarlenQ(C.Structure):
+    """struct tfa_kvcache_varlen_q (include/tfa.h): the packed query rows of tfa_fwd_kvcache_varlen, handed over beside TfaKvcacheParams."""
+
+    _fields_ = [
+        ("cu_seqlens_q", C.c_void_p),
+        ("max_seqlen_q", C.c_int32),
+        ("total_q", C.c_int32),
+        ("reserved_", C.c_int32 * 2),
     ]
 
 
@@ -561,6 +576,16 @@ def lib():
     L.tfa_fwd_kvcache_pack_plan.argtypes = [PK, P8, C.c_int, C.c_int, IP, IP, IP]
     L.tfa_fwd_kvcache_pack_suggest_splits.restype = C.c_int
     L.tfa_fwd_kvcache_pack_suggest_splits.argtypes = [PK, C.c_int]
+    # ... for packed ragged query rows (tfa_kvcache_varlen_q: cu_seqlens_q on the device)
+    PV = C.POINTER(TfaKvcacheVarlenQ)
+    L.tfa_fwd_kvcache_varlen.restype = C.c_int
+    L.tfa_fwd_kvcache_varlen.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_varlen_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_varlen_workspace.argtypes = [PK, PV, P8, C.c_int, C.c_int]
+    L.tfa_fwd_kvcache_varlen_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_varlen_plan.argtypes = [PK, PV, P8, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_varlen_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_varlen_suggest_splits.argtypes = [PK, PV, C.c_int]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

@@ -968,6 +968,179 @@ static int kvcache_suggest_splits(const tfa_kvcache_params* p, int pack) {
 int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) { return kvcache_suggest_splits(p, TFA_PACK_GQA_AUTO); }
 int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa) { return kvcache_suggest_splits(p, pack_gqa); }
 
+// ---- the varlen-q form (tfa.h: tfa_fwd_kvcache_varlen): q packed (total_q, H, D), sequence b's rows read from cu_seqlens_q on the device ----------------------------
+// packed iff asked (AUTO = ON) and the heads group: Hk < H, G <= 128.  G = 1 and G > 128 run the unpacked instantiations
+static bool kvcache_vq_packs(const tfa_kvcache_params* p, int pack) { return pack != TFA_PACK_GQA_OFF && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128; }
+
+// the launch geometry of max_q rows of gp heads each per (sequence, K/V head or head): query blocks, work items (causal blocks pair heavy / light on the launch-level index)
+static void kvcache_vq_blocks(int max_q, int gp, bool causal, long long* nmb, long long* nwork) {
+  const int bm = tfa::block_m_of(tfa::kSplitVariant);
+  *nmb = ((long long)max_q * gp + bm - 1) / bm;
+  *nwork = (causal && tfa::pairs_causal(tfa::kSplitVariant)) ? (*nmb + 1) / 2 : *nmb;
+}
+
+static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream,
+                          tfa::LaunchGeom* geom, bool dry) {
+  if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
+  int st = kvcache_check_cache(p, q8);
+  if (st != TFA_OK) return st;
+  if (!p->q || !p->out) return TFA_ERR_NULL;
+  if (p->H <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
+  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
+  if (vq->max_seqlen_q <= 0 || vq->total_q <= 0 || vq->reserved_[0] != 0 || vq->reserved_[1] != 0) return TFA_ERR_SHAPE;
+  if (p->k_new || p->v_new || p->n_new != 0) return TFA_ERR_SHAPE;      // the append for packed rows is tfa_kvcache_append_varlen
+  if ((uintptr_t)vq->cu_seqlens_q & 3) return TFA_ERR_ALIGN;
+  const bool paged = p->block_table != nullptr;
+  const int ns = kvcache_chunks(p, splits);
+  const int tq = vq->total_q;
+  const int mq = vq->max_seqlen_q < tq ? vq->max_seqlen_q : tq;          // the most rows a sequence can own after the device's clamp: what the descriptors must reach
+  const long long rows = (long long)p->H * tq;
+  // validate() sees one sequence of mq rows: strides, alignment, the 2 GiB bounds of the q / out descriptors (which start at the sequence's first row)
+  tfa_fwd_params f;
+  memset(&f, 0, sizeof(f));
+  f.q = p->q; f.k = p->k_cache; f.v = p->v_cache; f.out = p->out; f.lse = p->lse;
+  f.B = 1; f.H = p->H; f.Hk = p->Hk; f.Nq = mq; f.D = p->D;
+  f.Nk = paged ? p->page_size : p->capacity;
+  for (int i = 0; i < 3; ++i) { f.q_stride[i] = p->q_stride[i]; f.k_stride[i] = p->k_stride[i]; f.v_stride[i] = p->v_stride[i]; f.o_stride[i] = p->o_stride[i]; }
+  f.q_stride[0] = f.o_stride[0] = 0;                                     // {ignored, head, row}
+  f.softmax_scale = p->softmax_scale;
+  f.is_causal = p->is_causal ? 1 : 0;
+  f.dtype = f.out_dtype = p->dtype;
+  float* ws_o = workspace;
+  float* ws_l = workspace ? workspace + (long long)ns * rows * p->D : nullptr;
+  if (ns > 1) {
+    // the merge writes contiguous rows: out must be the contiguous (H, total_q, D); the partial pass writes fp32 O and LSE of every chunk into the workspace
+    if (p->o_stride[2] != p->D || p->o_stride[1] != (int64_t)tq * p->D) return TFA_ERR_STRIDE;
+    if (((uintptr_t)p->out & 15)) return TFA_ERR_ALIGN;
+    if (p->lse && ((uintptr_t)p->lse & 3)) return TFA_ERR_ALIGN;
+    if (!dry) {
+      if (!workspace) return TFA_ERR_NULL;
+      if ((uintptr_t)workspace & 15) return TFA_ERR_ALIGN;
+    }
+    f.out = dry ? (void*)p->out : (void*)ws_o;
+    f.lse = dry ? nullptr : ws_l;
+    f.out_dtype = TFA_F32;
+  }
+  tfa::KArgs a;
+  st = validate(&f, &a, tfa::kSplitVariant);
+  if (st != TFA_OK) return st;
+  const bool causal = f.is_causal != 0;
+  const int G = p->H / p->Hk;
+  const int osz = ns > 1 ? 4 : 2;
+  bool packed = kvcache_vq_packs(p, pack);
+  if (packed) {      // a head group's rows must fit the 32-bit byte offsets of one descriptor; else unpacked — packing is an optimisation, never a requirement
+    const long long q_ext = ((long long)(mq - 1) * a.qs_n + (long long)(G - 1) * a.qs_h + p->D) * 2;
+    const long long o_ext = ((long long)(mq - 1) * a.os_n + (long long)(G - 1) * a.os_h + p->D) * osz;
+    if ((long long)vq->max_seqlen_q * G >= 0x3fffffffll || q_ext >= 0x7fffffffll || o_ext >= 0x7fffffffll) packed = false;
+  }
+  const int gp = packed ? G : 1, heads = packed ? p->Hk : p->H;
+  if ((long long)vq->max_seqlen_q * gp >= 0x3fffffffll) return TFA_ERR_SHAPE;
+  long long nmb, nwork;
+  kvcache_vq_blocks(vq->max_seqlen_q, gp, causal, &nmb, &nwork);
+  if ((long long)p->B * heads * nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>> ka;        // (every launch takes the bases it has: vq_launch below)
+  memset(&ka, 0, sizeof(ka));
+  if (packed) {
+    ka.pk_g = G;
+    ka.pk_fd_g = tfa::fastdiv_of((unsigned)G);
+    ka.q_hs = a.qs_h;
+    ka.o_hs = a.os_h;
+    a.qs_h *= G;
+    a.os_h *= G;
+    a.H = p->Hk;
+  }
+  a.B = p->B;
+  a.Nq = (int)((long long)vq->max_seqlen_q * gp);           // sizes the grid; the kernels take every sequence's own row count
+  a.nmb = (int)nmb;
+  a.nwork = (int)nwork;
+  a.nbh = p->B * heads;
+  static_cast<tfa::KArgs&>(ka) = a;
+  ka.nsplit = ns;
+  ka.chunk = 0;
+  ka.o_part_stride = ns > 1 ? rows * p->D : 0;
+  ka.lse_part_stride = ns > 1 ? rows : 0;
+  ka.trace = nullptr;
+  ka.seqlens = p->cache_seqlens;
+  ka.block_table = p->block_table;
+  ka.bt_stride = p->block_table_stride;
+  ka.n_new = 0;
+  ka.capacity = p->capacity;
+  ka.num_pages = paged ? p->num_pages : 1;
+  ka.nq_pos = vq->max_seqlen_q;                              // (not read: the shift is len_b - nq_b)
+  ka.tpp = paged ? p->page_size / 64 : 1;
+  ka.fd_nsplit = tfa::fastdiv_of((unsigned)ns);
+  ka.fd_tpp = tfa::fastdiv_of((unsigned)ka.tpp);
+  ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * (q8 ? 2 : 4) >= (768ll << 20)) ? 1 : 0;
+  ka.vq_cu = vq->cu_seqlens_q;
+  ka.vq_max_q = vq->max_seqlen_q;
+  ka.vq_total_q = tq;
+  if (q8) {
+    ka.k_descale = q8->k_descale; ka.v_descale = q8->v_descale;
+    ka.kd_b = q8->k_descale_stride[0]; ka.kd_h = q8->k_descale_stride[1];
+    ka.vd_b = q8->v_descale_stride[0]; ka.vd_h = q8->v_descale_stride[1];
+  }
+  const bool nt = ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
+    using T = typename decltype(k)::T;
+    constexpr int W = decltype(k)::W;
+    // the arguments of the instantiation that runs: the same fields, without the bases it does not have
+    auto run = [&](auto* args) {
+      using A = std::remove_pointer_t<decltype(args)>;
+      using Base = typename A::vq_base;
+      A v;
+      memset(&v, 0, sizeof(v));
+      static_cast<tfa::KvcArgs&>(v) = ka;
+      if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
+      if constexpr (tfa::KvcPack<const Base>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
+      v.vq_cu = ka.vq_cu; v.vq_max_q = ka.vq_max_q; v.vq_total_q = ka.vq_total_q;
+      return tfa::launch_kvc_vq<T, W, A>(v, causal, ns > 1, nt, s, geom, dry);
+    };
+    if (packed) return q8 ? run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
+    return q8 ? run((tfa::KvcVarlenQ<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcArgs>*)nullptr);
+  });
+  if (e != hipSuccess) return (int)e;
+  if (dry || ns == 1) return TFA_OK;
+  return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
+}
+
+int tfa_fwd_kvcache_varlen(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
+  return kvcache_vq_run(p, vq, q8, pack_gqa, splits, workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_varlen_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+long long tfa_fwd_kvcache_varlen_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) {
+  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, nullptr, true);
+  if (st != TFA_OK) return st;
+  const int ns = kvcache_chunks(p, splits);
+  return ns > 1 ? (long long)ns * p->H * vq->total_q * (p->D + 1) : 0;
+}
+int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa) {
+  if (!p || !vq || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->capacity <= 0 || p->H % p->Hk != 0 || vq->max_seqlen_q <= 0 || vq->total_q <= 0) return 1;
+  if (pack_gqa != TFA_PACK_GQA_AUTO && pack_gqa != TFA_PACK_GQA_ON && pack_gqa != TFA_PACK_GQA_OFF) return 1;
+  // tfa_fwd_kvcache_pack_suggest_splits' rule; the workgroups that have rows are bounded from what the host knows: a sequence of n rows fills at most
+  // n * G' / 128 + 1 blocks, so the batch at most total_q * G' / 128 + B — and never more than the launch carries
+  const bool packed = kvcache_vq_packs(p, pack_gqa);
+  const int gp = packed ? p->H / p->Hk : 1;
+  const long long nmb = ((long long)vq->max_seqlen_q * gp + 127) / 128;
+  const long long launched = (long long)p->B * nmb, filled = ((long long)vq->total_q * gp + 127) / 128 + p->B;
+  const long long blocks = (long long)(packed ? p->Hk : p->H) * (launched < filled ? launched : filled);
+  const int cus = num_cus();
+  if (blocks * 2 > cus || p->capacity < 4096) return 1;
+  if (p->is_causal && vq->max_seqlen_q > 1 && (long long)vq->max_seqlen_q * 4 > p->capacity) return 1;
+  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
+  if (s > p->capacity / 1024) s = p->capacity / 1024;
+  if (s > 32) s = 32;
+  return s >= 2 ? (int)s : 1;
+}
+
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {
   const int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;

@@ -15,6 +15,7 @@
 #pragma once
 #include "tfa_fwd_kernel.h"
 #include "tfa_acc_regs.h"
+#include <type_traits>
 
 namespace tfa {
 
@@ -158,6 +159,30 @@ template <bool PACK>
 struct KvcPackView {
   template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
 };
+// The varlen-q form of the KV-cache form (tfa_fwd_kvcache_varlen; FlashAttention-3's cu_seqlens_q / max_seqlen_q): q is packed (total_q, H, D) and sequence b owns the
+// query rows [q0_b, q0_b + nq_b) — q0_b = clamp(cu[b], 0, total_q), nq_b = clamp(cu[b + 1] - cu[b], 0, min(max_q, total_q - q0_b)) — read and clamped by every work
+// item itself, as scalar loads, the way it reads the sequence's length.  The launch carries nmb = ceil(max_q * G' / 128) query blocks per (sequence, head) (G' = G packed,
+// 1 unpacked; KArgs::Nq = max_q * G' sizes it and is not read by this form's statements); a block with no row of its sequence (mb * 128 >= nq_b * G') issues no Q, K or V
+// request and no store.  Everything that reads the launch-uniform Nq / nq_pos elsewhere takes nq_b here: the causal shift len_b - nq_b, the packed block's last valid
+// row, row validity.  The Q descriptor starts at row q0_b and ends at the sequence's last row; O, LSE and the fp32 partials go to (h, q0_b + t) of (H, total_q, .)
+// buffers — qs_b / os_b are 0, os_h / the LSE's head stride total_q rows — so tfa_merge runs unchanged over H * total_q rows.  Known cost: the grid is sized by max_q, so
+// one long prefill chunk in a batch of decode rows makes most work items empty; each empty item costs its scalar loads and an exit.
+// The arguments ride BEHIND the form's struct (KvcArgs, Kvc8Args or their KvcPacked<>), for KvcPacked's reason: no existing kernel's argument block moves.
+// G = 1 (MHA) is served by the unpacked instantiations (KvcPacked::pk_g is 2..128): that is why both exist.
+template <typename Base>
+struct KvcVarlenQ : Base {
+  using vq_base = Base;
+  const int* vq_cu;         // device int32, B + 1 entries
+  int vq_max_q;             // max_seqlen_q: the most rows a sequence brings
+  int vq_total_q;           // rows of q / out / lse
+};
+template <typename B> struct KvcPack<const KvcVarlenQ<B>> : KvcPack<const B> {};
+template <typename A> struct KvcVq { static constexpr bool value = false; };
+template <typename B> struct KvcVq<const KvcVarlenQ<B>> { static constexpr bool value = true; };
+template <bool VQ>
+struct KvcVqView {
+  template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
+};
 template <bool KV8, typename T> struct KvElem { using type = T; };
 template <typename T> struct KvElem<true, T> { using type = unsigned char; };
 
@@ -227,6 +252,14 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_pack(const KvcPacke
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8_pack(const KvcPacked<Kvc8Args> p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+
+// The varlen-q forms of the four (packed ragged query rows: KvcVarlenQ above).  Args: KvcVarlenQ<> of KvcArgs, Kvc8Args or their KvcPacked<>; the e4m3 cache side
+// is the Args' own (Kvc8Args among its bases)
+template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT, typename Args>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_vq(const Args p) {
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0) | (NT ? VF_DMA_NT : 0);
 #include "tfa_fwd_kernel_dma_body.inc"
 }
 

@@ -6,6 +6,9 @@
   // the packed form of the KV-cache form (KvcPacked: GQA query heads as position-major rows, row = t * G + g); its arguments are read through KvcPackView<PACK>::of(p),
   // a dependent expression every other entry point never instantiates
   constexpr bool PACK = KVC && KvcPack<decltype(p)>::value;
+  // the varlen-q form of the KV-cache form (KvcVarlenQ: packed ragged query rows, every sequence's first row and row count read on the device); its arguments are read
+  // through KvcVqView<VQ>::of(p), as above
+  constexpr bool VQ = KVC && KvcVq<decltype(p)>::value;
   constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
   using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
@@ -89,6 +92,8 @@
   // paged: the block-table entry of the page the last tile issued lies in — one scalar load per page, not per tile (tiles are issued in ascending order; the
   // entry of the NEXT tile's page is requested right behind a tile's DMA pieces, a tile of compute ahead of its use)
   int pg_idx = -1, pg_val = 0;
+  // varlen-q form: the first query row, the row count and the block rows (nq_b * G packed) of the sequence the last decode() described
+  int vq_q0 = 0, vq_nq = 0, vq_rows = 0;
   auto decode = [&](int item_all, int pass, Blk& k) {
     k.sp = item_all / nitems0;
     const int item = item_all - k.sp * nitems0;
@@ -106,7 +111,20 @@
       const int chunk = (fd_div(len + nsplit - 1, pk.fd_nsplit) + 63) & ~63;
       const int rest = len - k.sp * chunk;
       k.nk = rest < chunk ? (rest > 0 ? rest : 0) : chunk;
-      k.shift = len - pk.nq_pos - k.sp * chunk;
+      int nq_pos = pk.nq_pos;
+      if constexpr (VQ) {
+        // the sequence's rows of the packed q, read and clamped as the length is: whatever cu_seqlens_q holds, [q0, q0 + nq) lies inside [0, total_q) and nq <= max_q
+        const auto& pv = KvcVqView<VQ>::of(p);
+        const int c0 = ((const cint4*)(uintptr_t)pv.vq_cu)[b0], c1 = ((const cint4*)(uintptr_t)pv.vq_cu)[b0 + 1];
+        vq_q0 = c0 < 0 ? 0 : (c0 > pv.vq_total_q ? pv.vq_total_q : c0);
+        const int room = pv.vq_total_q - vq_q0 < pv.vq_max_q ? pv.vq_total_q - vq_q0 : pv.vq_max_q;
+        const long long d = (long long)c1 - c0;
+        vq_nq = d < 0 ? 0 : (d > room ? room : (int)d);
+        vq_rows = vq_nq;
+        if constexpr (PACK) vq_rows = vq_nq * KvcPackView<PACK>::of(p).pk_g;
+        nq_pos = vq_nq;
+      }
+      k.shift = len - nq_pos - k.sp * chunk;
       k.tile0 = (k.sp * chunk) >> 6;
       k.bt_row = b0;
       pg_idx = -1;
@@ -129,14 +147,27 @@
     if (CAUSAL) {
       int lim = k.mb * BM + BM + k.shift;                        // one past the last key any row of the block sees
       if constexpr (PACK) {                                      // ... the position of the block's last valid row sees
-        const int last = k.mb * BM + BM - 1 < p.Nq - 1 ? k.mb * BM + BM - 1 : p.Nq - 1;
+        int rows = p.Nq;
+        if constexpr (VQ) rows = vq_rows > 0 ? vq_rows : 1;      // (a sequence without rows: every block of it is empty, below)
+        const int last = k.mb * BM + BM - 1 < rows - 1 ? k.mb * BM + BM - 1 : rows - 1;
         lim = fd_div(last, KvcPackView<PACK>::of(p).pk_fd_g) + 1 + k.shift;
       }
       kv_end = lim < kv_end ? lim : kv_end;
     }
     k.nt = kv_end > 0 ? (kv_end + BN - 1) / BN : 0;
+    if constexpr (VQ) {
+      if (k.mb * BM >= vq_rows) k.nt = 0;                        // a block without rows of its sequence: no K/V tile (prefetch: no Q either; the epilogue: no store)
+    }
     const int b = k.bh / p.H, h = k.bh - b * p.H, hk = h / (p.H / p.Hk);
-    k.q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const T*>(p.q) + b * p.qs_b + h * p.qs_h), 0, (unsigned)p.q_bytes, 0x00020000);
+    const T* q_base = reinterpret_cast<const T*>(p.q) + b * p.qs_b + h * p.qs_h;
+    unsigned q_ext = (unsigned)p.q_bytes;
+    if constexpr (VQ) {                                          // from the sequence's first row to its last (qs_b is 0; the host bounds max_q rows by 2 GiB)
+      long long e = (long long)(vq_nq - 1) * p.qs_n + p.dv;
+      if constexpr (PACK) e += (long long)(KvcPackView<PACK>::of(p).pk_g - 1) * KvcPackView<PACK>::of(p).q_hs;
+      q_base += (long long)vq_q0 * p.qs_n;
+      q_ext = vq_nq > 0 ? (unsigned)(e * 2) : 0u;
+    }
+    k.q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)q_base, 0, q_ext, 0x00020000);
     unsigned kb = (unsigned)p.k_bytes, vb = (unsigned)p.v_bytes;
     long long koff = 0, voff = 0;
     if constexpr (KVC) {
@@ -257,12 +288,22 @@
     if (PD > 1 && k.nt > 1) dma_issue(k, 1, 1);
     const int row = k.mb * BM + wave * 32 + qi;
     int qoff = row * (int)p.qs_n * 2 + hi * 16;
+    int q_rows = p.Nq;                                           // (read by the packed and varlen-q forms only)
+    if constexpr (VQ) {
+      q_rows = vq_rows;
+      if (k.mb * BM >= q_rows) {                                 // no row of the sequence in this block: nothing is requested
+#pragma unroll
+        for (int s = 0; s < DS; ++s) qf[s] = __builtin_bit_cast(X8, u32x4{0u, 0u, 0u, 0u});
+        return;
+      }
+      if constexpr (!PACK) qoff = row < q_rows ? qoff : (int)TFA_OOB;
+    }
     if constexpr (PACK) {
       // row = t * G + g lies at t * qs_n + g * q_hs behind the head group's base: the descriptor's extent bounds the group, not the rows — the rows behind the
       // last one (which would alias rows of the next positions' heads) are sent out of range here
       const auto& pp = KvcPackView<PACK>::of(p);
       const int t = fd_div(row, pp.pk_fd_g), g = row - t * pp.pk_g;
-      qoff = row < p.Nq ? (t * (int)p.qs_n + g * (int)pp.q_hs) * 2 + hi * 16 : (int)TFA_OOB;
+      qoff = row < q_rows ? (t * (int)p.qs_n + g * (int)pp.q_hs) * 2 + hi * 16 : (int)TFA_OOB;
     }
 #pragma unroll
     for (int s = 0; s < DS; ++s) {
@@ -285,12 +326,18 @@
     const int my_row = wave_row0 + qi;
     // the query POSITIONS the causal bounds below are formed from: the row's own, the wave's first row's and its last valid row's.  Packed: t = row / G
     int my_t = my_row, my_g = 0, wave_t0 = wave_row0, wave_t1 = wave_row0 + 31;
+    // the block's row count, first query row and positions: the launch's, or (varlen-q form) its sequence's — copies, decode() of the next block overwrites vq_*
+    int nrows = p.Nq;
+    const int cur_q0 = vq_q0, cur_nq = vq_nq;
+    if constexpr (VQ) nrows = vq_rows;
     if constexpr (PACK) {
       const auto& pp = KvcPackView<PACK>::of(p);
       my_t = fd_div(my_row, pp.pk_fd_g);
       my_g = my_row - my_t * pp.pk_g;
       wave_t0 = fd_div(wave_row0, pp.pk_fd_g);
-      wave_t1 = fd_div(wave_row0 + 31 < p.Nq - 1 ? wave_row0 + 31 : p.Nq - 1, pp.pk_fd_g);
+      int last_row = nrows - 1;
+      if constexpr (VQ) last_row = nrows > 0 ? nrows - 1 : 0;
+      wave_t1 = fd_div(wave_row0 + 31 < last_row ? wave_row0 + 31 : last_row, pp.pk_fd_g);
     }
 
     f32x16 oacc[WIDE ? 1 : DT];
@@ -536,7 +583,20 @@
     }
 
     // ---- epilogue of the block just finished ------------------------------------------------------
+    if constexpr (VQ) {
+      if (wave_row0 - wave * 32 >= nrows) {                  // a block without rows: nothing to store; the next block of the stream has been requested above
+        if (!have_next) break;
+        continue;
+      }
+    }
     const int ob = cur_bh / p.H, oh = cur_bh - ob * p.H;
+    // varlen-q form: the extent of the sequence's rows of O behind (h, q0_b) — the descriptors below end at its last row
+    unsigned o_ext = (unsigned)p.o_bytes;
+    if constexpr (VQ) {
+      long long e = (long long)(cur_nq - 1) * p.os_n + p.dv;
+      if constexpr (PACK) e += (long long)(KvcPackView<PACK>::of(p).pk_g - 1) * KvcPackView<PACK>::of(p).o_hs;
+      o_ext = cur_nq > 0 ? (unsigned)(e * (F32OUT ? 4 : 2)) : 0u;
+    }
     float og[WIDE ? DT : 1][16];                           // WIDE: O read out of the hand-owned AccVGPRs
     if constexpr (WIDE) {
 #pragma unroll
@@ -546,17 +606,25 @@
     const float l_tot = pair_sum(l_run);
     const bool empty = !(l_tot > 0.f);
     const float inv = KV8 ? (empty ? 1.f : 1.f / l_tot) * cur_vd : (empty ? 1.f : 1.f / l_tot);   // e4m3 form: v_descale in fp32, in front of the one rounding of O
-    if (p.lse != nullptr && hi == 0 && my_row < p.Nq) {
+    if (p.lse != nullptr && hi == 0 && my_row < nrows) {
       const float lse = empty ? INFINITY : (m_run * (KV8 ? cur_scale_lse : p.scale) + __builtin_amdgcn_logf(l_tot) * 0.6931471805599453f);
       // (packed: cur_bh = b * Hk + hk and p.Nq = Nq * G, so the first two terms are the caller's (b * H + hk * G) * Nq; head g, position t follow)
-      if constexpr (PACK) p.lse[lse_part + (long long)cur_bh * p.Nq + my_g * KvcPackView<PACK>::of(p).nq_pos + my_t] = lse;
+      // (varlen-q: (H, total_q) — head oh, or hk * G + g packed, at row q0_b + t)
+      if constexpr (VQ) {
+        int lh = oh;
+        if constexpr (PACK) lh = oh * KvcPackView<PACK>::of(p).pk_g + my_g;
+        p.lse[lse_part + (long long)lh * KvcVqView<VQ>::of(p).vq_total_q + cur_q0 + my_t] = lse;
+      }
+      else if constexpr (PACK) p.lse[lse_part + (long long)cur_bh * p.Nq + my_g * KvcPackView<PACK>::of(p).nq_pos + my_t] = lse;
       else p.lse[lse_part + (long long)cur_bh * p.Nq + my_row] = lse;
     }
     if (F32OUT) {
       float* obase = reinterpret_cast<float*>(p.o) + o_part + ob * p.os_b + oh * p.os_h;
-      auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, (unsigned)p.o_bytes, 0x00020000);
+      if constexpr (VQ) obase += (long long)cur_q0 * p.os_n;
+      auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, o_ext, 0x00020000);
       int ooff = my_row * (int)p.os_n * 4 + hi * 16;
-      if constexpr (PACK) ooff = my_row < p.Nq ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 4 + hi * 16 : (int)TFA_OOB;   // the caller's (b, h, t) row
+      if constexpr (VQ && !PACK) ooff = my_row < nrows ? ooff : (int)TFA_OOB;
+      if constexpr (PACK) ooff = my_row < nrows ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 4 + hi * 16 : (int)TFA_OOB;   // the caller's (b, h, t) row
 #pragma unroll
       for (int d = 0; d < DT; ++d)
 #pragma unroll
@@ -600,9 +668,11 @@
       }
     } else {
       T* obase = reinterpret_cast<T*>(p.o) + o_part + ob * p.os_b + oh * p.os_h;
-      auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, (unsigned)p.o_bytes, 0x00020000);
+      if constexpr (VQ) obase += (long long)cur_q0 * p.os_n;
+      auto o_rs = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, o_ext, 0x00020000);
       int ooff = my_row * (int)p.os_n * 2 + hi * 8;
-      if constexpr (PACK) ooff = my_row < p.Nq ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 2 + hi * 8 : (int)TFA_OOB;
+      if constexpr (VQ && !PACK) ooff = my_row < nrows ? ooff : (int)TFA_OOB;
+      if constexpr (PACK) ooff = my_row < nrows ? (my_t * (int)p.os_n + my_g * (int)KvcPackView<PACK>::of(p).o_hs) * 2 + hi * 8 : (int)TFA_OOB;
       typedef __attribute__((ext_vector_type(4))) T t4;
 #pragma unroll
       for (int d = 0; d < DT; ++d)

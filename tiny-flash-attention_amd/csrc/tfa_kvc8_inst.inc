@@ -5,13 +5,22 @@
 #ifndef TFA_KVC_PACK
 #define TFA_KVC_PACK 0       // 1: the unit of the packed form (tfa_kvc8_inst_pack_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc8_pack and its arguments
 #endif
+#ifndef TFA_KVC_VQ
+#define TFA_KVC_VQ 0         // 1: the unit of the varlen-q form (tfa_kvc8_inst_vq_<dtype>_<W>, tfa_kvc8_inst_pack_vq_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc_vq
+#endif
 
 namespace tfa {
 
+// the arguments of this unit's kernels: the form's struct, behind it the packed form's (TFA_KVC_PACK), behind both the varlen-q form's (TFA_KVC_VQ)
+using UnitBase = std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<Kvc8Args>, Kvc8Args>;
+using UnitArgs = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
+
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-static hipError_t launch_kvc8_one(const std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<Kvc8Args>, Kvc8Args>& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
+static hipError_t launch_kvc8_one(const UnitArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
   constexpr int lds = 4 * 64 * D * 2;                          // two K and two V tile buffers of DECODED (16-bit) tiles: the 16-bit form's size
-#if TFA_KVC_PACK
+#if TFA_KVC_VQ
+  auto kern = fwd_kernel_dma_kvc_vq<T, D, CAUSAL, F32OUT, NT, UnitArgs>;
+#elif TFA_KVC_PACK
   auto kern = fwd_kernel_dma_kvc8_pack<T, D, CAUSAL, F32OUT, NT>;
 #else
   auto kern = fwd_kernel_dma_kvc8<T, D, CAUSAL, F32OUT, NT>;
@@ -30,7 +39,9 @@ static hipError_t launch_kvc8_one(const std::conditional_t<TFA_KVC_PACK != 0, Kv
 }
 
 template <>
-#if TFA_KVC_PACK
+#if TFA_KVC_VQ
+hipError_t launch_kvc_vq<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a,
+#elif TFA_KVC_PACK
 hipError_t launch_kvc8_pack<TFA_T, TFA_D>(const KvcPacked<Kvc8Args>& a,
 #else
 hipError_t launch_kvc8<TFA_T, TFA_D>(const Kvc8Args& a,

@@ -217,6 +217,15 @@ hipError_t launch_kvc8_pack(const KvcPacked<Kvc8Args>& a, bool causal, bool f32o
   template <> hipError_t launch_kvc8_pack<T, D>(const KvcPacked<Kvc8Args>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
 TFA_KVCP_UNITS(__bf16, 64) TFA_KVCP_UNITS(__bf16, 128) TFA_KVCP_UNITS(_Float16, 64) TFA_KVCP_UNITS(_Float16, 128)
 #undef TFA_KVCP_UNITS
+// ... and the varlen-q forms of the four (tfa_fwd_kvcache_varlen; fwd_kernel_dma_kvc_vq): units of their own, tfa_kvc_inst_vq_*, tfa_kvc_inst_pack_vq_*, tfa_kvc8_inst_vq_*
+// and tfa_kvc8_inst_pack_vq_* — the same .inc files compiled with TFA_KVC_VQ.  Args: KvcVarlenQ<> of the form's struct
+template <typename T, int D, typename Args>
+hipError_t launch_kvc_vq(const Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVCVQ_UNIT(T, D, A) template <> hipError_t launch_kvc_vq<T, D, KvcVarlenQ<A>>(const KvcVarlenQ<A>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+#define TFA_KVCVQ_UNITS(T, D) TFA_KVCVQ_UNIT(T, D, KvcArgs) TFA_KVCVQ_UNIT(T, D, Kvc8Args) TFA_KVCVQ_UNIT(T, D, KvcPacked<KvcArgs>) TFA_KVCVQ_UNIT(T, D, KvcPacked<Kvc8Args>)
+TFA_KVCVQ_UNITS(__bf16, 64) TFA_KVCVQ_UNITS(__bf16, 128) TFA_KVCVQ_UNITS(_Float16, 64) TFA_KVCVQ_UNITS(_Float16, 128)
+#undef TFA_KVCVQ_UNITS
+#undef TFA_KVCVQ_UNIT
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

@@ -902,7 +902,8 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
-                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, k_descale=None, v_descale=None):
+                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None,
+                            v_descale=None):
     """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
 
     ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
@@ -927,6 +928,19 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     output by ``v_descale[b, hk]`` in fp32; Q and P are not quantised.  ``k`` / ``v`` are quantised on the device as they are appended —
     ``rne_e4m3fn(clamp(x / descale, -448, 448))`` — and attended as quantised.  The descales are read by the kernels only (no synchronisation; a captured step sees
     values overwritten in place) and must be finite and > 0.  The head dim must be a multiple of 16.
+    ``cu_seqlens_q`` / ``max_seqlen_q`` (keyword-only, FlashAttention-3's; tfa_fwd_kvcache_varlen): packed ragged query rows — the call for a unified batch of
+    decode rows and chunked-prefill rows.  ``q`` is then (total_q, H, D) with any row and head strides, unit stride along D and 16-byte aligned rows;
+    ``cu_seqlens_q`` a contiguous int32 device tensor of B + 1 entries, never read on the host; ``max_seqlen_q`` a positive host int (required: it sizes the
+    grid).  B = cu_seqlens_q.numel() - 1 must be the batch of a contiguous cache, the rows of ``block_table``, of ``cache_seqlens`` and of the descales.  Sequence
+    b owns the rows [q0_b, q0_b + nq_b), q0_b = clamp(cu_seqlens_q[b], 0, total_q), nq_b = clamp(cu_seqlens_q[b+1] - cu_seqlens_q[b], 0, min(max_seqlen_q,
+    total_q - q0_b)), and attends keys [0, len_b), len_b = clamp(cache_seqlens[b], 0, capacity): ``cache_seqlens`` INCLUDES the rows appended for this step (pass
+    ``cache_seqlens_before + (cu_seqlens_q[1:] - cu_seqlens_q[:-1])``, a device op).  ``causal``: key j is visible to row t of sequence b iff
+    j <= t + (len_b - nq_b).  A row that sees no key gives out = 0, lse = +inf; nq_b = 0 is legal; rows of out / lse that belong to no sequence are unspecified.
+    ``k`` / ``v`` must be None (ValueError: ``kvcache_append_varlen`` is the append for packed rows).  ``pack_gqa``: None and True pack whenever Hk < H and
+    H / Hk <= 128, False runs unpacked (as do H == Hk and H / Hk > 128).  ``num_splits=0`` asks tfa_fwd_kvcache_varlen_suggest_splits.  Returns ``out``
+    (total_q, H, D), a transposed view of the dense (H, total_q, D) buffer the kernel or the merge writes, and ``lse`` (H, total_q) fp32.  Paged and contiguous
+    caches, fp8 caches with descales, zero fill behind the lengths, no host synchronisation, graph capture and "not differentiable": as above.  The grid is sized
+    by ``max_seqlen_q``: one long prefill chunk in a batch of decode rows makes most work items empty (each costs its scalar loads and an exit).
     Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes,
     fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
     name = "flash_attn_with_kvcache"
@@ -938,6 +952,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise NotImplementedError(f"{name}: window_size is not implemented in the K/V-cache path (got {tuple(window_size)})")
     if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
         raise NotImplementedError(f"{name}: softcap is not implemented in the K/V-cache path")
+    if cu_seqlens_q is None and max_seqlen_q is not None:
+        raise ValueError(f"{name}: max_seqlen_q belongs to cu_seqlens_q (packed (total_q, H, D) query rows), which was not given")
+    if cu_seqlens_q is not None:
+        return _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse,
+                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q)
     for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{name}: {n} must be a 4-D tensor")
@@ -1052,6 +1071,142 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         else:
             _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
     out = dense.transpose(1, 2)
+    return (out, lse) if return_softmax_lse else out
+
+
+def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse, pack_gqa,
+                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q):
+    """``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=)`` (tfa_fwd_kvcache_varlen): the checks of the packed form, then the calls.  Every refusal comes
+    before any library call."""
+    name = "flash_attn_with_kvcache"
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        got = tuple(q.shape) if isinstance(q, torch.Tensor) else type(q).__name__
+        raise ValueError(f"{name}: with cu_seqlens_q, q must be packed (total_q, H, D) (got {got}); a 4-D q takes no cu_seqlens_q")
+    for n, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be a 4-D tensor")
+    for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+    if k is not None or v is not None:
+        raise ValueError(f"{name}: with cu_seqlens_q, k / v must be None — kvcache_append_varlen is the append for packed rows (cache_seqlens then includes them)")
+    if max_seqlen_q is None or isinstance(max_seqlen_q, (bool, torch.Tensor)) or not isinstance(max_seqlen_q, int) or max_seqlen_q <= 0:
+        raise ValueError(f"{name}: cu_seqlens_q needs max_seqlen_q, a positive host int (it sizes the grid; got {max_seqlen_q!r})")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+        raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of B + 1 entries")
+    if cu_seqlens_q.device != q.device or not cu_seqlens_q.is_contiguous():
+        raise ValueError(f"{name}: cu_seqlens_q must be contiguous and on q's device")
+    if q.dtype == torch.float32:
+        raise ValueError(f"{name}: float16 / bfloat16 inputs only (no fp32 K/V-cache path)")
+    if q.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
+    total_q, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    if total_q <= 0:
+        raise ValueError(f"{name}: q holds no row")
+    if D > 128:
+        raise ValueError(f"{name}: head dims up to 128 (got {D})")
+    if D % 8 != 0 or D < 8:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
+        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype, or both caches be torch.float8_e4m3fn (got {q.dtype}, {k_cache.dtype}, "
+                        f"{v_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
+    if fp8 and D % 16 != 0:
+        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError(f"{name}: k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a {k_cache.dtype} cache)")
+    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
+        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    Hk = k_cache.shape[2]
+    if Hk <= 0 or H % Hk != 0:
+        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
+    for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name}: {n} must be a float32 tensor")
+        if tuple(t.shape) != (B, Hk) or t.device != q.device:
+            raise ValueError(f"{name}: {n} must have shape ({B}, {Hk}) — B = cu_seqlens_q.numel() - 1 — on q's device (got {tuple(t.shape)} on {t.device})")
+    if q.stride(2) != 1 or k_cache.stride(3) != 1 or v_cache.stride(3) != 1:
+        raise ValueError(f"{name}: q, k_cache and v_cache must have unit stride along the head dim")
+    if (q.stride(0) * 2) % 16 != 0 or (q.stride(1) * 2) % 16 != 0:
+        raise ValueError(f"{name}: the rows of q must be 16-byte aligned (strides {q.stride(0)}, {q.stride(1)} elements)")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks) — B = cu_seqlens_q.numel() - 1")
+        if block_table.device != q.device or block_table.stride(1) != 1:
+            raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
+        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0:
+            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
+        capacity = block_table.shape[1] * k_cache.shape[1]
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"{name}: a contiguous cache must have the batch size cu_seqlens_q.numel() - 1 = {B} (got {k_cache.shape[0]}); cache_batch_idx is not implemented")
+        capacity = k_cache.shape[1]
+    if capacity <= 0:
+        raise ValueError(f"{name}: the cache holds no key")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k_cache, v_cache)):
+        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
+    if cache_seqlens is None:
+        cache_seqlens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
+    elif isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), int(cache_seqlens), dtype=torch.int32, device=q.device)
+    elif (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
+          or not cache_seqlens.is_contiguous() or cache_seqlens.device != q.device):
+        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},) — B = cu_seqlens_q.numel() - 1 — on q's device, a host int, or None")
+    num_splits = int(num_splits)
+    if num_splits < 0:
+        raise ValueError(f"{name}: num_splits must be >= 0 (0 = automatic; got {num_splits})")
+    if pack_gqa is not None and pack_gqa is not True and pack_gqa is not False:
+        raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+
+    L = _lib.lib()
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device) if return_softmax_lse else None
+    dense = torch.empty((H, total_q, D), dtype=q.dtype, device=q.device)          # what the merge writes; one chunk: the kernel writes it the same way
+    p = _lib.TfaKvcacheParams()
+    p.q, p.out = q.data_ptr(), dense.data_ptr()
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    p.cache_seqlens = cache_seqlens.data_ptr()
+    p.B, p.H, p.Hk, p.Nq, p.D, p.capacity = B, H, Hk, 0, D, capacity              # (Nq is not looked at)
+    if block_table is not None:
+        p.block_table = block_table.data_ptr()
+        p.block_table_stride = block_table.stride(0)
+        p.page_size, p.num_pages = k_cache.shape[1], k_cache.shape[0]
+    p.q_stride[0], p.q_stride[1], p.q_stride[2] = 0, q.stride(1), q.stride(0)     # {ignored, head, row}
+    p.o_stride[0], p.o_stride[1], p.o_stride[2] = 0, total_q * D, D
+    for sname, t in (("k_stride", k_cache), ("v_stride", v_cache)):
+        arr = getattr(p, sname)
+        arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)
+    p.softmax_scale = float(softmax_scale)
+    p.is_causal = 1 if causal else 0
+    p.dtype = _DT[q.dtype]
+    vq = _lib.TfaKvcacheVarlenQ()
+    vq.cu_seqlens_q = cu_seqlens_q.data_ptr()
+    vq.max_seqlen_q, vq.total_q = int(max_seqlen_q), total_q
+    pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
+    if num_splits == 0:
+        num_splits = max(1, int(L.tfa_fwd_kvcache_varlen_suggest_splits(C.byref(p), C.byref(vq), pack)))
+    p8 = None
+    if fp8:
+        p8 = _lib.TfaKvcacheFp8()
+        p8.format = _lib.TFA_KV_E4M3
+        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
+            if t is not None:
+                setattr(p8, ptr, t.data_ptr())
+                strides[0], strides[1] = t.stride(0), t.stride(1)
+    q8 = C.byref(p8) if fp8 else None
+    need = L.tfa_fwd_kvcache_varlen_workspace(C.byref(p), C.byref(vq), q8, pack, num_splits)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.tfa_fwd_kvcache_varlen(C.byref(p), C.byref(vq), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+    out = dense.transpose(0, 1)
     return (out, lse) if return_softmax_lse else out
 
 
