@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + packed ragged query rows over a K/V cache — tfa_fwd_kvcache_varlen and its _workspace / _plan / _suggest_splits companions (struct tfa_kvcache_varlen_q: cu_seqlens_q in device memory, max_seqlen_q, total_q; q packed (total_q, H, D), every sequence's rows read and clamped on the device: the varlen-q form of the KV-cache kernel, packed GQA rows by default); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + the packed append into an e4m3 cache and / or with q rotated in place in the same launch — tfa_kvcache_append_varlen_ex / _plan (struct tfa_append_q; tfa_kvcache_fp8 as in tfa_fwd_kvcache_fp8); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + packed ragged query rows over a K/V cache — tfa_fwd_kvcache_varlen and its _workspace / _plan / _suggest_splits companions (struct tfa_kvcache_varlen_q: cu_seqlens_q in device memory, max_seqlen_q, total_q; q packed (total_q, H, D), every sequence's rows read and clamped on the device: the varlen-q form of the KV-cache kernel, packed GQA rows by default); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -904,7 +904,8 @@ int tfa_rotary_plan(const tfa_rotary_params* p, int* grid, int* block);
  * with tables seqlen_ro <= 0, rotary_interleaved not 0 or 1, reserved_ != 0 (TFA_ERR_SHAPE); strides negative or not multiples of 16 bytes, row strides below D,
  * block_table_stride < capacity / page_size, a table row stride below rotary_dim / 2 (TFA_ERR_STRIDE); bases not 16-byte aligned, the int32 arrays not 4-byte aligned
  * (TFA_ERR_ALIGN).
- * Out of scope: fp8 caches (tfa_fwd_varlen_paged reads 16-bit pools only), a rotation of anything but K, advancing cache_seqlens.
+ * e4m3 caches and the step's q rotated in the same launch: tfa_kvcache_append_varlen_ex, below (this entry point serves 16-bit caches and rotates K only).
+ * Out of scope: advancing cache_seqlens.
  * Measured: profiles/rotary_append_bench.txt (tools/bench_rotary_append.py), quoted in README.md. */
 typedef struct tfa_kvcache_append_varlen_params {
   const void* k;                  /* (total_new, Hk, D) by k_stride */
@@ -922,7 +923,7 @@ typedef struct tfa_kvcache_append_varlen_params {
   int32_t num_pages;              /* paged: pages in the caches; contiguous: ignored */
   int32_t rotary_dim, seqlen_ro;  /* with tables only */
   int32_t rotary_interleaved;
-  int32_t dtype;                  /* TFA_F16 or TFA_BF16: k, v, caches */
+  int32_t dtype;                  /* TFA_F16 or TFA_BF16: k, v, caches (tfa_kvcache_append_varlen_ex with q8: k, v and q; the caches hold e4m3) */
   int32_t cs_dtype;               /* with tables: dtype, or TFA_F32 */
   int64_t k_stride[2];            /* head, row (elements) */
   int64_t v_stride[2];
@@ -935,6 +936,43 @@ typedef struct tfa_kvcache_append_varlen_params {
 } tfa_kvcache_append_varlen_params;
 int tfa_kvcache_append_varlen(const tfa_kvcache_append_varlen_params* p, void* stream);
 int tfa_kvcache_append_varlen_plan(const tfa_kvcache_append_varlen_params* p, int* grid, int* block);
+
+/* ---- the packed append into an e4m3 cache, and / or with the step's q rotated in place in the same launch ------------------------------------------------
+ * tfa_kvcache_append_varlen with two optional companions; with both NULL the call IS tfa_kvcache_append_varlen's launch (the same kernel, the same bits).
+ * q8 (tfa_kvcache_fp8, as in tfa_fwd_kvcache_fp8): k_cache / v_cache hold e4m3fn bytes, paged or contiguous.  k / v stay 16-bit: p->dtype is THEIR dtype, and
+ *   kc_stride / vc_stride count cache elements, which are bytes.  Sequence, position, page lookup and every drop rule are the 16-bit packed append's.  Stored
+ *   byte = rne_e4m3fn(clamp(float(x) / descale[b, hk], -448, 448)) — a true fp32 division, NaN stays NaN: the rule, the device function (csrc/tfa_quantise8.h)
+ *   and the bits of tfa_kvcache_append_fp8.  The descales are indexed by the sequence b, not by the page, element (b, hk) at b * stride[0] + hk * stride[1]
+ *   (0 allowed: a broadcast per-tensor scale; NULL = 1.0), and read on the device only.  With rotary tables K is first rotated and rounded once to p->dtype —
+ *   the bits tfa_rotary leaves — and then quantised; V is only quantised: the caches hold the bytes of tfa_rotary(k, cu_seqlens, seqlen_offsets = cache_seqlens)
+ *   followed by the plain e4m3 append (a pos at or beyond seqlen_ro: stored unrotated).  D: a multiple of 16 in [16, 128]; cache strides: multiples of 16 bytes.
+ * rq (tfa_append_q): q, packed (total_new, H, D) of p->dtype with strides {head, row} in elements, unit stride along D, 16-byte aligned rows and base — a slice
+ *   of a packed QKV projection works — is rotated IN PLACE at the positions K is rotated at: row t of sequence b at cache_seqlens[b] + t.  It leaves the bits
+ *   of tfa_rotary(q, out = q, cu_seqlens, seqlen_offsets = cache_seqlens).  Untouched bit for bit: elements behind rotary_dim, rows outside every sequence,
+ *   rows whose position lies outside [0, seqlen_ro).  q has no capacity: a row whose K is dropped (beyond the capacity, a bad table entry) still has its q
+ *   rotated.  Requires the tables; no relation between H and Hk is needed.  PRECONDITION: q must not overlap k, v or the caches (k / v are read by other
+ *   threads of the launch than the ones that write q).
+ * Kernel (csrc/tfa_kvcache_append_varlen_ex.hip): the append's threads — one per (row, K/V head, 16-byte chunk of the 16-bit source); e4m3: 8-byte stores,
+ * neighbouring lanes neighbouring pieces of a row — followed by q's: one per (row, head, item of the rotated part), an item a pair of chunks (GPT-NeoX: the
+ * thread that stores a chunk loaded it, nothing to order in place) or one chunk (GPT-J).  _plan reports
+ *   ceil((total_new * Hk * D / 8 + total_new * H * items) / 256) blocks of 256 threads, items = rotary_dim / 16 (GPT-NeoX) or rotary_dim / 8 (GPT-J), 0 without rq;
+ * with q8 and rq both NULL, tfa_kvcache_append_varlen_plan's answer.
+ * Refused, nothing launched: everything tfa_kvcache_append_varlen refuses (with q8 the cache strides are checked as bytes); from q8 what tfa_kvcache_append_fp8
+ * refuses — format other than TFA_KV_E4M3 (TFA_ERR_DTYPE), reserved_ != 0 (TFA_ERR_SHAPE), D not a multiple of 16 in [16, 128] (TFA_ERR_HEAD_DIM), cache strides not
+ * multiples of 16 bytes, a negative descale stride (TFA_ERR_STRIDE), a descale pointer not 4-byte aligned (TFA_ERR_ALIGN); from rq — a NULL q, missing tables
+ * (TFA_ERR_NULL), H <= 0, reserved_ != 0 (TFA_ERR_SHAPE), strides negative or not multiples of 16 bytes, a row stride below D (TFA_ERR_STRIDE), a base not 16-byte
+ * aligned (TFA_ERR_ALIGN).
+ * Out of scope: an out-of-place q, per-token or per-page scales, scales computed on the device, e5m2 / e4m3fnuz caches, D > 128, advancing cache_seqlens.
+ * Measured: profiles/append_varlen_ex_bench.txt (tools/bench_rotary_append.py), quoted in README.md. */
+typedef struct tfa_append_q {
+  void* q;                        /* (total_new, H, D) by q_stride, of p->dtype; rotated in place */
+  int32_t H;
+  int32_t reserved_;              /* must be 0 */
+  int64_t q_stride[2];            /* head, row (elements) */
+} tfa_append_q;
+int tfa_kvcache_append_varlen_ex(const tfa_kvcache_append_varlen_params* p, const tfa_kvcache_fp8* q8 /* NULL: 16-bit caches */, const tfa_append_q* rq /* NULL: no q */,
+                                 void* stream);
+int tfa_kvcache_append_varlen_ex_plan(const tfa_kvcache_append_varlen_params* p, const tfa_kvcache_fp8* q8, const tfa_append_q* rq, int* grid, int* block);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen
 takes ``attn_bias``: a dense additive bias or mask as scaled_dot_product_attention's ``attn_mask`` (fixed-length calls; no gradient for the bias).
 Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append; 16-bit or fp8 e4m3 caches with ``k_descale`` / ``v_descale``).
 Around attention: ``apply_rotary_emb`` / ``apply_rotary_emb_qk_`` (rotary embedding at device-side positions) and ``kvcache_append_varlen`` (a unified batch's
-new K/V rows into a paged or contiguous cache, K optionally rotated on the way in) — with the two attention calls a whole decode or chunked-prefill step.
+new K/V rows into a paged or contiguous cache — 16-bit or e4m3 with descales —, K optionally rotated on the way in and q in place in the same launch) — with the two attention calls a whole decode or chunked-prefill step.
 """
 from .ops import (  # noqa: F401
     flash_attention_v2_cutlass,

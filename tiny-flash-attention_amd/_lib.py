@@ -111,6 +111,8 @@ SYMBOLS = (
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
     "tfa_kvcache_append_varlen_plan",
+    "tfa_kvcache_append_varlen_ex",
+    "tfa_kvcache_append_varlen_ex_plan",
 )
 
 
@@ -417,6 +419,17 @@ class TfaKvcacheAppendVarlenParams(C.Structure):
     ]
 
 
+class TfaAppendQ(C.Structure):
+    """struct tfa_append_q (include/tfa.h): the q that tfa_kvcache_append_varlen_ex rotates in place, handed over beside TfaKvcacheAppendVarlenParams."""
+
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("H", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("q_stride", C.c_int64 * 2),
+    ]
+
+
 class TfaError(RuntimeError):
     def __init__(self, status, text):
         super().__init__(f"tfa status {status}: {text}")
@@ -589,7 +602,10 @@ def lib():
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),
-                       ("tfa_kvcache_append_varlen", [PA, C.c_void_p]), ("tfa_kvcache_append_varlen_plan", [PA, IP, IP])):
+                       ("tfa_kvcache_append_varlen", [PA, C.c_void_p]), ("tfa_kvcache_append_varlen_plan", [PA, IP, IP]),
+                       # ... into an e4m3 cache and / or with q rotated in the launch (P8 / the tfa_append_q may be None)
+                       ("tfa_kvcache_append_varlen_ex", [PA, P8, C.POINTER(TfaAppendQ), C.c_void_p]),
+                       ("tfa_kvcache_append_varlen_ex_plan", [PA, P8, C.POINTER(TfaAppendQ), IP, IP])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args
     _lib = L

@@ -2,34 +2,15 @@
 // tfa_fwd_kvcache_fp8 when k_new / v_new are given).  tfa_kvcache_append.hip with a quantisation in the middle: every thread reads one 16-byte chunk (8 elements) of one new K
 // row and of the V row, divides by the (sequence, K/V head)'s descale in fp32 (a true division: no fast-math in this build), clamps into the finite e4m3 range — the
 // conversion does not saturate: without the clamp everything above 448 would become NaN — converts with round-to-nearest-even and stores 8 bytes.  A NaN stays NaN.
+// (tfa_quantise8.h: the arithmetic, shared with the packed append.)
 // Positions, capacity and page checks are the 16-bit append's: nothing is ever stored outside the cache tensors.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tfa_kvcache.h"
+#include "tfa_quantise8.h"
 
 namespace tfa {
-
-template <typename T>
-static __device__ __forceinline__ void quantise8(const void* src, long long off, float d, void* dst, long long doff) {
-  typedef __attribute__((ext_vector_type(8))) T t8;
-  typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-  const t8 x = *reinterpret_cast<const t8*>(reinterpret_cast<const T*>(src) + off);
-  float y[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float q = (float)x[i] / d;
-    y[i] = q != q ? q : fminf(fmaxf(q, -448.f), 448.f);
-  }
-  u32x2 r;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * h + 0], y[4 * h + 1], 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * h + 2], y[4 * h + 3], w, true);
-    r[h] = (unsigned)w;
-  }
-  *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(dst) + doff) = r;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void kvcache_append_fp8_kernel(const Append8Args a) {

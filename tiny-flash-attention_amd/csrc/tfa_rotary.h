@@ -1,6 +1,6 @@
-// tfa_rotary.h — rotary position embedding (include/tfa.h: tfa_rotary, tfa_kvcache_append_varlen): the pair arithmetic, ONCE, as device functions both kernels
-// call (tfa_rotary.hip rotates a tensor; tfa_kvcache_append_varlen.hip rotates K on its way into the cache and must leave the same bits), the search that finds
-// a packed row's sequence, and the two launchers' arguments.
+// tfa_rotary.h — rotary position embedding (include/tfa.h: tfa_rotary, tfa_kvcache_append_varlen, tfa_kvcache_append_varlen_ex): the pair arithmetic, ONCE, as device
+// functions all kernels call (tfa_rotary.hip rotates a tensor; tfa_kvcache_append_varlen.hip and tfa_kvcache_append_varlen_ex.hip rotate K on its way into the cache,
+// the latter q in place too, and must leave the same bits), the search that finds a packed row's sequence, and the launchers' arguments.
 //   o1 = x1 * cos - x2 * sin,  o2 = x1 * sin + x2 * cos  in fp32, each output rounded once to the 16-bit type.
 // The products and sums are spelled as one fp32 multiply and one fused multiply-add per output (no contraction left to the compiler), so the bits do not
 // depend on the unit the function is inlined into; an fma rounds once where a product and a sum round twice: inside the stated bound, never outside.
@@ -159,5 +159,18 @@ struct AppendVarlenArgs {
   int interleaved, bf16, cos_f32;
 };
 hipError_t launch_kvcache_append_varlen(const AppendVarlenArgs& a, hipStream_t stream, int* grid, int* block, bool dry);
+
+// ---- tfa_kvcache_append_varlen_ex.hip: the same append into an e4m3 cache (cache strides then count bytes) and / or with q rotated in place in the launch -------
+struct AppendVarlenExArgs : AppendVarlenArgs {
+  const float* k_descale;       // fp8: device fp32 by (kd_b, kd_h) elements, or nullptr = 1.0
+  const float* v_descale;
+  long long kd_b, kd_h, vd_b, vd_h;
+  void* q;                      // (total_new, H, D) by q_h / q_n (elements), rotated in place at K's positions, or nullptr
+  long long q_h, q_n;
+  long long q_total;            // threads with q work behind the `total` K/V ones: total_new * H * q_ipr (0 without q)
+  int H, q_ipr;                 // q_ipr: work items per (row, head) — the rotated part only: rd8 / 2 pairs of chunks (halves) or rd8 chunks (interleaved)
+  int fp8;                      // 1: the caches hold e4m3 bytes
+};
+hipError_t launch_kvcache_append_varlen_ex(const AppendVarlenExArgs& a, hipStream_t stream, int* grid, int* block, bool dry);
 
 }  // namespace tfa

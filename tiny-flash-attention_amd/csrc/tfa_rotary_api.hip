@@ -1,5 +1,5 @@
 // tfa_rotary_api.hip — the C entry points of the serving step's parts around attention (include/tfa.h): tfa_rotary / tfa_rotary_plan and
-// tfa_kvcache_append_varlen / _plan.  Validation on host-known values only (nothing here reads device memory), then one launch on the caller's stream.
+// tfa_kvcache_append_varlen / _plan and tfa_kvcache_append_varlen_ex / _plan.  Validation on host-known values only (nothing here reads device memory), then one launch on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,6 +10,7 @@
 namespace {
 
 bool bad_stride(int64_t s) { return s < 0 || (s * 2) % 16 != 0; }     // 16-bit elements: every row, head and batch a whole number of 16-byte chunks on
+bool bad_stride8(int64_t s) { return s < 0 || s % 16 != 0; }          // the strides of an e4m3 cache: bytes
 
 // the tables of both entry points: (seqlen_ro, rotary_dim / 2) of cs_dtype, 16-byte aligned rows
 int check_tables(const void* cos, const void* sin, int dtype, int cs_dtype, int D, int rotary_dim, int seqlen_ro, int64_t cos_stride, int64_t sin_stride, int interleaved) {
@@ -76,8 +77,19 @@ int rotary_run(const tfa_rotary_params* p, void* stream, int* grid, int* block, 
   return (int)tfa::launch_rotary(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
 }
 
-int append_varlen_run(const tfa_kvcache_append_varlen_params* p, void* stream, int* grid, int* block, bool dry) {
+// q8 != nullptr: the caches hold e4m3 bytes — their strides count bytes, D is a multiple of 16 (tfa_fwd_kvcache_fp8's rules: the attention kernels read these caches);
+// rq != nullptr: q is rotated in place in the same launch.  Both nullptr: tfa_kvcache_append_varlen's launch.
+int append_varlen_run(const tfa_kvcache_append_varlen_params* p, const tfa_kvcache_fp8* q8, const tfa_append_q* rq, void* stream, int* grid, int* block, bool dry) {
   if (!p) return TFA_ERR_NULL;
+  if (q8) {
+    if (q8->format != TFA_KV_E4M3) return TFA_ERR_DTYPE;
+    if (q8->reserved_ != 0) return TFA_ERR_SHAPE;
+    if (p->D < 16 || p->D > 128 || (p->D % 16) != 0) return TFA_ERR_HEAD_DIM;
+    for (int i = 0; i < 2; ++i)
+      if (q8->k_descale_stride[i] < 0 || q8->v_descale_stride[i] < 0) return TFA_ERR_STRIDE;
+    if (((uintptr_t)q8->k_descale | (uintptr_t)q8->v_descale) & 3) return TFA_ERR_ALIGN;
+  }
+  if (rq && (!rq->q || !p->rotary_cos || !p->rotary_sin)) return TFA_ERR_NULL;
   if (!p->k || !p->v || !p->k_cache || !p->v_cache || !p->cu_seqlens || !p->cache_seqlens) return TFA_ERR_NULL;
   if ((p->rotary_cos == nullptr) != (p->rotary_sin == nullptr)) return TFA_ERR_NULL;
   if (p->dtype != TFA_F16 && p->dtype != TFA_BF16) return TFA_ERR_DTYPE;
@@ -90,8 +102,9 @@ int append_varlen_run(const tfa_kvcache_append_varlen_params* p, void* stream, i
   }
   for (int i = 0; i < 2; ++i)
     if (bad_stride(p->k_stride[i]) || bad_stride(p->v_stride[i])) return TFA_ERR_STRIDE;
-  for (int i = 0; i < 3; ++i)
-    if (bad_stride(p->kc_stride[i]) || bad_stride(p->vc_stride[i])) return TFA_ERR_STRIDE;
+  for (int i = 0; i < 3; ++i) {
+    if (q8 ? bad_stride8(p->kc_stride[i]) || bad_stride8(p->vc_stride[i]) : bad_stride(p->kc_stride[i]) || bad_stride(p->vc_stride[i])) return TFA_ERR_STRIDE;
+  }
   if (p->k_stride[1] < p->D || p->v_stride[1] < p->D || p->kc_stride[2] < p->D || p->vc_stride[2] < p->D) return TFA_ERR_STRIDE;
   if (p->rotary_cos) {
     const int tb = check_tables(p->rotary_cos, p->rotary_sin, p->dtype, p->cs_dtype, p->D, p->rotary_dim, p->seqlen_ro, p->cos_stride, p->sin_stride,
@@ -100,8 +113,13 @@ int append_varlen_run(const tfa_kvcache_append_varlen_params* p, void* stream, i
   }
   if (((uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->k_cache | (uintptr_t)p->v_cache) & 15) return TFA_ERR_ALIGN;
   if (((uintptr_t)p->cu_seqlens | (uintptr_t)p->cache_seqlens | (uintptr_t)p->block_table) & 3) return TFA_ERR_ALIGN;
+  if (rq) {
+    if (rq->H <= 0 || rq->reserved_ != 0) return TFA_ERR_SHAPE;
+    if (bad_stride(rq->q_stride[0]) || bad_stride(rq->q_stride[1]) || rq->q_stride[1] < p->D) return TFA_ERR_STRIDE;
+    if ((uintptr_t)rq->q & 15) return TFA_ERR_ALIGN;
+  }
 
-  tfa::AppendVarlenArgs a;
+  tfa::AppendVarlenExArgs a;
   memset(&a, 0, sizeof(a));
   a.k = p->k; a.v = p->v; a.k_cache = p->k_cache; a.v_cache = p->v_cache;
   a.cu = p->cu_seqlens; a.seqlens = p->cache_seqlens; a.block_table = p->block_table;
@@ -125,7 +143,21 @@ int append_varlen_run(const tfa_kvcache_append_varlen_params* p, void* stream, i
   }
   a.bf16 = p->dtype == TFA_BF16 ? 1 : 0;
   if ((a.total + 255) / 256 >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
-  return (int)tfa::launch_kvcache_append_varlen(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
+  if (!q8 && !rq) return (int)tfa::launch_kvcache_append_varlen(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
+  if (q8) {
+    a.fp8 = 1;
+    a.k_descale = q8->k_descale; a.v_descale = q8->v_descale;
+    a.kd_b = q8->k_descale_stride[0]; a.kd_h = q8->k_descale_stride[1];
+    a.vd_b = q8->v_descale_stride[0]; a.vd_h = q8->v_descale_stride[1];
+  }
+  if (rq) {
+    a.q = rq->q; a.H = rq->H;
+    a.q_h = rq->q_stride[0]; a.q_n = rq->q_stride[1];
+    a.q_ipr = p->rotary_interleaved ? a.rd8 : a.rd8 / 2;
+    a.q_total = (long long)p->total_new * rq->H * a.q_ipr;
+  }
+  if ((a.total + a.q_total + 255) / 256 >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  return (int)tfa::launch_kvcache_append_varlen_ex(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
 }
 
 }  // namespace
@@ -135,7 +167,16 @@ extern "C" {
 int tfa_rotary(const tfa_rotary_params* p, void* stream) { return rotary_run(p, stream, nullptr, nullptr, false); }
 int tfa_rotary_plan(const tfa_rotary_params* p, int* grid, int* block) { return rotary_run(p, nullptr, grid, block, true); }
 
-int tfa_kvcache_append_varlen(const tfa_kvcache_append_varlen_params* p, void* stream) { return append_varlen_run(p, stream, nullptr, nullptr, false); }
-int tfa_kvcache_append_varlen_plan(const tfa_kvcache_append_varlen_params* p, int* grid, int* block) { return append_varlen_run(p, nullptr, grid, block, true); }
+int tfa_kvcache_append_varlen(const tfa_kvcache_append_varlen_params* p, void* stream) { return append_varlen_run(p, nullptr, nullptr, stream, nullptr, nullptr, false); }
+int tfa_kvcache_append_varlen_plan(const tfa_kvcache_append_varlen_params* p, int* grid, int* block) {
+  return append_varlen_run(p, nullptr, nullptr, nullptr, grid, block, true);
+}
+
+int tfa_kvcache_append_varlen_ex(const tfa_kvcache_append_varlen_params* p, const tfa_kvcache_fp8* q8, const tfa_append_q* rq, void* stream) {
+  return append_varlen_run(p, q8, rq, stream, nullptr, nullptr, false);
+}
+int tfa_kvcache_append_varlen_ex_plan(const tfa_kvcache_append_varlen_params* p, const tfa_kvcache_fp8* q8, const tfa_append_q* rq, int* grid, int* block) {
+  return append_varlen_run(p, q8, rq, nullptr, grid, block, true);
+}
 
 }  // extern "C"

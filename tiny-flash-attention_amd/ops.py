@@ -1413,7 +1413,8 @@ def _append_varlen_params(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, blo
     return p
 
 
-def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table=None, *, rotary_cos=None, rotary_sin=None, rotary_interleaved=False):
+def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table=None, *, rotary_cos=None, rotary_sin=None, rotary_interleaved=False,
+                          q=None, k_descale=None, v_descale=None):
     """A unified batch's new K/V rows into a paged or contiguous cache (tfa_kvcache_append_varlen) — the append ``flash_attn_varlen_func(..., block_table=)`` needs.
 
     ``k`` / ``v`` (total_new, Hk, D) packed, of the caches' 16-bit dtype, any strides with unit stride along D; ``cu_seqlens`` (B + 1,) and ``cache_seqlens`` (B,)
@@ -1422,17 +1423,43 @@ def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, blo
     below 0 or at / beyond the capacity, a row whose block-table entry is not a page of the pool, a packed row outside every sequence; nothing is stored outside
     the caches.  ``cache_seqlens`` is not advanced.  Nothing is read on the host: no synchronisation, capturable in a graph.
     ``rotary_cos`` / ``rotary_sin``: K is rotated at its key position on the way in (V is copied) — the bits ``apply_rotary_emb(k, cos, sin, cu_seqlens=cu_seqlens,
-    seqlen_offsets=cache_seqlens)`` followed by the plain append leaves; the query side is ``apply_rotary_emb(q, ..., cu_seqlens=cu_q, seqlen_offsets=cache_seqlens)``.
-    Not differentiable; fp8 caches are not served (the paged varlen attention reads 16-bit pools)."""
+    seqlen_offsets=cache_seqlens)`` followed by the plain append leaves; the query side is ``q=`` below, or ``apply_rotary_emb(q, ..., cu_seqlens=cu_q,
+    seqlen_offsets=cache_seqlens)``.
+    ``q`` (needs the tables; tfa_kvcache_append_varlen_ex): packed (total_new, H, D) of k's dtype, any row and head strides with unit stride along D and 16-byte
+    aligned rows — ``qkv[:, :H]`` of a packed projection works — rotated IN PLACE in the same launch at the positions K is rotated at, row t of sequence b at
+    ``cache_seqlens[b] + t``: the bits ``apply_rotary_emb(q, cos, sin, interleaved, inplace=True, seqlen_offsets=cache_seqlens, cu_seqlens=cu_seqlens)`` leaves.
+    Untouched bit for bit: elements behind rotary_dim, rows outside every sequence, rows whose position lies outside [0, seqlen_ro).  q has no capacity: a row
+    whose K is dropped still has its q rotated.  No relation between H and Hk is needed.  Precondition: q must not overlap k, v or the caches.
+    fp8 caches (tfa_kvcache_append_varlen_ex): ``k_cache`` / ``v_cache`` of dtype ``torch.float8_e4m3fn`` (paged or contiguous, strides multiples of 16 bytes, D a
+    multiple of 16) with ``k_descale`` / ``v_descale``, float32 device tensors of shape (B, Hk) with any strides, indexed by the sequence (not the page) and
+    read on the device only.  Both are required — ``None`` does not mean 1.0 here; unit scales are ``torch.ones(1, 1, device=...).expand(B, Hk)``.  k / v stay
+    16-bit; stored byte = ``rne_e4m3fn(clamp(float(x) / descale[b, hk], -448, 448))``, a true fp32 division, NaN stays NaN — the 4-D fp8 append's bytes; with
+    tables K is rotated and rounded once to its 16-bit dtype first, then quantised.  Positions, page lookup and drop rules are the 16-bit append's.
+    Without ``q`` and descales the call is tfa_kvcache_append_varlen's.  Not differentiable."""
     name = "kvcache_append_varlen"
     for n, t in (("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens", cu_seqlens), ("cache_seqlens", cache_seqlens)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name}: {n} must be a tensor (got {type(t).__name__})")
     if k.dtype not in _DT:
         raise TypeError(f"{name}: float16 or bfloat16 only (got {k.dtype} for k)")
-    for n, t in (("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dtype != k.dtype:
-            raise TypeError(f"{name}: {n} must have k's dtype {k.dtype} (got {t.dtype}; fp8 caches are not served by the packed append)")
+    if v.dtype != k.dtype:
+        raise TypeError(f"{name}: v must have k's dtype {k.dtype} (got {v.dtype})")
+    fp8s = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+    fp8 = k_cache.dtype in fp8s or v_cache.dtype in fp8s
+    if fp8:
+        if k_cache.dtype != v_cache.dtype:
+            raise TypeError(f"{name}: k_cache and v_cache must share one dtype (got {k_cache.dtype}, {v_cache.dtype})")
+        if k_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{name}: fp8 caches must be torch.float8_e4m3fn (got {k_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
+        if k_descale is None or v_descale is None:
+            raise TypeError(f"{name}: fp8 caches are not served without k_descale / v_descale (both are required; unit scales are "
+                            f"torch.ones(1, 1, device=...).expand(B, Hk))")
+    else:
+        for n, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if t.dtype != k.dtype:
+                raise TypeError(f"{name}: {n} must have k's dtype {k.dtype}, or both caches be torch.float8_e4m3fn with k_descale / v_descale (got {t.dtype})")
+        if k_descale is not None or v_descale is not None:
+            raise TypeError(f"{name}: k_descale / v_descale belong to torch.float8_e4m3fn caches (got {k_cache.dtype} caches)")
     for n, t in (("k", k), ("v", v)):
         if t.dim() != 3:
             raise ValueError(f"{name}: {n} must be 3-D (total_new, Hk, D) (got {tuple(t.shape)})")
@@ -1447,10 +1474,12 @@ def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, blo
         raise ValueError(f"{name}: k and v must have one non-empty shape (got {tuple(k.shape)}, {tuple(v.shape)})")
     if D % 8 != 0 or D < 8 or D > 128:
         raise ValueError(f"{name}: the head dim must be a multiple of 8 up to 128 (got {D})")
+    if fp8 and D % 16 != 0:
+        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
     if k_cache.shape != v_cache.shape or k_cache.shape[2] != Hk or k_cache.shape[3] != D:
         raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., {Hk}, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
     for n, t in (("k", k), ("v", v), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(-1) != 1 or any(s % 8 != 0 for s in t.stride()[:-1]) or t.device != k.device:
+        if t.stride(-1) != 1 or any((s * t.element_size()) % 16 != 0 for s in t.stride()[:-1]) or t.device != k.device:
             raise ValueError(f"{name}: {n} must be on k's device with unit stride along the head dim and 16-byte aligned rows (got strides {t.stride()})")
     if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.shape[0] < 2 or not cu_seqlens.is_contiguous() or cu_seqlens.device != k.device:
         raise ValueError(f"{name}: cu_seqlens must be a contiguous int32 tensor of B + 1 entries on k's device")
@@ -1476,10 +1505,47 @@ def kvcache_append_varlen(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, blo
         raise ValueError(f"{name}: rotary_cos and rotary_sin must be given together")
     if rotary_cos is not None:
         rotary_cos, rotary_sin, rotary_dim, seqlen_ro = _rotary_tables(name, rotary_cos, rotary_sin, k.dtype, D, k.device, "rotary_cos", "rotary_sin")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (k, v, k_cache, v_cache)):
+    if fp8:
+        for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError(f"{name}: {n} must be a float32 tensor")
+            if tuple(t.shape) != (B, Hk) or t.device != k.device:
+                raise TypeError(f"{name}: {n} must have shape ({B}, {Hk}) — B = cu_seqlens.numel() - 1 — on k's device (got {tuple(t.shape)} on {t.device})")
+    if q is not None:
+        if not isinstance(q, torch.Tensor):
+            raise TypeError(f"{name}: q must be a tensor (got {type(q).__name__})")
+        if q.dtype != k.dtype:
+            raise TypeError(f"{name}: q must have k's dtype {k.dtype} (got {q.dtype})")
+        if rotary_cos is None:
+            raise ValueError(f"{name}: q is rotated by rotary_cos / rotary_sin and needs them")
+        if q.dim() != 3 or q.shape[0] != total or q.shape[1] < 1 or q.shape[2] != D:
+            raise ValueError(f"{name}: q must be 3-D ({total}, H, {D}) — k's rows and head dim (got {tuple(q.shape)})")
+        if q.device != k.device:
+            raise ValueError(f"{name}: q must be on k's device (got {q.device})")
+        if q.stride(2) != 1 or any(s % 8 != 0 for s in q.stride()[:2]):
+            raise ValueError(f"{name}: q must have unit stride along the head dim and 16-byte aligned rows (strides multiples of 8 elements; got {q.stride()})")
+        if q.data_ptr() % 16 != 0:
+            raise ValueError(f"{name}: q must start at a 16-byte aligned address")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (k, v, k_cache, v_cache) + ((q,) if q is not None else ())):
         raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
 
     p = _append_varlen_params(k, v, k_cache, v_cache, cu_seqlens, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved)
+    if not fp8 and q is None:
+        with torch.cuda.device(k.device):
+            _lib.check(_lib.lib().tfa_kvcache_append_varlen(C.byref(p), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return None
+    p8 = rq = None
+    if fp8:
+        p8 = _lib.TfaKvcacheFp8()
+        p8.format = _lib.TFA_KV_E4M3
+        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
+            setattr(p8, ptr, t.data_ptr())
+            strides[0], strides[1] = t.stride(0), t.stride(1)
+    if q is not None:
+        rq = _lib.TfaAppendQ()
+        rq.q, rq.H = q.data_ptr(), q.shape[1]
+        rq.q_stride[0], rq.q_stride[1] = q.stride(1), q.stride(0)               # (total, H, D): head, row
     with torch.cuda.device(k.device):
-        _lib.check(_lib.lib().tfa_kvcache_append_varlen(C.byref(p), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().tfa_kvcache_append_varlen_ex(C.byref(p), C.byref(p8) if fp8 else None, C.byref(rq) if rq is not None else None,
+                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return None

@@ -5,8 +5,12 @@ are read and written once) plus the table rows; append = read of k / v plus writ
   rotary:  q + k at 4 x 4096, H32 / Hk8, D128 = rotary_dim, bf16, both layouts, in place and out of place (one launch for both tensors)
   append:  the "56 short + 4 long" prefill mix of tools/bench_varlen.py (Hk8, D128, bf16) into 256-key pages through a shuffled table, with and without fused RoPE
   decode:  B = 64, one row per sequence — rotary of q + k, and the packed append of 64 rows (launch-latency bound)
-Expectation before measuring: the large shapes are bound by HBM bytes, the decode shapes by launch latency.
-usage: python tools/bench_rotary_append.py [--iters 10] [--rounds 3] [--out profiles/rotary_append_bench.txt]"""
+  ex:      tfa_kvcache_append_varlen_ex at the same two append shapes — the append into an e4m3 pool, plain and with fused RoPE, alternated with the 16-bit
+           append of the same rows; and the append with q rotated in its launch (16-bit pool, H32 q), alternated with what the step needs without it:
+           tfa_kvcache_append_varlen with tables plus tfa_rotary on q in place (two launches)
+Expectation before measuring: the large shapes are bound by HBM bytes, the decode shapes by launch latency; the fp8 append moves three quarters of the 16-bit
+append's bytes; the fused-q call saves about one launch at decode shapes.
+usage: python tools/bench_rotary_append.py [--iters 10] [--rounds 3] [--out profiles/rotary_append_bench.txt] [--ex-out profiles/append_varlen_ex_bench.txt] [--only-ex]"""
 import argparse
 import ctypes as C
 import math
@@ -41,15 +45,19 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ex-out", default=None, help="file for the tfa_kvcache_append_varlen_ex rows")
+    ap.add_argument("--only-ex", action="store_true", help="skip the rotary and plain-append rows")
     a = ap.parse_args()
     L = _lib.lib()
     dev = torch.device("cuda:0")
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     lines = []
 
-    def emit(s):
+    ex_lines = []
+
+    def emit(s, to=None):
         print(s, flush=True)
-        lines.append(s)
+        (lines if to is None else to).append(s)
 
     def race(tfa_call, torch_call):
         best = [math.inf, math.inf]
@@ -68,7 +76,7 @@ def main():
         emit(f"  {label:<58} | {t[0]:8.4f} {nbytes / (t[0] * 1e-3) / 1e9:7.0f} | {t[1]:8.4f} {nbytes / (t[1] * 1e-3) / 1e9:7.0f} | {t[1] / t[0]:11.2f}")
 
     # ---- rotary of q and k ---------------------------------------------------------------------------------------------------------------
-    for label, B, N in (("prefill 4 x 4096", 4, 4096), ("decode B = 64, one row", 64, 1)):
+    for label, B, N in (() if a.only_ex else (("prefill 4 x 4096", 4, 4096), ("decode B = 64, one row", 64, 1))):
         q = torch.empty((B, N, H, D), dtype=DT, device=dev).normal_(0, 1.0)
         k = torch.empty((B, N, HK, D), dtype=DT, device=dev).normal_(0, 0.5)
         qo, ko = torch.empty_like(q), torch.empty_like(k)
@@ -89,6 +97,15 @@ def main():
                 t = race(lambda: _lib.check(L.tfa_rotary(C.byref(p), stream)), torch_call)
                 row(f"rotary q + k, {label}, {'GPT-J' if interleaved else 'GPT-NeoX'}, {'in place' if inplace else 'out of place'}", nbytes, t)
         del q, k, qo, ko
+
+    emit(f"# tfa_kvcache_append_varlen_ex, H{H} Hk{HK} D{D} rotary_dim {D} bf16 rows, page {PAGE}; HIP events, best of {a.rounds} rounds x {a.iters} calls, "
+         "the two arms alternated in one process", ex_lines)
+    emit("# fp8: the append into an e4m3 pool against the 16-bit append of the same rows; q=: the append with q rotated in its launch against "
+         "tfa_kvcache_append_varlen with tables + tfa_rotary on q in place; GB/s over the bytes the arm must move", ex_lines)
+    emit(f"# {'shape':<66} | {'ex ms':>8} {'GB/s':>7} | {'other ms':>8} {'GB/s':>7} | {'other / ex':>10}", ex_lines)
+
+    def ex_row(label, nbytes, t):
+        emit(f"  {label:<66} | {t[0]:8.4f} {nbytes[0] / (t[0] * 1e-3) / 1e9:7.0f} | {t[1]:8.4f} {nbytes[1] / (t[1] * 1e-3) / 1e9:7.0f} | {t[1] / t[0]:10.2f}", ex_lines)
 
     # ---- the packed append ---------------------------------------------------------------------------------------------------------------
     for label, new in (("prefill mix 56 short + 4 long", mix_lengths("prefill")), ("decode B = 64, one row", [1] * 64)):
@@ -116,7 +133,39 @@ def main():
                 pos.append(pp)
         idx = (torch.tensor(pages, device=dev), torch.tensor(rows, device=dev))
         posd = torch.tensor(pos, device=dev)
+        # ---- tfa_kvcache_append_varlen_ex: the e4m3 pool, and q rotated in the launch
+        kp8 = torch.zeros((nb, PAGE, HK, D), dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+        vp8 = torch.zeros((nb, PAGE, HK, D), dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+        kd = torch.empty((B, HK), dtype=torch.float32, device=dev).uniform_(0.006, 0.012)
+        vd = torch.empty((B, HK), dtype=torch.float32, device=dev).uniform_(0.006, 0.012)
+        p8 = _lib.TfaKvcacheFp8()
+        p8.format, p8.k_descale, p8.v_descale = _lib.TFA_KV_E4M3, kd.data_ptr(), vd.data_ptr()
+        p8.k_descale_stride[0], p8.k_descale_stride[1], p8.v_descale_stride[0], p8.v_descale_stride[1] = HK, 1, HK, 1
+        rows16 = 2.0 * (k.numel() + v.numel())                                   # bytes of the 16-bit rows, read once
+        tab = 2.0 * total * (D // 2) * 2
         for fused in (False, True):
+            pe = ops._append_varlen_params(k, v, kp8, vp8, cud, lens, btd, cos if fused else None, sin if fused else None, False)
+            po = ops._append_varlen_params(k, v, kp, vp, cud, lens, btd, cos if fused else None, sin if fused else None, False)
+            t = race(lambda: _lib.check(L.tfa_kvcache_append_varlen_ex(C.byref(pe), C.byref(p8), None, stream)),
+                     lambda: _lib.check(L.tfa_kvcache_append_varlen(C.byref(po), stream)))
+            ex_row(f"fp8 append vs 16-bit append, {label} ({total} rows){', fused RoPE' if fused else ''}",
+                   (1.5 * rows16 + (tab if fused else 0.0), 2.0 * rows16 + (tab if fused else 0.0)), t)
+        q = torch.empty((total, H, D), dtype=DT, device=dev).normal_(0, 1.0)
+        pq = ops._append_varlen_params(k, v, kp, vp, cud, lens, btd, cos, sin, False)
+        rq = _lib.TfaAppendQ()
+        rq.q, rq.H = q.data_ptr(), H
+        rq.q_stride[0], rq.q_stride[1] = q.stride(1), q.stride(0)
+        pr, keep = ops._rotary_params("bench", (q,), (q,), cos, sin, False, False, lens, cud)
+
+        def two_launches():
+            _lib.check(L.tfa_kvcache_append_varlen(C.byref(pq), stream))
+            _lib.check(L.tfa_rotary(C.byref(pr), stream))
+
+        t = race(lambda: _lib.check(L.tfa_kvcache_append_varlen_ex(C.byref(pq), None, C.byref(rq), stream)), two_launches)
+        nb_q = 2.0 * rows16 + 2.0 * q.numel() * 2 + tab
+        ex_row(f"append with q= vs append + tfa_rotary(q), {label} ({total} rows)", (nb_q, nb_q + tab), t)
+        del q, kp8, vp8
+        for fused in (() if a.only_ex else (False, True)):
             p = ops._append_varlen_params(k, v, kp, vp, cud, lens, btd, cos if fused else None, sin if fused else None, False)
 
             def torch_call():
@@ -130,6 +179,9 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+    if a.ex_out:
+        with open(a.ex_out, "w") as f:
+            f.write("\n".join(ex_lines) + "\n")
 
 
 if __name__ == "__main__":
