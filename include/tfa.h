@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define TFA_VERSION 111 /* 0.1.11 (still): + the packed append into an e4m3 cache and / or with q rotated in place in the same launch — tfa_kvcache_append_varlen_ex / _plan (struct tfa_append_q; tfa_kvcache_fp8 as in tfa_fwd_kvcache_fp8); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + packed ragged query rows over a K/V cache — tfa_fwd_kvcache_varlen and its _workspace / _plan / _suggest_splits companions (struct tfa_kvcache_varlen_q: cu_seqlens_q in device memory, max_seqlen_q, total_q; q packed (total_q, H, D), every sequence's rows read and clamped on the device: the varlen-q form of the KV-cache kernel, packed GQA rows by default); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
+#define TFA_VERSION 111 /* 0.1.11 (still): + a device-built work list for the packed-q K/V-cache call — tfa_kvcache_varlen_schedule / _schedule_size / _schedule_plan build it from cu_seqlens_q in one launch, tfa_fwd_kvcache_varlen_sched / _sched_plan run heads * bound work items from it instead of B * heads * ceil(max_seqlen_q * G' / 128) (FlashAttention-3's get_scheduler_metadata / scheduler_metadata=; the scheduled form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the packed append into an e4m3 cache and / or with q rotated in place in the same launch — tfa_kvcache_append_varlen_ex / _plan (struct tfa_append_q; tfa_kvcache_fp8 as in tfa_fwd_kvcache_fp8); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + packed ragged query rows over a K/V cache — tfa_fwd_kvcache_varlen and its _workspace / _plan / _suggest_splits companions (struct tfa_kvcache_varlen_q: cu_seqlens_q in device memory, max_seqlen_q, total_q; q packed (total_q, H, D), every sequence's rows read and clamped on the device: the varlen-q form of the KV-cache kernel, packed GQA rows by default); new struct, entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the GQA packing of the K/V-cache calls chosen by the caller — tfa_fwd_kvcache_pack and its _workspace / _plan / _suggest_splits companions (TFA_PACK_GQA_AUTO / ON / OFF; ON packs the query heads of a K/V head as position-major rows at any Nq: the packed form of the KV-cache kernel); new entry points and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + the serving step's parts around attention — tfa_rotary / tfa_rotary_plan (rotary embedding at device-side positions, one or two tensors a launch) and tfa_kvcache_append_varlen / _plan (packed new K/V rows into a paged or contiguous cache, K optionally rotated on the way in); new structs and kernels only: every existing entry point, struct, kernel and result bit unchanged.  0.1.11 (still): + a dense additive bias / mask — tfa_fwd_bias / tfa_bwd_bias and their _plan / _variant / _rounding_rule companions (struct tfa_attn_bias: a (B|1, H|1, Nq, Nk) tensor of q's dtype or fp32 in device memory, read by the kernels inside the tile loop; a third form of the fixed-length local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + attention over a K/V cache — tfa_fwd_kvcache, its _workspace / _plan / _suggest_splits companions and tfa_kvcache_append (device-side cache_seqlens, paged K/V through a block table, in-place append; the KV-cache form of the LDS-DMA kernel); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + soft-capping — tfa_fwd_softcap / tfa_bwd_softcap, their varlen forms and _plan / _variant / _rounding_rule companions (softcap: a host float, tanh capping of the scaled scores in front of the ALiBi bias and the mask; slopes optional; a second form of the local kernels on the ALiBi hook); every existing entry point, kernel and result bit unchanged.  0.1.11 (still): + ALiBi — tfa_fwd_alibi / tfa_bwd_alibi, their varlen forms and _plan / _variant / _rounding_rule companions (alibi_slopes in device memory, a form of the local kernels); every existing entry point, kernel and result bit unchanged.  0.1.11: tfa_bwd at head dims up to 128 runs hand-scheduled tile loops in both launches; the dQ launch accumulates dP from -delta (gradient bits differ from 0.1.10, inside the same bounds); no interface change.  0.1.10: bf16 on the default kernels rounds P against the first key tile's row maximum (max-free tile loop; tfa_fwd_rounding_rule says which rule a call runs), the tile bodies behind the hand-scheduled loop are generated too, tfa_debug_mfma_ceiling returns TFA_ERR_SHAPE for bad sizes; 0.1.9: (b,h) slices of 2 GiB and more at head dims above 128 (windowed instantiations of the 256-wide forward and backward kernels; TFA_ERR_STRIDE before), tfa_debug_mfma_ceiling; 0.1.8: TFA_FWD_EXACT_MAX runs the il8 kernel's exact-max instantiation (variant 38) on grids that fill the chip; 0.1.7: tfa_bwd computes delta inside its dQ launch (tfa_debug_bwd_split bit 3 restores the separate launch), tfa_debug_set_trace is served by traced twins of the main kernels; 0.1.6: + fp32 q,k,v (TFA_F32 input: the correctness path behind the reference's fp32 fixtures), variant numbers are ids (tfa_variant_available), tfa_bwd_workspace_bytes is 0 wherever the workspace would be ignored; 0.1.5: + tfa_fwd_params::flags (TFA_FWD_EXACT_MAX), split-KV for head dims up to 256; 0.1.4: + tfa_fwd_suggest_splits, key-split kernels for small grids, split-KV / backward head dims multiples of 8; 0.1.3: forward head dims = every multiple of 8 up to 256; tfa_debug_set_flags; 0.1.2: + tfa_variant_available; debug knobs are per thread; 0.1.1: split-KV, tfa_merge, tfa_bwd */
 
 /* element types */
 enum tfa_dtype { TFA_F16 = 0, TFA_BF16 = 1,
@@ -813,8 +813,8 @@ int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gq
  * unpacked (KvcPacked serves G = 2..128; MHA is why the unpacked varlen-q instantiations exist).  A scheduling choice: it never changes the result's definition.
  * Geometry: work item = (sequence, K/V head or head, query block, chunk); the launch carries nmb = ceil(max_seqlen_q * G' / 128) blocks per (sequence, head), G' = G
  * packed, 1 unpacked; causal blocks pair heavy / light on that launch-level index; _plan's grid = B * heads * work items * chunks.  A block with no row of its sequence
- * issues no Q, K or V request and no store.  KNOWN COST: the grid is sized by max_seqlen_q — one 2048-row prefill chunk in a batch of decode rows makes most work
- * items empty, each costing its scalar loads and an exit.
+ * issues no Q, K or V request and no store.  The grid is sized by max_seqlen_q — one 2048-row prefill chunk in a batch of decode rows makes most work items empty,
+ * each costing its scalar loads and an exit: tfa_fwd_kvcache_varlen_sched below runs the same blocks from a device-built work list that holds the non-empty items only.
  * _workspace: 0 for one chunk, else chunks * H * total_q * (D + 1) floats.  _suggest_splits: tfa_fwd_kvcache_pack_suggest_splits' rule with the workgroups counted as
  * heads * min(B * nmb, ceil(total_q * G' / 128) + B) — the second term bounds the non-empty blocks from what the host knows.
  * Refused, nothing launched: a NULL vq or cu_seqlens_q (TFA_ERR_NULL); max_seqlen_q <= 0, total_q <= 0, a nonzero reserved field (TFA_ERR_SHAPE); a cu_seqlens_q that
@@ -830,6 +830,40 @@ int tfa_fwd_kvcache_varlen(const tfa_kvcache_params* p, const tfa_kvcache_varlen
 long long tfa_fwd_kvcache_varlen_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits);
 int tfa_fwd_kvcache_varlen_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
 int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa);
+
+/* ---- the SCHEDULED form of the packed-q call (FlashAttention-3's get_scheduler_metadata(...) / scheduler_metadata=, the interface this mirrors) -----------------------
+ * tfa_fwd_kvcache_varlen launches B * heads * ceil(max_seqlen_q * G' / 128) query blocks per chunk whatever the row counts are.  Here a serving step builds a work list
+ * once — tfa_kvcache_varlen_schedule: ONE launch of one workgroup on `stream`, nothing read on the host, nothing allocated — and every layer's attention call
+ * (tfa_fwd_kvcache_varlen_sched) launches heads * bound * chunks workgroups that take their (sequence, item) from it.  Both launches capture into a graph; a replay
+ * follows in-place updates of cu_seqlens_q and cache_seqlens as long as B, max_seqlen_q, total_q, the packing and is_causal stay what the list was sized for.
+ * metadata: int32 in device memory, 8-byte aligned, tfa_kvcache_varlen_schedule_size elements = 8 + 2 * bound:
+ *   [0..8)       header: n_items, B, G', causal, max_seqlen_q, total_q, bound, 0          (n_items is read by the kernel; the rest is for debugging and tests)
+ *   [8 + 2 i ..) item i: (b, wi), i < n_items — ascending b, then ascending wi; a sequence without rows contributes nothing.  (Longest-first is not done.)
+ *   (q0_b, nq_b) are clamped as tfa_fwd_kvcache_varlen's work items clamp them; nb_b = ceil(nq_b * G' / 128) blocks.  Not causal: nb_b items, wi = the block.  Causal:
+ *   ceil(nb_b / 2) items, wi = the heavy / light pair of blocks (nb_b - 1 - wi, wi) of the SEQUENCE's own count (the middle block alone when nb_b is odd).
+ * bound, the item rows the buffer holds and the per-head grid, is what the host knows: with nmb = ceil(max_seqlen_q * G' / 128) and F = ceil(total_q * G' / 128),
+ *   not causal:  min(B * nmb, F + B)                        — a sequence of n rows fills at most n * G' / 128 + 1 blocks, and the rows sum to at most total_q;
+ *   causal:      min(B * ceil(nmb / 2), floor((F + 2 B) / 2)) — ceil(nb / 2) <= (nb + 1) / 2 for every sequence, summed over the blocks bounded above.
+ *   A cu_seqlens_q that is not monotonic can describe more items; the list then ends at `bound` (n_items is clamped, nothing is written behind the buffer) and the
+ *   rows of the dropped items are not written.
+ * The list is a hint to the attention kernel, never trusted: n_items is clamped into [0, bound], b into [0, B), nq_b and nb_b are recomputed from cu_seqlens_q, a wi
+ * outside the sequence's own items is an empty item.  Stale, foreign or random metadata gives unspecified or unwritten rows; nothing outside the tensors is read or
+ * written — the guarantee the call gives for cu_seqlens_q, cache_seqlens and block_table.  With the list of this batch, out and lse equal tfa_fwd_kvcache_varlen's bit
+ * for bit: a block's arithmetic does not depend on the work item that runs it.
+ * tfa_kvcache_varlen_schedule* read of *p only B, H, Hk; is_causal is their own argument (the attention call takes p->is_causal: the two must agree).  pack_gqa as above.
+ *   _schedule_size: the int32 elements, or a negative tfa_status.  _schedule_plan: grid 1, block 256, the scan's LDS bytes; validates without a GPU.
+ *   Refused, nothing launched: NULL p / vq / cu_seqlens_q / metadata (TFA_ERR_NULL); B, H, Hk <= 0, H % Hk != 0, a bad pack_gqa, max_seqlen_q <= 0, total_q <= 0, a nonzero
+ *   reserved field (TFA_ERR_SHAPE); cu_seqlens_q not 4-byte or metadata not 8-byte aligned (TFA_ERR_ALIGN).
+ * tfa_fwd_kvcache_varlen_sched: tfa_fwd_kvcache_varlen with the list; _workspace and _suggest_splits are tfa_fwd_kvcache_varlen's, unchanged.  _sched_plan's grid =
+ *   heads * bound * chunks.  Refused: a NULL metadata (TFA_ERR_NULL), one not 8-byte aligned (TFA_ERR_ALIGN), everything tfa_fwd_kvcache_varlen_plan refuses, and a
+ *   packing that tfa_fwd_kvcache_varlen would silently drop (a head group's rows beyond one descriptor: TFA_ERR_STRIDE — the list was sized for the packing named).
+ * Kernels: csrc/tfa_kvcache_schedule.hip; csrc/tfa_fwd_kernel_dma.h (KvcSched, behind KvcVarlenQ) — instantiations and units of their own, so every other kernel
+ * keeps its instructions (profiles/kvcache_sched_isa_unchanged.txt). */
+long long tfa_kvcache_varlen_schedule_size(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal);
+int tfa_kvcache_varlen_schedule(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal, int32_t* metadata, void* stream);
+int tfa_kvcache_varlen_schedule_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_kvcache_varlen_sched(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int splits, const int32_t* metadata, float* workspace, void* stream);
+int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
 
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the

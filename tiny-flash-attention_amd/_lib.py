@@ -107,6 +107,11 @@ SYMBOLS = (
     "tfa_fwd_kvcache_varlen_workspace",
     "tfa_fwd_kvcache_varlen_plan",
     "tfa_fwd_kvcache_varlen_suggest_splits",
+    "tfa_kvcache_varlen_schedule_size",
+    "tfa_kvcache_varlen_schedule",
+    "tfa_kvcache_varlen_schedule_plan",
+    "tfa_fwd_kvcache_varlen_sched",
+    "tfa_fwd_kvcache_varlen_sched_plan",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -599,6 +604,17 @@ def lib():
     L.tfa_fwd_kvcache_varlen_plan.argtypes = [PK, PV, P8, C.c_int, C.c_int, IP, IP, IP]
     L.tfa_fwd_kvcache_varlen_suggest_splits.restype = C.c_int
     L.tfa_fwd_kvcache_varlen_suggest_splits.argtypes = [PK, PV, C.c_int]
+    # ... and its scheduled form: the work list built on the device (metadata: int32 in device memory), then the attention call that runs from it
+    L.tfa_kvcache_varlen_schedule_size.restype = C.c_longlong
+    L.tfa_kvcache_varlen_schedule_size.argtypes = [PK, PV, C.c_int, C.c_int]
+    L.tfa_kvcache_varlen_schedule.restype = C.c_int
+    L.tfa_kvcache_varlen_schedule.argtypes = [PK, PV, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.tfa_kvcache_varlen_schedule_plan.restype = C.c_int
+    L.tfa_kvcache_varlen_schedule_plan.argtypes = [PK, PV, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_varlen_sched.restype = C.c_int
+    L.tfa_fwd_kvcache_varlen_sched.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_varlen_sched_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_varlen_sched_plan.argtypes = [PK, PV, P8, C.c_int, C.c_int, IP, IP, IP]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

@@ -979,9 +979,27 @@ static void kvcache_vq_blocks(int max_q, int gp, bool causal, long long* nmb, lo
   *nwork = (causal && tfa::pairs_causal(tfa::kSplitVariant)) ? (*nmb + 1) / 2 : *nmb;
 }
 
+// the scheduled form's host-known upper bound of the batch's work items per head (= the item rows of the metadata and the `nwork` of its launch).  A sequence of n rows
+// fills nb = ceil(n * G' / 128) <= n * G' / 128 + 1 blocks and never more than nmb, so with sum n <= total_q (a monotonic cu_seqlens_q) the blocks number at most
+// S = min(B * nmb, ceil(total_q * G' / 128) + B): the non-causal bound.  Causal items are pairs, ceil(nb / 2) <= (nb + 1) / 2 each, so they number at most
+// min(B * ceil(nmb / 2), floor((ceil(total_q * G' / 128) + 2 B) / 2)).  (tests/test_kvcache_sched_abi.py enumerates small batches against both.)
+static long long kvcache_sched_bound(int B, int max_q, int total_q, int gp, bool causal) {
+  long long nmb, nwork;
+  kvcache_vq_blocks(max_q, gp, causal, &nmb, &nwork);
+  const long long filled = ((long long)total_q * gp + 127) / 128;
+  const long long launched = (long long)B * nwork, rows = nwork < nmb ? (filled + 2ll * B) / 2 : filled + B;
+  return launched < rows ? launched : rows;
+}
+static_assert(tfa::SCHED_HDR == tfa::SCHEDULE_HDR, "one header size for the kernel that writes the list and the one that reads it");
+
+// sched: the scheduled form (tfa_fwd_kvcache_varlen_sched) — meta is the list tfa_kvcache_varlen_schedule built (NULL allowed in a dry run)
 static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream,
-                          tfa::LaunchGeom* geom, bool dry) {
+                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false) {
   if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
+  if (sched && !dry) {
+    if (!meta) return TFA_ERR_NULL;
+    if ((uintptr_t)meta & 7) return TFA_ERR_ALIGN;
+  }
   int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   if (!p->q || !p->out) return TFA_ERR_NULL;
@@ -1032,13 +1050,16 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
     const long long q_ext = ((long long)(mq - 1) * a.qs_n + (long long)(G - 1) * a.qs_h + p->D) * 2;
     const long long o_ext = ((long long)(mq - 1) * a.os_n + (long long)(G - 1) * a.os_h + p->D) * osz;
     if ((long long)vq->max_seqlen_q * G >= 0x3fffffffll || q_ext >= 0x7fffffffll || o_ext >= 0x7fffffffll) packed = false;
+    if (sched && !packed) return TFA_ERR_STRIDE;         // the list was sized and built for the packing the caller named (tfa_kvcache_varlen_schedule_size): no silent change of it
   }
   const int gp = packed ? G : 1, heads = packed ? p->Hk : p->H;
   if ((long long)vq->max_seqlen_q * gp >= 0x3fffffffll) return TFA_ERR_SHAPE;
   long long nmb, nwork;
   kvcache_vq_blocks(vq->max_seqlen_q, gp, causal, &nmb, &nwork);
+  const long long bound = sched ? kvcache_sched_bound(p->B, vq->max_seqlen_q, tq, gp, causal) : 0;
   if ((long long)p->B * heads * nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
-  tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>> ka;        // (every launch takes the bases it has: vq_launch below)
+  if (sched && (long long)heads * bound * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>> ka;        // (every launch takes the bases it has: vq_launch below)
   memset(&ka, 0, sizeof(ka));
   if (packed) {
     ka.pk_g = G;
@@ -1054,6 +1075,10 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
   a.nmb = (int)nmb;
   a.nwork = (int)nwork;
   a.nbh = p->B * heads;
+  if (sched) {                                               // heads * bound work items: the item decomposition runs over (head, row of the list)
+    a.nbh = heads;
+    a.nwork = (int)bound;
+  }
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
   ka.chunk = 0;
@@ -1074,6 +1099,8 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
   ka.vq_cu = vq->cu_seqlens_q;
   ka.vq_max_q = vq->max_seqlen_q;
   ka.vq_total_q = tq;
+  ka.sc_meta = meta;
+  ka.sc_bound = (int)bound;
   if (q8) {
     ka.k_descale = q8->k_descale; ka.v_descale = q8->v_descale;
     ka.kd_b = q8->k_descale_stride[0]; ka.kd_h = q8->k_descale_stride[1];
@@ -1094,8 +1121,13 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
       if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
       if constexpr (tfa::KvcPack<const Base>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
       v.vq_cu = ka.vq_cu; v.vq_max_q = ka.vq_max_q; v.vq_total_q = ka.vq_total_q;
+      if constexpr (tfa::KvcSc<const A>::value) { v.sc_meta = ka.sc_meta; v.sc_bound = ka.sc_bound; v.sc_pad_ = 0; }
       return tfa::launch_kvc_vq<T, W, A>(v, causal, ns > 1, nt, s, geom, dry);
     };
+    if (sched) {
+      if (packed) return q8 ? run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>>*)nullptr) : run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::KvcArgs>>>*)nullptr);
+      return q8 ? run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcArgs>>*)nullptr);
+    }
     if (packed) return q8 ? run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
     return q8 ? run((tfa::KvcVarlenQ<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcArgs>*)nullptr);
   });
@@ -1139,6 +1171,69 @@ int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa
   if (s > p->capacity / 1024) s = p->capacity / 1024;
   if (s > 32) s = 32;
   return s >= 2 ? (int)s : 1;
+}
+
+// ---- the scheduled form (tfa.h: tfa_kvcache_varlen_schedule, tfa_fwd_kvcache_varlen_sched): the work items of a list built on the device ---------------------------
+// what the list depends on, checked: of *p only B, H, Hk are read.  *gp_out: G' of the packing named; *bound_out: the item rows
+static int kvcache_sched_check(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack, int* gp_out, long long* bound_out, int is_causal) {
+  if (!p || !vq) return TFA_ERR_NULL;
+  if (p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->H % p->Hk != 0) return TFA_ERR_SHAPE;
+  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
+  if (vq->max_seqlen_q <= 0 || vq->total_q <= 0 || vq->reserved_[0] != 0 || vq->reserved_[1] != 0) return TFA_ERR_SHAPE;
+  const int gp = kvcache_vq_packs(p, pack) ? p->H / p->Hk : 1;
+  if ((long long)vq->max_seqlen_q * gp >= 0x3fffffffll) return TFA_ERR_SHAPE;
+  const long long bound = kvcache_sched_bound(p->B, vq->max_seqlen_q, vq->total_q, gp, is_causal != 0);
+  if (bound >= 0x3fffffffll) return TFA_ERR_SHAPE;
+  *gp_out = gp;
+  *bound_out = bound;
+  return TFA_OK;
+}
+long long tfa_kvcache_varlen_schedule_size(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal) {
+  int gp;
+  long long bound;
+  const int st = kvcache_sched_check(p, vq, pack_gqa, &gp, &bound, is_causal);
+  return st != TFA_OK ? st : tfa::SCHEDULE_HDR + 2 * bound;
+}
+static int kvcache_schedule_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack, int is_causal, int32_t* meta, void* stream, bool dry) {
+  int gp;
+  long long bound;
+  const int st = kvcache_sched_check(p, vq, pack, &gp, &bound, is_causal);
+  if (st != TFA_OK) return st;
+  if (!vq->cu_seqlens_q || (!dry && !meta)) return TFA_ERR_NULL;
+  if (((uintptr_t)vq->cu_seqlens_q & 3) || ((uintptr_t)meta & 7)) return TFA_ERR_ALIGN;
+  if (dry) return TFA_OK;
+  tfa::ScheduleArgs a;
+  a.cu = vq->cu_seqlens_q;
+  a.meta = meta;
+  a.B = p->B; a.gp = gp; a.causal = is_causal ? 1 : 0;
+  a.max_q = vq->max_seqlen_q; a.total_q = vq->total_q;
+  a.bound = (int)bound;
+  return (int)tfa::launch_kvcache_schedule(a, reinterpret_cast<hipStream_t>(stream));
+}
+int tfa_kvcache_varlen_schedule(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal, int32_t* metadata, void* stream) {
+  return kvcache_schedule_run(p, vq, pack_gqa, is_causal, metadata, stream, false);
+}
+int tfa_kvcache_varlen_schedule_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int is_causal, int* grid, int* block, int* lds_bytes) {
+  const int st = kvcache_schedule_run(p, vq, pack_gqa, is_causal, nullptr, nullptr, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = 1;
+  if (block) *block = 256;
+  if (lds_bytes) *lds_bytes = 256 * 8;
+  return TFA_OK;
+}
+int tfa_fwd_kvcache_varlen_sched(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, const int32_t* metadata,
+                                 float* workspace, void* stream) {
+  return kvcache_vq_run(p, vq, q8, pack_gqa, splits, workspace, stream, nullptr, false, metadata, true);
+}
+int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block,
+                                      int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, &g, true, nullptr, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
 }
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {

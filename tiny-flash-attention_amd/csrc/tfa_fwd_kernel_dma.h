@@ -165,8 +165,8 @@ struct KvcPackView {
 // 1 unpacked; KArgs::Nq = max_q * G' sizes it and is not read by this form's statements); a block with no row of its sequence (mb * 128 >= nq_b * G') issues no Q, K or V
 // request and no store.  Everything that reads the launch-uniform Nq / nq_pos elsewhere takes nq_b here: the causal shift len_b - nq_b, the packed block's last valid
 // row, row validity.  The Q descriptor starts at row q0_b and ends at the sequence's last row; O, LSE and the fp32 partials go to (h, q0_b + t) of (H, total_q, .)
-// buffers — qs_b / os_b are 0, os_h / the LSE's head stride total_q rows — so tfa_merge runs unchanged over H * total_q rows.  Known cost: the grid is sized by max_q, so
-// one long prefill chunk in a batch of decode rows makes most work items empty; each empty item costs its scalar loads and an exit.
+// buffers — qs_b / os_b are 0, os_h / the LSE's head stride total_q rows — so tfa_merge runs unchanged over H * total_q rows.  The grid is sized by max_q, so
+// one long prefill chunk in a batch of decode rows makes most work items empty; each empty item costs its scalar loads and an exit (KvcSched below removes them).
 // The arguments ride BEHIND the form's struct (KvcArgs, Kvc8Args or their KvcPacked<>), for KvcPacked's reason: no existing kernel's argument block moves.
 // G = 1 (MHA) is served by the unpacked instantiations (KvcPacked::pk_g is 2..128): that is why both exist.
 template <typename Base>
@@ -181,6 +181,30 @@ template <typename A> struct KvcVq { static constexpr bool value = false; };
 template <typename B> struct KvcVq<const KvcVarlenQ<B>> { static constexpr bool value = true; };
 template <bool VQ>
 struct KvcVqView {
+  template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
+};
+// The scheduled form of the varlen-q form (tfa_fwd_kvcache_varlen_sched; FlashAttention-3's scheduler_metadata): the launch carries heads * bound work items instead of
+// B * heads * ceil(max_q * G' / 128) — bound = the host's upper limit of the batch's non-empty items — and work item `si` of a head takes its (sequence, item of that
+// sequence) from row si of a list that tfa_kvcache_varlen_schedule built on the device: int32 metadata, SCHED_HDR header words (n_items first), then n_items rows
+// (b, wi), 8 bytes each, one scalar load.  KArgs::nbh = heads and nwork = bound feed the item decomposition (the per-XCD head grouping included) unchanged.
+// The list is a HINT, verified against what the kernel already trusts: n_items is clamped into [0, bound], b into [0, B), nq_b / the block count nb_b are
+// recomputed from cu_seqlens_q as in the varlen-q form, and a wi outside the sequence's own items is an empty item — so stale, foreign or random metadata
+// misplaces or drops work, it never moves an access outside the tensors.  A causal item is the heavy / light pair (nb_b - 1 - wi, wi) of the SEQUENCE's blocks
+// (the varlen-q form pairs on the launch-level count).  An index at or beyond n_items exits in front of its first request.
+// The arguments ride BEHIND KvcVarlenQ<>, for KvcPacked's reason: no existing kernel's argument block moves.
+constexpr int SCHED_HDR = 8;     // header words of the metadata: n_items, B, G', causal, max_seqlen_q, total_q, bound, 0
+template <typename Base>
+struct KvcSched : Base {
+  const int* sc_meta;       // device int32, SCHED_HDR + 2 * sc_bound entries, 8-byte aligned
+  int sc_bound;             // item rows the buffer holds = KArgs::nwork
+  int sc_pad_;
+};
+template <typename B> struct KvcPack<const KvcSched<B>> : KvcPack<const B> {};
+template <typename B> struct KvcVq<const KvcSched<B>> : KvcVq<const B> {};
+template <typename A> struct KvcSc { static constexpr bool value = false; };
+template <typename B> struct KvcSc<const KvcSched<B>> { static constexpr bool value = true; };
+template <bool SCHED>
+struct KvcScView {
   template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
 };
 template <bool KV8, typename T> struct KvElem { using type = T; };
@@ -256,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8_pack(const KvcPack
 }
 
 // The varlen-q forms of the four (packed ragged query rows: KvcVarlenQ above).  Args: KvcVarlenQ<> of KvcArgs, Kvc8Args or their KvcPacked<>; the e4m3 cache side
-// is the Args' own (Kvc8Args among its bases)
+// is the Args' own (Kvc8Args among its bases).  The scheduled forms (KvcSched<KvcVarlenQ<>>) are further instantiations of this entry point
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT, typename Args>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_vq(const Args p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0) | (NT ? VF_DMA_NT : 0);

@@ -9,6 +9,8 @@
   // the varlen-q form of the KV-cache form (KvcVarlenQ: packed ragged query rows, every sequence's first row and row count read on the device); its arguments are read
   // through KvcVqView<VQ>::of(p), as above
   constexpr bool VQ = KVC && KvcVq<decltype(p)>::value;
+  // the scheduled form of the varlen-q form (KvcSched: the work items of a device-built list); its arguments are read through KvcScView<SCHED>::of(p), as above
+  constexpr bool SCHED = VQ && KvcSc<decltype(p)>::value;
   constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
   using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
@@ -27,6 +29,7 @@
   static_assert(PPW >= 1 && PPW * NW == PIECES, "tile does not split into whole DMA pieces per wave");
   static_assert(!WIDE || (NW == 4 && AB == 0), "the 256-wide form: four waves, no ablations");
   static_assert(!KVC || (!WIDE && AB == 0 && !(VF & (VF_PERSIST | VF_LDSEPI))), "the KV-cache form: 64 / 128 wide, one work item per workgroup");
+  static_assert(!SCHED || !(VF & VF_PERSIST), "the scheduled form: one work item per workgroup (an item behind the list's end returns)");
   static_assert(!KV8 || (KVC && NBUF == 2), "the e4m3 form: a form of the two-buffer KV-cache kernel (one tile staged in registers)");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -94,6 +97,9 @@
   int pg_idx = -1, pg_val = 0;
   // varlen-q form: the first query row, the row count and the block rows (nq_b * G packed) of the sequence the last decode() described
   int vq_q0 = 0, vq_nq = 0, vq_rows = 0;
+  // scheduled form: the item's index among its sequence's own items, that sequence's block count (>= 1), and whether the index lies behind the list's end
+  int sc_wi = 0, sc_nmb = 1;
+  bool sc_dead = false;
   auto decode = [&](int item_all, int pass, Blk& k) {
     k.sp = item_all / nitems0;
     const int item = item_all - k.sp * nitems0;
@@ -105,7 +111,22 @@
       // cache; the chunk size comes from THIS sequence's length, so ragged batches stay balanced; a chunk behind the end is empty (nt = 0: out = 0, lse = +inf)
       typedef __attribute__((address_space(4))) const int cint4;
       const int bh0 = ((p.nbh & 7) == 0) ? (item & 7) + 8 * ((item >> 3) / p.nwork) : item / p.nwork;
-      const int b0 = bh0 / p.H;
+      int b0 = bh0 / p.H;
+      if constexpr (SCHED) {
+        // nbh = heads and nwork = bound: bh0 is the head, the index inside the head the row of the list.  n_items and the row are one scalar load each; both are
+        // hints — n_items clamped into [0, bound] (the rows the buffer holds), b into [0, B), wi checked against the sequence's own items below
+        const auto& ps = KvcScView<SCHED>::of(p);
+        typedef __attribute__((ext_vector_type(2))) int i32x2;
+        typedef __attribute__((address_space(4))) const i32x2 ci32x2;
+        const int si = ((p.nbh & 7) == 0) ? (item >> 3) % p.nwork : item % p.nwork;
+        int n_items = ((const cint4*)(uintptr_t)ps.sc_meta)[0];
+        n_items = n_items < 0 ? 0 : (n_items > ps.sc_bound ? ps.sc_bound : n_items);
+        sc_dead = si >= n_items;
+        i32x2 row = {0, -1};
+        if (!sc_dead) row = ((ci32x2*)(uintptr_t)ps.sc_meta)[SCHED_HDR / 2 + si];
+        b0 = row[0] < 0 ? 0 : (row[0] >= p.B ? p.B - 1 : row[0]);
+        sc_wi = row[1];
+      }
       int len = ((const cint4*)(uintptr_t)pk.seqlens)[b0] + pk.n_new;
       len = len < 0 ? 0 : (len > pk.capacity ? pk.capacity : len);
       const int chunk = (fd_div(len + nsplit - 1, pk.fd_nsplit) + 63) & ~63;
@@ -122,6 +143,12 @@
         vq_nq = d < 0 ? 0 : (d > room ? room : (int)d);
         vq_rows = vq_nq;
         if constexpr (PACK) vq_rows = vq_nq * KvcPackView<PACK>::of(p).pk_g;
+        if constexpr (SCHED) {
+          // the sequence's own blocks and items, from the rows just clamped; a wi that is none of them is an item of a sequence without rows (nothing requested or stored)
+          sc_nmb = (vq_rows + BM - 1) / BM;
+          const int items_b = PAIR ? (sc_nmb + 1) >> 1 : sc_nmb;
+          if (sc_wi < 0 || sc_wi >= items_b) { vq_nq = 0; vq_rows = 0; sc_wi = 0; sc_nmb = 1; }
+        }
         nq_pos = vq_nq;
       }
       k.shift = len - nq_pos - k.sp * chunk;
@@ -141,8 +168,14 @@
       k.bh = item / p.nwork;
       k.wi = item % p.nwork;
     }
-    if (PAIR) k.mb = pass == 0 ? (p.nmb - 1 - k.wi) : k.wi;     // heavy block first, then the light one
-    else k.mb = CAUSAL ? (p.nmb - 1 - k.wi) : k.wi;
+    int nmb = p.nmb;
+    if constexpr (SCHED) {                                       // the list's (sequence, item) and the sequence's own block count in the place of the launch's
+      k.bh = k.bt_row * p.H + k.bh;
+      k.wi = sc_wi;
+      nmb = sc_nmb;
+    }
+    if (PAIR) k.mb = pass == 0 ? (nmb - 1 - k.wi) : k.wi;       // heavy block first, then the light one
+    else k.mb = CAUSAL ? (nmb - 1 - k.wi) : k.wi;
     int kv_end = k.nk;
     if (CAUSAL) {
       int lim = k.mb * BM + BM + k.shift;                        // one past the last key any row of the block sees
@@ -317,6 +350,9 @@
   if (item >= nitems) return;
   Blk cur;
   decode(item, pass, cur);
+  if constexpr (SCHED) {
+    if (sc_dead) return;                                         // behind the list's end (one item per workgroup: the whole workgroup leaves, in front of its first request)
+  }
   prefetch(cur);
 
   while (true) {
@@ -569,7 +605,9 @@
     const long long o_part = (long long)cur.sp * p.o_part_stride, lse_part = (long long)cur.sp * p.lse_part_stride;   // 0 unless split
     constexpr bool LDS_EPI = !F32OUT && (VF & VF_LDSEPI);   // 16-bit O goes out through LDS as whole rows
     bool have_next;
-    if (PAIR && pass == 0 && (p.nmb - 1 - cur.wi) != cur.wi) {
+    int pair_nmb = p.nmb;
+    if constexpr (SCHED) pair_nmb = sc_nmb;                      // (still the finished block's: decode() of the next one comes below)
+    if (PAIR && pass == 0 && (pair_nmb - 1 - cur.wi) != cur.wi) {
       pass = 1;
       have_next = true;
     } else {

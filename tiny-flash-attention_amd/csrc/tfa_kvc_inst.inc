@@ -8,12 +8,19 @@
 #ifndef TFA_KVC_VQ
 #define TFA_KVC_VQ 0         // 1: the unit of the varlen-q form (tfa_kvc_inst_vq_<dtype>_<W>, tfa_kvc_inst_pack_vq_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc_vq
 #endif
+#ifndef TFA_KVC_SCHED
+#define TFA_KVC_SCHED 0      // 1 (with TFA_KVC_VQ): the unit of the scheduled form (tfa_kvc_inst_vq_sched_<dtype>_<W>, tfa_kvc_inst_pack_vq_sched_<dtype>_<W>) — fwd_kernel_dma_kvc_vq over KvcSched<>
+#endif
+#if TFA_KVC_SCHED && !TFA_KVC_VQ
+#error "the scheduled form is a form of the varlen-q form"
+#endif
 
 namespace tfa {
 
 // the arguments of this unit's kernels: the form's struct, behind it the packed form's (TFA_KVC_PACK), behind both the varlen-q form's (TFA_KVC_VQ)
 using UnitBase = std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<KvcArgs>, KvcArgs>;
-using UnitArgs = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
+using UnitVq = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
+using UnitArgs = std::conditional_t<TFA_KVC_SCHED != 0, KvcSched<UnitVq>, UnitVq>;     // ... and behind the three the scheduled form's (TFA_KVC_SCHED)
 
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {

@@ -37,4 +37,15 @@ struct Append8Args : AppendArgs {
 };
 hipError_t launch_kvcache_append_fp8(const Append8Args& a, hipStream_t stream);
 
+// tfa_kvcache_schedule.hip: the work list of tfa_fwd_kvcache_varlen_sched, built on the device from cu_seqlens_q (one workgroup of 256 threads)
+constexpr int SCHEDULE_HDR = 8;   // header words (tfa_fwd_kernel_dma.h: SCHED_HDR — the same number, asserted in tfa_api.hip)
+struct ScheduleArgs {
+  const int* cu;              // device int32, B + 1 entries
+  int* meta;                  // device int32, SCHEDULE_HDR + 2 * bound entries, 8-byte aligned
+  int B, gp, causal;          // gp = G' (G packed, 1 unpacked)
+  int max_q, total_q;
+  int bound;                  // item rows the buffer holds
+};
+hipError_t launch_kvcache_schedule(const ScheduleArgs& a, hipStream_t stream);
+
 }  // namespace tfa

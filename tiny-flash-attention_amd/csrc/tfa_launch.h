@@ -226,6 +226,13 @@ hipError_t launch_kvc_vq(const Args& a, bool causal, bool f32out, bool nt, hipSt
 TFA_KVCVQ_UNITS(__bf16, 64) TFA_KVCVQ_UNITS(__bf16, 128) TFA_KVCVQ_UNITS(_Float16, 64) TFA_KVCVQ_UNITS(_Float16, 128)
 #undef TFA_KVCVQ_UNITS
 #undef TFA_KVCVQ_UNIT
+// ... and the scheduled forms of those (tfa_fwd_kvcache_varlen_sched; the same kernel template over KvcSched<KvcVarlenQ<>>): tfa_kvc_inst_vq_sched_*, tfa_kvc_inst_pack_vq_sched_*,
+// tfa_kvc8_inst_vq_sched_* and tfa_kvc8_inst_pack_vq_sched_* — the same .inc files compiled with TFA_KVC_VQ and TFA_KVC_SCHED
+#define TFA_KVCSC_UNIT(T, D, A) template <> hipError_t launch_kvc_vq<T, D, KvcSched<KvcVarlenQ<A>>>(const KvcSched<KvcVarlenQ<A>>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+#define TFA_KVCSC_UNITS(T, D) TFA_KVCSC_UNIT(T, D, KvcArgs) TFA_KVCSC_UNIT(T, D, Kvc8Args) TFA_KVCSC_UNIT(T, D, KvcPacked<KvcArgs>) TFA_KVCSC_UNIT(T, D, KvcPacked<Kvc8Args>)
+TFA_KVCSC_UNITS(__bf16, 64) TFA_KVCSC_UNITS(__bf16, 128) TFA_KVCSC_UNITS(_Float16, 64) TFA_KVCSC_UNITS(_Float16, 128)
+#undef TFA_KVCSC_UNITS
+#undef TFA_KVCSC_UNIT
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

@@ -902,8 +902,8 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
-                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, k_descale=None,
-                            v_descale=None):
+                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, scheduler_metadata=None,
+                            k_descale=None, v_descale=None):
     """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
 
     ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
@@ -940,7 +940,15 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     H / Hk <= 128, False runs unpacked (as do H == Hk and H / Hk > 128).  ``num_splits=0`` asks tfa_fwd_kvcache_varlen_suggest_splits.  Returns ``out``
     (total_q, H, D), a transposed view of the dense (H, total_q, D) buffer the kernel or the merge writes, and ``lse`` (H, total_q) fp32.  Paged and contiguous
     caches, fp8 caches with descales, zero fill behind the lengths, no host synchronisation, graph capture and "not differentiable": as above.  The grid is sized
-    by ``max_seqlen_q``: one long prefill chunk in a batch of decode rows makes most work items empty (each costs its scalar loads and an exit).
+    by ``max_seqlen_q``: one long prefill chunk in a batch of decode rows makes most work items empty (each costs its scalar loads and an exit) — unless
+    ``scheduler_metadata`` is given.
+    ``scheduler_metadata`` (keyword-only, FlashAttention-3's; tfa_fwd_kvcache_varlen_sched): the tensor ``get_scheduler_metadata`` returned for this step's
+    ``cu_seqlens_q``, ``max_seqlen_q``, total_q, head counts, ``causal`` and ``pack_gqa`` — the list of the batch's non-empty work items, built once per step on
+    the device and reused by every layer.  The launch then carries heads * bound work items (bound: the host-known limit of the list) instead of
+    B * heads * ceil(max_seqlen_q * G' / 128); ``out`` and ``lse`` are bit for bit those of the call without it.  The kernel verifies every entry against
+    ``cu_seqlens_q``: a list that does not belong to the batch gives unspecified or unwritten rows and never an access outside the tensors.  Refused before any
+    launch: given without ``cu_seqlens_q`` (ValueError), a non-tensor (TypeError), not int32 / not on q's device / not contiguous, or a ``numel`` other than
+    tfa_kvcache_varlen_schedule_size for this call (ValueError).  None (the default): the call is exactly what it was.
     Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes,
     fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
     name = "flash_attn_with_kvcache"
@@ -954,9 +962,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise NotImplementedError(f"{name}: softcap is not implemented in the K/V-cache path")
     if cu_seqlens_q is None and max_seqlen_q is not None:
         raise ValueError(f"{name}: max_seqlen_q belongs to cu_seqlens_q (packed (total_q, H, D) query rows), which was not given")
+    if cu_seqlens_q is None and scheduler_metadata is not None:
+        raise ValueError(f"{name}: scheduler_metadata belongs to cu_seqlens_q (packed (total_q, H, D) query rows), which was not given")
     if cu_seqlens_q is not None:
         return _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse,
-                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q)
+                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata)
     for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{name}: {n} must be a 4-D tensor")
@@ -1075,9 +1085,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
 
 
 def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse, pack_gqa,
-                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q):
-    """``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=)`` (tfa_fwd_kvcache_varlen): the checks of the packed form, then the calls.  Every refusal comes
-    before any library call."""
+                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata=None):
+    """``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=)`` (tfa_fwd_kvcache_varlen; with ``scheduler_metadata`` tfa_fwd_kvcache_varlen_sched): the checks of the
+    packed form, then the calls.  Every refusal comes before any launch."""
     name = "flash_attn_with_kvcache"
     if not isinstance(q, torch.Tensor) or q.dim() != 3:
         got = tuple(q.shape) if isinstance(q, torch.Tensor) else type(q).__name__
@@ -1162,8 +1172,19 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
         raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
+    if scheduler_metadata is not None:
+        if not isinstance(scheduler_metadata, torch.Tensor):
+            raise TypeError(f"{name}: scheduler_metadata must be the tensor get_scheduler_metadata returned (got {type(scheduler_metadata).__name__})")
+        if scheduler_metadata.dtype != torch.int32 or scheduler_metadata.device != q.device or not scheduler_metadata.is_contiguous():
+            raise ValueError(f"{name}: scheduler_metadata must be a contiguous int32 tensor on q's device (got {scheduler_metadata.dtype} on "
+                             f"{scheduler_metadata.device})")
 
     L = _lib.lib()
+    if scheduler_metadata is not None:
+        want = _scheduler_metadata_size(name, B, H, Hk, int(max_seqlen_q), total_q, pack_gqa, causal)
+        if scheduler_metadata.numel() != want:
+            raise ValueError(f"{name}: scheduler_metadata holds {scheduler_metadata.numel()} entries, this call's schedule (B {B}, max_seqlen_q {max_seqlen_q}, "
+                             f"total_q {total_q}, H {H}, Hk {Hk}, causal {bool(causal)}, pack_gqa {pack_gqa!r}) holds {want}: it was built for another batch")
     lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device) if return_softmax_lse else None
     dense = torch.empty((H, total_q, D), dtype=q.dtype, device=q.device)          # what the merge writes; one chunk: the kernel writes it the same way
     p = _lib.TfaKvcacheParams()
@@ -1205,9 +1226,70 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
     ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
     with torch.cuda.device(q.device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.tfa_fwd_kvcache_varlen(C.byref(p), C.byref(vq), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        if scheduler_metadata is not None:
+            _lib.check(L.tfa_fwd_kvcache_varlen_sched(C.byref(p), C.byref(vq), q8, pack, num_splits, C.c_void_p(scheduler_metadata.data_ptr()),
+                                                      ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        else:
+            _lib.check(L.tfa_fwd_kvcache_varlen(C.byref(p), C.byref(vq), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
     out = dense.transpose(0, 1)
     return (out, lse) if return_softmax_lse else out
+
+
+def _scheduler_metadata_size(name, B, H, Hk, max_seqlen_q, total_q, pack_gqa, causal):
+    """tfa_kvcache_varlen_schedule_size for a batch: the int32 entries of its work list (of the parameter block only B, H, Hk are read)."""
+    p = _lib.TfaKvcacheParams()
+    p.B, p.H, p.Hk = B, H, Hk
+    vq = _lib.TfaKvcacheVarlenQ()
+    vq.max_seqlen_q, vq.total_q = max_seqlen_q, total_q
+    pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
+    n = int(_lib.lib().tfa_kvcache_varlen_schedule_size(C.byref(p), C.byref(vq), pack, 1 if causal else 0))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+def get_scheduler_metadata(cu_seqlens_q, max_seqlen_q, total_q, num_heads, num_heads_k, *, causal=False, pack_gqa=None, out=None):
+    """FlashAttention-3's ``get_scheduler_metadata`` for ``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=, scheduler_metadata=)``
+    (tfa_kvcache_varlen_schedule): the work list of a unified batch, built on the device in ONE launch on the current stream — nothing is read on the host, so
+    the call does not synchronise and captures into a graph.  Build it once per step and hand it to every layer's attention call.
+
+    ``cu_seqlens_q``: contiguous int32 device tensor of B + 1 entries; ``max_seqlen_q``, ``total_q`` (= q.shape[0]), ``num_heads``, ``num_heads_k``: positive
+    host ints; ``causal`` and ``pack_gqa`` as the attention call will get them (None / True pack when Hk < H and H / Hk <= 128).  ``out``: an int32 tensor of
+    the right size from an earlier step, overwritten and returned — a captured step keeps one buffer.  Returns the int32 tensor
+    (8 + 2 * bound entries: a header — n_items, B, G', causal, max_seqlen_q, total_q, bound, 0 — then one (sequence, item) row per non-empty work item)."""
+    name = "get_scheduler_metadata"
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2:
+        raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of B + 1 entries")
+    if not cu_seqlens_q.is_cuda:
+        raise RuntimeError("cu_seqlens_q must be a CUDA tensor")
+    if not cu_seqlens_q.is_contiguous():
+        raise ValueError(f"{name}: cu_seqlens_q must be contiguous")
+    for n, val in (("max_seqlen_q", max_seqlen_q), ("total_q", total_q), ("num_heads", num_heads), ("num_heads_k", num_heads_k)):
+        if isinstance(val, (bool, torch.Tensor)) or not isinstance(val, int) or val <= 0:
+            raise ValueError(f"{name}: {n} must be a positive host int (got {val!r})")
+    if num_heads % num_heads_k != 0:
+        raise ValueError(f"{name}: the K/V heads ({num_heads_k}) must divide the query heads ({num_heads})")
+    if pack_gqa is not None and pack_gqa is not True and pack_gqa is not False:
+        raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
+    B = cu_seqlens_q.numel() - 1
+    want = _scheduler_metadata_size(name, B, num_heads, num_heads_k, max_seqlen_q, total_q, pack_gqa, causal)
+    if out is None:
+        out = torch.empty((want,), dtype=torch.int32, device=cu_seqlens_q.device)
+    elif not isinstance(out, torch.Tensor):
+        raise TypeError(f"{name}: out must be a tensor (got {type(out).__name__})")
+    elif out.dtype != torch.int32 or out.device != cu_seqlens_q.device or not out.is_contiguous() or out.numel() != want:
+        raise ValueError(f"{name}: out must be a contiguous int32 tensor of {want} entries on cu_seqlens_q's device")
+    L = _lib.lib()
+    p = _lib.TfaKvcacheParams()
+    p.B, p.H, p.Hk = B, num_heads, num_heads_k
+    vq = _lib.TfaKvcacheVarlenQ()
+    vq.cu_seqlens_q = cu_seqlens_q.data_ptr()
+    vq.max_seqlen_q, vq.total_q = max_seqlen_q, total_q
+    pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
+    with torch.cuda.device(cu_seqlens_q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.tfa_kvcache_varlen_schedule(C.byref(p), C.byref(vq), pack, 1 if causal else 0, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    return out
 
 
 # ---- the serving step's parts around attention: rotary embedding and the packed append (tfa_rotary, tfa_kvcache_append_varlen) ------------------------------
