@@ -140,6 +140,14 @@ typedef struct tfa_fwd_params {
  *   every path, 16-bit output vs the exact (fp64) result:      |d| <= 1e-2                 — the reference's own bar (test.py:87)
  *   every path, fp32 output vs the exact result:               |d| <= eps16 * A + 1e-6     — the rigorous bound of rounding P to 16 bits
  *   every path, LSE:                                           |d| <= 1e-4, +inf exactly where a row sees no key
+ *   the KV-cache family (tfa_fwd_kvcache and its _fp8 / _pack / _varlen / _varlen_sched forms, any split count, behind either append),
+ *   16-bit output vs the exact result:                         |d| <= eps16 * A + 1e-6 + half an ulp16 of the result — the fp32-output bound plus the ONE
+ *                                                              rounding of O (partials and tfa_merge are fp32); A = v_descale * sum_j P_ij |dec v_jd|
+ *   the KV-cache family, LSE (u = 2^-24, T = max_j scale * k_descale * sum_d |q_d| |dec k_jd|, n keys):
+ *                                                              |d| <= u * ((D + 15) * T + 4 * ceil(n / 64) + 13) + 2^-22 * |lse|, merged over s parts
+ *                                                              + u * (5 * s + 4) + u * |lse| — derived term by term from the kernel body and tfa_merge
+ *                                                              (tests/kvcache_ref.py: lse_bound); both asserted element by element in
+ *                                                              tests/test_kvcache_fwd_bounds_gpu.py, proved to fit and to bite in tests/test_kvcache_bounds_cpu.py
  *   default kernels (TFA_RULE_LAZY / TFA_RULE_FIRST_TILE), fp32 output vs the reference's tile loop restated with THEIR rounding points:
  *                                                              |d| <= 1e-3 * |ref| + 1e-4 * A  (<= 1e-4 of the elements may flip one rounding of P)
  *   TFA_FWD_EXACT_MAX, fp32 output vs the reference's own tile loop (main_torch_only.py:160-270), element by element:
