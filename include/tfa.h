@@ -873,6 +873,35 @@ int tfa_kvcache_varlen_schedule_plan(const tfa_kvcache_params* p, const tfa_kvca
 int tfa_fwd_kvcache_varlen_sched(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int splits, const int32_t* metadata, float* workspace, void* stream);
 int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes);
 
+/* ---- a SLIDING WINDOW over the K/V cache (the model configs' sliding_window; FlashAttention's window_size = (window_left, 0)) -------------------------------
+ * One entry point for every form above: vq == NULL is the 4-D call (tfa_fwd_kvcache_pack's arguments, k_new / v_new appended first), vq != NULL the packed-q call
+ * (tfa_fwd_kvcache_varlen's), metadata != NULL its scheduled form (tfa_fwd_kvcache_varlen_sched's; needs vq); q8 != NULL an e4m3 cache.  p->is_causal must be set.
+ * Definition: key j is visible to row t of sequence b iff  t + shift_b - window_left <= j <= t + shift_b  and  0 <= j < len_b,  shift_b = len_b - nq_b, with len_b and
+ *   nq_b clamped exactly as the underlying form clamps them (Nq in the 4-D form, the clamped cu_seqlens_q difference in the packed form): a row sees its own key and
+ *   the window_left keys in front of it.  A row that sees no key gives out = 0, lse = +inf.  window_left >= capacity reaches every key a row can see.
+ * Chunks: with lo_b = max(0, shift_b - window_left) the first key the sequence's first row sees and lo64_b = lo_b & ~63, the range cut into the call's chunks is
+ *   [lo64_b, len_b), not [0, len_b): chunk_b = round_up(ceil((len_b - lo64_b) / chunks), 64), chunk s covers [lo64_b + s * chunk_b, min(len_b, lo64_b + (s + 1) *
+ *   chunk_b)).  Chunk starts stay multiples of 64 (a tile never straddles a page); trailing empty chunks give the empty partials tfa_merge skips.  The chunk count, the
+ *   workspace size and the merge are the underlying form's.
+ * What is touched (the promise to an engine that frees the pages behind the window): no work item of sequence b loads a block-table entry of a page that ends at or
+ *   before lo64_b, and none loads a K/V byte in front of key lo64_b.  Those table entries may hold anything, those pages may hold NaN.  Inside a query block the tile
+ *   loop starts at the first 64-key tile some row of the block sees (packed rows: per position t = row / G), and a wave skips the tiles in front of its own first
+ *   row's window.  Behind len_b the descriptors end as they do in every form.
+ * Finite keys: the keys of a VISITED tile that lie left of a row's window are masked to -inf — they are the sequence's own older keys, at or behind lo64_b, and the
+ *   caller keeps them finite: P = 0 times a NaN V row is NaN.
+ * GQA at Nq == 1 (vq == NULL): TFA_PACK_GQA_AUTO and _ON run the G heads of a K/V head as position-major packed rows (t = row / G = 0, the causal bounds hold), so K/V
+ *   streams once per K/V head; at Nq > 1 the packing follows tfa_fwd_kvcache_pack (ON packs, AUTO does not).  Packed-q calls pack as tfa_fwd_kvcache_varlen does.
+ * _window_suggest_splits: the underlying form's rule with min(capacity, round_up(window_left + rows, 64) + 64) standing in for the lengths, rows = Nq or max_seqlen_q.
+ * _window_plan: the underlying form's grid, block and LDS bytes (the window changes no launch geometry); validates without a GPU.  A plan has no list: `scheduled`
+ *   != 0 asks for the scheduled form's geometry (tfa_fwd_kvcache_varlen_sched_plan's; needs vq), 0 for the unscheduled one's.
+ * Refused, nothing launched: window_left < 0, p->is_causal == 0, metadata without vq (TFA_ERR_SHAPE); everything the underlying form refuses, with its codes.
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcWindow, behind the form's struct; fwd_kernel_dma_kvc_win) — the causal template, the 16-bit direct output and the fp32 partials,
+ * units of their own (tfa_kvc_inst_win_*, tfa_kvc8_inst_win_*), so every other kernel keeps its instructions (profiles/kvcache_window_isa_unchanged.txt). */
+int tfa_fwd_kvcache_window(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq /* NULL: 4-D */, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int window_left, int splits, const int32_t* metadata /* NULL: unscheduled; needs vq */, float* workspace, void* stream);
+int tfa_fwd_kvcache_window_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, int scheduled, int* grid, int* block, int* lds_bytes);
+long long tfa_fwd_kvcache_window_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits);
+int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int window_left);
+
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the
  * same launch (q and k of one step).  16-bit elements, any batch / head / row strides (elements), unit stride along D: a slice of a packed QKV projection works.

@@ -112,6 +112,10 @@ SYMBOLS = (
     "tfa_kvcache_varlen_schedule_plan",
     "tfa_fwd_kvcache_varlen_sched",
     "tfa_fwd_kvcache_varlen_sched_plan",
+    "tfa_fwd_kvcache_window",
+    "tfa_fwd_kvcache_window_plan",
+    "tfa_fwd_kvcache_window_workspace",
+    "tfa_fwd_kvcache_window_suggest_splits",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -615,6 +619,15 @@ def lib():
     L.tfa_fwd_kvcache_varlen_sched.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tfa_fwd_kvcache_varlen_sched_plan.restype = C.c_int
     L.tfa_fwd_kvcache_varlen_sched_plan.argtypes = [PK, PV, P8, C.c_int, C.c_int, IP, IP, IP]
+    # ... and a sliding window over the cache, one entry point for every form (PV None: the 4-D call; the metadata pointer None: unscheduled)
+    L.tfa_fwd_kvcache_window.restype = C.c_int
+    L.tfa_fwd_kvcache_window.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_window_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_window_plan.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_window_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_window_workspace.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_int]
+    L.tfa_fwd_kvcache_window_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_window_suggest_splits.argtypes = [PK, PV, C.c_int, C.c_int]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

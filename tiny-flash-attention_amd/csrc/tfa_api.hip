@@ -815,9 +815,13 @@ static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8
 
 // one host path for the 16-bit cache (q8 == nullptr: tfa_fwd_kvcache) and the e4m3 cache (tfa_fwd_kvcache_fp8): validation, chunking, packing and the three launches
 // pack: TFA_PACK_GQA_AUTO — what tfa_fwd_kvcache runs, ON / OFF — tfa_fwd_kvcache_pack's choices
-static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+// win_left >= 0: the windowed form (tfa_fwd_kvcache_window) — the same checks, chunks and workspace; causal only; Nq == 1 packs position-major like Nq > 1
+static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry,
+                       int win_left = -1) {
   int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
+  const bool win = win_left >= 0;
+  if (win && !p->is_causal) return TFA_ERR_SHAPE;
   if (!p->q || !p->out) return TFA_ERR_NULL;
   if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
   if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
@@ -852,7 +856,7 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   {
     tfa_fwd_params fp;
     st = TFA_ERR_SHAPE;
-    if (pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
+    if (!win && pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
       st = validate(&fp, &a, tfa::kSplitVariant);
       if (st == TFA_OK) f = fp;
     }
@@ -862,7 +866,9 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   tfa::KvcPacked<tfa::Kvc8Args> ka;                         // (the 16-bit launch takes its KvcArgs base; the unpacked launches theirs, without the packed form's tail)
   memset(&ka, 0, sizeof(ka));
   // several rows per sequence, packed: the validated problem is the caller's own — its packed description replaces the geometry only
-  const bool packed_rows = kvcache_packs_positions(p, pack) && kvcache_pack_args(p, f.is_causal != 0, ns > 1 ? 4 : 2, &a, &ka);
+  // (windowed, one row per sequence: the heads-as-rows packing above is a non-causal problem, which has no window — the position-major one serves it, t = row / G = 0)
+  const bool pack_pos = kvcache_packs_positions(p, pack) || (win && pack != TFA_PACK_GQA_OFF && kvcache_packs(p));
+  const bool packed_rows = pack_pos && kvcache_pack_args(p, f.is_causal != 0, ns > 1 ? 4 : 2, &a, &ka);
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
   ka.chunk = 0;                                            // (formed per sequence on the device)
@@ -895,6 +901,21 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   }
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
     using T = typename decltype(k)::T;
+    if (win) {
+      // the arguments of the instantiation that runs: the form's struct with the window behind it
+      auto run = [&](auto* args) {
+        using A = std::remove_pointer_t<decltype(args)>;
+        A v;
+        memset(&v, 0, sizeof(v));
+        static_cast<tfa::KvcArgs&>(v) = ka;
+        if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
+        if constexpr (tfa::KvcPack<const A>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
+        v.win_left = win_left < p->capacity ? win_left : p->capacity;
+        return tfa::launch_kvc_win<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
+      };
+      if (packed_rows) return q8 ? run((tfa::KvcWindow<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcWindow<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
+      return q8 ? run((tfa::KvcWindow<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcWindow<tfa::KvcArgs>*)nullptr);
+    }
     if (packed_rows) {
       if (q8) return tfa::launch_kvc8_pack<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
       tfa::KvcPacked<tfa::KvcArgs> k16;
@@ -994,8 +1015,10 @@ static_assert(tfa::SCHED_HDR == tfa::SCHEDULE_HDR, "one header size for the kern
 
 // sched: the scheduled form (tfa_fwd_kvcache_varlen_sched) — meta is the list tfa_kvcache_varlen_schedule built (NULL allowed in a dry run)
 static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream,
-                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false) {
+                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false, int win_left = -1) {
   if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
+  const bool win = win_left >= 0;                            // the windowed form (tfa_fwd_kvcache_window): the same checks, geometry and workspace; causal only
+  if (win && !p->is_causal) return TFA_ERR_SHAPE;
   if (sched && !dry) {
     if (!meta) return TFA_ERR_NULL;
     if ((uintptr_t)meta & 7) return TFA_ERR_ALIGN;
@@ -1122,6 +1145,13 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
       if constexpr (tfa::KvcPack<const Base>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
       v.vq_cu = ka.vq_cu; v.vq_max_q = ka.vq_max_q; v.vq_total_q = ka.vq_total_q;
       if constexpr (tfa::KvcSc<const A>::value) { v.sc_meta = ka.sc_meta; v.sc_bound = ka.sc_bound; v.sc_pad_ = 0; }
+      if (win) {
+        tfa::KvcWindow<A> w;
+        memset(&w, 0, sizeof(w));
+        static_cast<A&>(w) = v;
+        w.win_left = win_left < p->capacity ? win_left : p->capacity;
+        return tfa::launch_kvc_win<T, W, tfa::KvcWindow<A>>(w, ns > 1, s, geom, dry);
+      }
       return tfa::launch_kvc_vq<T, W, A>(v, causal, ns > 1, nt, s, geom, dry);
     };
     if (sched) {
@@ -1234,6 +1264,45 @@ int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvc
   if (block) *block = g.block;
   if (lds_bytes) *lds_bytes = g.lds;
   return TFA_OK;
+}
+
+// ---- the windowed form (tfa.h: tfa_fwd_kvcache_window): one entry point over the 4-D, packed-q and scheduled host paths above ------------------------------------
+static int kvcache_window_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int left, int splits, const int32_t* meta,
+                              bool sched, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+  if (!p) return TFA_ERR_NULL;
+  if (left < 0 || !p->is_causal || (sched && !vq)) return TFA_ERR_SHAPE;
+  if (vq) return kvcache_vq_run(p, vq, q8, pack, splits, workspace, stream, geom, dry, meta, sched, left);
+  return kvcache_run(p, q8, pack, splits, workspace, stream, geom, dry, left);
+}
+int tfa_fwd_kvcache_window(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, const int32_t* metadata,
+                           float* workspace, void* stream) {
+  return kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, metadata, metadata != nullptr, workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_window_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, int scheduled,
+                                int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, nullptr, scheduled != 0, nullptr, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+long long tfa_fwd_kvcache_window_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits) {
+  const int st = kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, nullptr, false, nullptr, nullptr, nullptr, true);
+  if (st != TFA_OK) return st;
+  const int ns = kvcache_chunks(p, splits);
+  if (ns <= 1) return 0;
+  return vq ? (long long)ns * p->H * vq->total_q * (p->D + 1) : (long long)ns * p->B * p->H * p->Nq * (p->D + 1);
+}
+int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int window_left) {
+  if (!p || window_left < 0 || p->capacity <= 0) return 1;
+  // the underlying form's rule; the keys a row streams, min(capacity, round_up(window_left + rows, 64) + 64), stand in for the lengths
+  const long long rows = vq ? vq->max_seqlen_q : p->Nq;
+  const long long reach = ((window_left + (rows > 0 ? rows : 0) + 63) & ~63ll) + 64;
+  tfa_kvcache_params w = *p;
+  if (reach < w.capacity) w.capacity = (int)reach;
+  return vq ? tfa_fwd_kvcache_varlen_suggest_splits(&w, vq, pack_gqa) : kvcache_suggest_splits(&w, pack_gqa);
 }
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {

@@ -207,6 +207,28 @@ template <bool SCHED>
 struct KvcScView {
   template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
 };
+// The windowed form of the KV-cache form (tfa_fwd_kvcache_window; the model configs' sliding_window, FlashAttention's window_size = (left, 0)): on the causal template,
+// key j is visible to the row at position t of sequence b iff t + shift_b - left <= j <= t + shift_b (and 0 <= j < len_b), shift_b = len_b - nq_b.  With
+// lo_b = max(0, shift_b - left) the first key the sequence's first row sees and lo64_b = lo_b & ~63, the range cut into chunks is [lo64_b, len_b): no work item loads a
+// block-table entry of a page that ends at or before lo64_b, or a K/V byte in front of it.  A query block starts at the first 64-key tile some row of it sees — its
+// chunk is narrowed to start there in decode(), so the prefetch, the tile loop and the buffer rotation count from it — and a wave skips the tiles in front of its
+// first row's window as it skips those behind its last row's diagonal.  Keys of a visited tile left of a row's window are masked to -inf (they must be finite:
+// P = 0 times a NaN V row is NaN).  The one argument rides BEHIND the form's struct — any of the twelve above — for KvcPacked's reason.
+template <typename Base>
+struct KvcWindow : Base {
+  using win_base = Base;
+  int win_left;             // keys a row sees in front of its own: w - 1 >= 0 (the host clamps it to the capacity)
+  int win_pad_;
+};
+template <typename B> struct KvcPack<const KvcWindow<B>> : KvcPack<const B> {};
+template <typename B> struct KvcVq<const KvcWindow<B>> : KvcVq<const B> {};
+template <typename B> struct KvcSc<const KvcWindow<B>> : KvcSc<const B> {};
+template <typename A> struct KvcWin { static constexpr bool value = false; };
+template <typename B> struct KvcWin<const KvcWindow<B>> { static constexpr bool value = true; };
+template <bool WIN>
+struct KvcWinView {
+  template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
+};
 template <bool KV8, typename T> struct KvElem { using type = T; };
 template <typename T> struct KvElem<true, T> { using type = unsigned char; };
 
@@ -284,6 +306,15 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8_pack(const KvcPack
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT, typename Args>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_vq(const Args p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0) | (NT ? VF_DMA_NT : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+
+// The windowed forms of all twelve (a sliding window over the cache: KvcWindow above).  Args: KvcWindow<> of any form's struct; causal only, no non-temporal twin
+// (a window's range is small)
+template <typename T, int D, bool F32OUT, typename Args>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_win(const Args p) {
+  constexpr bool CAUSAL = true;
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0);
 #include "tfa_fwd_kernel_dma_body.inc"
 }
 

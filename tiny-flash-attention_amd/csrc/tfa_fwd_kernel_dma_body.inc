@@ -11,6 +11,8 @@
   constexpr bool VQ = KVC && KvcVq<decltype(p)>::value;
   // the scheduled form of the varlen-q form (KvcSched: the work items of a device-built list); its arguments are read through KvcScView<SCHED>::of(p), as above
   constexpr bool SCHED = VQ && KvcSc<decltype(p)>::value;
+  // the windowed form of any of those (KvcWindow: a sliding window of win_left keys in front of a row's own); its argument is read through KvcWinView<WIN>::of(p), as above
+  constexpr bool WIN = KVC && KvcWin<decltype(p)>::value;
   constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
   using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
@@ -30,6 +32,7 @@
   static_assert(!WIDE || (NW == 4 && AB == 0), "the 256-wide form: four waves, no ablations");
   static_assert(!KVC || (!WIDE && AB == 0 && !(VF & (VF_PERSIST | VF_LDSEPI))), "the KV-cache form: 64 / 128 wide, one work item per workgroup");
   static_assert(!SCHED || !(VF & VF_PERSIST), "the scheduled form: one work item per workgroup (an item behind the list's end returns)");
+  static_assert(!WIN || (CAUSAL && PAIR), "the windowed form: a form of the causal KV-cache kernel");
   static_assert(!KV8 || (KVC && NBUF == 2), "the e4m3 form: a form of the two-buffer KV-cache kernel (one tile staged in registers)");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -129,8 +132,8 @@
       }
       int len = ((const cint4*)(uintptr_t)pk.seqlens)[b0] + pk.n_new;
       len = len < 0 ? 0 : (len > pk.capacity ? pk.capacity : len);
-      const int chunk = (fd_div(len + nsplit - 1, pk.fd_nsplit) + 63) & ~63;
-      const int rest = len - k.sp * chunk;
+      int chunk = (fd_div(len + nsplit - 1, pk.fd_nsplit) + 63) & ~63;
+      int rest = len - k.sp * chunk;
       k.nk = rest < chunk ? (rest > 0 ? rest : 0) : chunk;
       int nq_pos = pk.nq_pos;
       if constexpr (VQ) {
@@ -153,6 +156,16 @@
       }
       k.shift = len - nq_pos - k.sp * chunk;
       k.tile0 = (k.sp * chunk) >> 6;
+      if constexpr (WIN) {
+        // the chunks are cut from [lo64, len): lo the first key the sequence's first row sees, rounded down to a tile; shift counts against the chunk's first key
+        const int lo = len - nq_pos - KvcWinView<WIN>::of(p).win_left;
+        const int lo64 = lo > 0 ? lo & ~63 : 0;
+        chunk = (fd_div(len - lo64 + nsplit - 1, pk.fd_nsplit) + 63) & ~63;
+        rest = len - lo64 - k.sp * chunk;
+        k.nk = rest < chunk ? (rest > 0 ? rest : 0) : chunk;
+        k.shift = len - nq_pos - lo64 - k.sp * chunk;
+        k.tile0 = (lo64 + k.sp * chunk) >> 6;
+      }
       k.bt_row = b0;
       pg_idx = -1;
     } else if (nsplit > 1) {
@@ -176,6 +189,17 @@
     }
     if (PAIR) k.mb = pass == 0 ? (nmb - 1 - k.wi) : k.wi;       // heavy block first, then the light one
     else k.mb = CAUSAL ? (nmb - 1 - k.wi) : k.wi;
+    if constexpr (WIN) {
+      // the block's first tile: the first one the block's first row (packed: its position) sees.  The chunk is narrowed to start there — tile0, shift and nk move
+      // together — so tile 0 of everything below (the two prefetched tiles, the loop, the buffer rotation, the contiguous descriptors' base) is that tile
+      int t_first = k.mb * BM;
+      if constexpr (PACK) t_first = fd_div(t_first, KvcPackView<PACK>::of(p).pk_fd_g);
+      const int c = t_first + k.shift - KvcWinView<WIN>::of(p).win_left;
+      const int j0 = c > 0 ? c >> 6 : 0;
+      k.tile0 += j0;
+      k.shift -= j0 * BN;
+      k.nk = k.nk > j0 * BN ? k.nk - j0 * BN : 0;
+    }
     int kv_end = k.nk;
     if (CAUSAL) {
       int lim = k.mb * BM + BM + k.shift;                        // one past the last key any row of the block sees
@@ -402,13 +426,22 @@
 
     const int shift = cur.shift;
     const int wave_last_tile = CAUSAL ? ((wave_t1 + shift) >= 0 ? (wave_t1 + shift) / BN : -1) : (nt - 1);
+    // windowed form: the first tile the wave's first row sees (the tiles in front of it are left of every row's window), and the window's reach
+    int wave_first_tile = 0, left = 0;
+    if constexpr (WIN) {
+      left = KvcWinView<WIN>::of(p).win_left;
+      const int c = wave_t0 + shift - left;
+      wave_first_tile = c > 0 ? c >> 6 : 0;
+    }
 
     auto tile_body = [&](int j, int buf) {
       // tile j+2 goes into the buffer tile j-1 just vacated
       const bool more = (j + PD < nt) && !(AB & AB_NOSTAGE);
       if (more) dma_issue(cur, j + PD, (buf + PD) % NBUF);
 
-      if (j <= wave_last_tile) {
+      bool mine = j <= wave_last_tile;
+      if constexpr (WIN) mine = mine && j >= wave_first_tile;
+      if (mine) {
         const char* kb = kl + buf * TILE_BYTES;
         const char* vb = vl + buf * TILE_BYTES;
 
@@ -491,17 +524,29 @@
         const int key0 = j * BN;
         bool need_mask = (key0 + BN > cur.nk);
         if (CAUSAL) need_mask = need_mask || (key0 + BN - 1 > wave_t0 + shift);
+        if constexpr (WIN) need_mask = need_mask || (key0 < wave_t1 + shift - left);     // some row of the wave has its window's left edge inside the tile or behind it
         if (need_mask) {
           int lim = cur.nk - 1;
           if (CAUSAL) { const int c = my_t + shift; lim = c < lim ? c : lim; }
           lim -= key0 + 4 * hi;
+          if constexpr (WIN) {
+            const int llim = my_t + shift - left - (key0 + 4 * hi);                      // the first key of the tile this row sees
 #pragma unroll
-          for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int ko = 32 * t + (r & 3) + 8 * (r >> 2);
-              if (ko > lim) sacc[t][r] = -INFINITY;
-            }
+              for (int r = 0; r < 16; ++r) {
+                const int ko = 32 * t + (r & 3) + 8 * (r >> 2);
+                if (ko > lim || ko < llim) sacc[t][r] = -INFINITY;
+              }
+          } else {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const int ko = 32 * t + (r & 3) + 8 * (r >> 2);
+                if (ko > lim) sacc[t][r] = -INFINITY;
+              }
+          }
         }
 
         float mloc = sacc[0][0];

@@ -11,6 +11,9 @@
 #ifndef TFA_KVC_SCHED
 #define TFA_KVC_SCHED 0      // 1 (with TFA_KVC_VQ): the unit of the scheduled form (tfa_kvc8_inst_vq_sched_<dtype>_<W>, tfa_kvc8_inst_pack_vq_sched_<dtype>_<W>) — fwd_kernel_dma_kvc_vq over KvcSched<>
 #endif
+#ifndef TFA_KVC_WIN
+#define TFA_KVC_WIN 0        // 1 (with any of the above): the unit of the form's windowed form (tfa_kvc8_inst_win_*) — fwd_kernel_dma_kvc_win over KvcWindow<> of the form's arguments:
+#endif                       // the causal template only, the 16-bit direct output and the fp32 partials, no non-temporal twin
 #if TFA_KVC_SCHED && !TFA_KVC_VQ
 #error "the scheduled form is a form of the varlen-q form"
 #endif
@@ -20,12 +23,16 @@ namespace tfa {
 // the arguments of this unit's kernels: the form's struct, behind it the packed form's (TFA_KVC_PACK), behind both the varlen-q form's (TFA_KVC_VQ)
 using UnitBase = std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<Kvc8Args>, Kvc8Args>;
 using UnitVq = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
-using UnitArgs = std::conditional_t<TFA_KVC_SCHED != 0, KvcSched<UnitVq>, UnitVq>;     // ... and behind the three the scheduled form's (TFA_KVC_SCHED)
+using UnitForm = std::conditional_t<TFA_KVC_SCHED != 0, KvcSched<UnitVq>, UnitVq>;     // ... and behind the three the scheduled form's (TFA_KVC_SCHED)
+using UnitArgs = std::conditional_t<TFA_KVC_WIN != 0, KvcWindow<UnitForm>, UnitForm>;  // ... and behind them all the window's (TFA_KVC_WIN)
 
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 static hipError_t launch_kvc8_one(const UnitArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
   constexpr int lds = 4 * 64 * D * 2;                          // two K and two V tile buffers of DECODED (16-bit) tiles: the 16-bit form's size
-#if TFA_KVC_VQ
+#if TFA_KVC_WIN
+  static_assert(CAUSAL && !NT, "the windowed form: causal, no non-temporal twin");
+  auto kern = fwd_kernel_dma_kvc_win<T, D, F32OUT, UnitArgs>;
+#elif TFA_KVC_VQ
   auto kern = fwd_kernel_dma_kvc_vq<T, D, CAUSAL, F32OUT, NT, UnitArgs>;
 #elif TFA_KVC_PACK
   auto kern = fwd_kernel_dma_kvc8_pack<T, D, CAUSAL, F32OUT, NT>;
@@ -45,6 +52,12 @@ static hipError_t launch_kvc8_one(const UnitArgs& a_in, hipStream_t stream, Laun
   return hipGetLastError();
 }
 
+#if TFA_KVC_WIN
+template <>
+hipError_t launch_kvc_win<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
+  return f32out ? launch_kvc8_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc8_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry);
+}
+#else
 template <>
 #if TFA_KVC_VQ
 hipError_t launch_kvc_vq<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a,
@@ -58,5 +71,6 @@ hipError_t launch_kvc8<TFA_T, TFA_D>(const Kvc8Args& a,
   if (nt) return causal ? launch_kvc8_one<TFA_T, TFA_D, true, true, true>(a, s, g, dry) : launch_kvc8_one<TFA_T, TFA_D, false, true, true>(a, s, g, dry);
   return causal ? launch_kvc8_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc8_one<TFA_T, TFA_D, false, true, false>(a, s, g, dry);
 }
+#endif
 
 }  // namespace tfa

@@ -233,6 +233,17 @@ TFA_KVCVQ_UNITS(__bf16, 64) TFA_KVCVQ_UNITS(__bf16, 128) TFA_KVCVQ_UNITS(_Float1
 TFA_KVCSC_UNITS(__bf16, 64) TFA_KVCSC_UNITS(__bf16, 128) TFA_KVCSC_UNITS(_Float16, 64) TFA_KVCSC_UNITS(_Float16, 128)
 #undef TFA_KVCSC_UNITS
 #undef TFA_KVCSC_UNIT
+// ... and the windowed forms of all of them (tfa_fwd_kvcache_window; fwd_kernel_dma_kvc_win over KvcWindow<> of the form's struct): tfa_kvc_inst_win_* and tfa_kvc8_inst_win_* —
+// the same .inc files compiled with TFA_KVC_WIN besides the form's own defines.  Causal only; f32out: the fp32 partials of a split launch
+template <typename T, int D, typename Args>
+hipError_t launch_kvc_win(const Args& a, bool f32out, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVCW_UNIT(T, D, A) template <> hipError_t launch_kvc_win<T, D, KvcWindow<A>>(const KvcWindow<A>&, bool, hipStream_t, LaunchGeom*, bool);
+#define TFA_KVCW_FORMS(T, D, A) TFA_KVCW_UNIT(T, D, A) TFA_KVCW_UNIT(T, D, KvcVarlenQ<A>) TFA_KVCW_UNIT(T, D, KvcSched<KvcVarlenQ<A>>)
+#define TFA_KVCW_UNITS(T, D) TFA_KVCW_FORMS(T, D, KvcArgs) TFA_KVCW_FORMS(T, D, Kvc8Args) TFA_KVCW_FORMS(T, D, KvcPacked<KvcArgs>) TFA_KVCW_FORMS(T, D, KvcPacked<Kvc8Args>)
+TFA_KVCW_UNITS(__bf16, 64) TFA_KVCW_UNITS(__bf16, 128) TFA_KVCW_UNITS(_Float16, 64) TFA_KVCW_UNITS(_Float16, 128)
+#undef TFA_KVCW_UNITS
+#undef TFA_KVCW_FORMS
+#undef TFA_KVCW_UNIT
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

@@ -903,7 +903,7 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, scheduler_metadata=None,
-                            k_descale=None, v_descale=None):
+                            sliding_window=None, k_descale=None, v_descale=None):
     """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
 
     ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
@@ -949,15 +949,34 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     ``cu_seqlens_q``: a list that does not belong to the batch gives unspecified or unwritten rows and never an access outside the tensors.  Refused before any
     launch: given without ``cu_seqlens_q`` (ValueError), a non-tensor (TypeError), not int32 / not on q's device / not contiguous, or a ``numel`` other than
     tfa_kvcache_varlen_schedule_size for this call (ValueError).  None (the default): the call is exactly what it was.
-    Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes,
-    fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
+    ``sliding_window`` (keyword-only; tfa_fwd_kvcache_window): the model configs' sliding window over the cache — a host integer w >= 1, the row's own key included,
+    with ``causal=True`` required.  Key j is visible to row t of sequence b iff t + shift_b - (w - 1) <= j <= t + shift_b and 0 <= j < len_b, shift_b = len_b - nq_b
+    with len_b and nq_b clamped as above (Nq in the 4-D form): FlashAttention's ``window_size=(w - 1, 0)``.  A row that sees no key gives out = 0, lse = +inf.  With
+    lo_b = max(0, shift_b - (w - 1)) and lo64_b = lo_b & ~63, the chunks of ``num_splits`` are cut from [lo64_b, len_b), and the kernel loads no block-table entry of a
+    page that ends at or before lo64_b and no K/V byte in front of key lo64_b — an engine may free those pages; their table entries may hold anything.  The keys
+    from lo64_b on must stay finite (a visited tile's keys left of a row's window are masked; P = 0 times a NaN V row is NaN).  Both layouts, ``scheduler_metadata``
+    (``get_scheduler_metadata`` does not learn about the window), paged / contiguous / fp8 caches, ``pack_gqa``, ``k`` / ``v`` appended first, no host
+    synchronisation and graph capture: as without it; at Nq == 1 the default and ``pack_gqa=True`` still stream K / V once per K/V head.  ``num_splits=0`` asks
+    tfa_fwd_kvcache_window_suggest_splits (the window's reach stands in for the lengths).  With w - 1 >= the capacity the window reaches every key a row can see and the
+    call is the plain causal one, through its entry points.  None (the default): the call is exactly what it was.  Refused before any launch: a tensor or
+    non-integer (TypeError), w < 1 (ValueError), ``causal=False`` (ValueError).
+    Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size (``sliding_window`` is this call's
+    window), softcap, alibi_slopes, fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
     name = "flash_attn_with_kvcache"
     for arg, val in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad),
                      ("alibi_slopes", alibi_slopes)):
         if val is not None:
             raise NotImplementedError(f"{name}: {arg} is not implemented in the K/V-cache path")
     if tuple(int(w) for w in window_size) != (-1, -1):
-        raise NotImplementedError(f"{name}: window_size is not implemented in the K/V-cache path (got {tuple(window_size)})")
+        raise NotImplementedError(f"{name}: window_size is not implemented in the K/V-cache path (got {tuple(window_size)}); the window over a cache is "
+                                  f"sliding_window=w (w tokens, the row's own included: window_size=(w - 1, 0)) with causal=True")
+    if sliding_window is not None:
+        if isinstance(sliding_window, (bool, torch.Tensor)) or not isinstance(sliding_window, int):
+            raise TypeError(f"{name}: sliding_window must be a host int (got {type(sliding_window).__name__})")
+        if sliding_window < 1:
+            raise ValueError(f"{name}: sliding_window must be >= 1 (w tokens, the row's own included; got {sliding_window})")
+        if not causal:
+            raise ValueError(f"{name}: sliding_window needs causal=True (a window without causal is not implemented)")
     if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
         raise NotImplementedError(f"{name}: softcap is not implemented in the K/V-cache path")
     if cu_seqlens_q is None and max_seqlen_q is not None:
@@ -966,7 +985,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise ValueError(f"{name}: scheduler_metadata belongs to cu_seqlens_q (packed (total_q, H, D) query rows), which was not given")
     if cu_seqlens_q is not None:
         return _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse,
-                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata)
+                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata, sliding_window)
     for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{name}: {n} must be a 4-D tensor")
@@ -1052,6 +1071,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     dense = torch.empty((B, H, Nq, D), dtype=q.dtype, device=q.device)            # what the merge writes; one chunk: the kernel writes it the same way
     p = _kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal)
     pack = None if pack_gqa is None else (_lib.TFA_PACK_GQA_ON if pack_gqa else _lib.TFA_PACK_GQA_OFF)   # None: the entry points without the argument
+    left = _window_left(sliding_window, capacity)
+    if left is not None:
+        _kvcache_window_call(L, p, None, k_descale, v_descale, fp8, _lib.TFA_PACK_GQA_AUTO if pack is None else pack, left, num_splits, None, q.device)
+        out = dense.transpose(1, 2)
+        return (out, lse) if return_softmax_lse else out
     if num_splits == 0:
         num_splits = max(1, int(L.tfa_fwd_kvcache_suggest_splits(C.byref(p)) if pack is None else L.tfa_fwd_kvcache_pack_suggest_splits(C.byref(p), pack)))
     p8 = None
@@ -1085,7 +1109,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
 
 
 def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse, pack_gqa,
-                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata=None):
+                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata=None, sliding_window=None):
     """``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=)`` (tfa_fwd_kvcache_varlen; with ``scheduler_metadata`` tfa_fwd_kvcache_varlen_sched): the checks of the
     packed form, then the calls.  Every refusal comes before any launch."""
     name = "flash_attn_with_kvcache"
@@ -1209,6 +1233,11 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
     vq.cu_seqlens_q = cu_seqlens_q.data_ptr()
     vq.max_seqlen_q, vq.total_q = int(max_seqlen_q), total_q
     pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
+    left = _window_left(sliding_window, capacity)
+    if left is not None:
+        _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, q.device)
+        out = dense.transpose(0, 1)
+        return (out, lse) if return_softmax_lse else out
     if num_splits == 0:
         num_splits = max(1, int(L.tfa_fwd_kvcache_varlen_suggest_splits(C.byref(p), C.byref(vq), pack)))
     p8 = None
@@ -1233,6 +1262,38 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
             _lib.check(L.tfa_fwd_kvcache_varlen(C.byref(p), C.byref(vq), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
     out = dense.transpose(0, 1)
     return (out, lse) if return_softmax_lse else out
+
+
+def _window_left(sliding_window, capacity):
+    """The ``window_left`` of tfa_fwd_kvcache_window for a checked ``sliding_window``, or None where the plain causal entry points run: no window, or one that
+    reaches every key a row can see (w - 1 >= capacity — the host knows it)."""
+    if sliding_window is None or sliding_window - 1 >= capacity:
+        return None
+    return sliding_window - 1
+
+
+def _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, device):
+    """The one dispatch to tfa_fwd_kvcache_window, from the 4-D (``vq`` None) and the packed-q host paths: split count, fp8 block, workspace, launch."""
+    pv = C.byref(vq) if vq is not None else None
+    if num_splits == 0:
+        num_splits = max(1, int(L.tfa_fwd_kvcache_window_suggest_splits(C.byref(p), pv, pack, left)))
+    p8 = None
+    if fp8:
+        p8 = _lib.TfaKvcacheFp8()
+        p8.format = _lib.TFA_KV_E4M3
+        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
+            if t is not None:
+                setattr(p8, ptr, t.data_ptr())
+                strides[0], strides[1] = t.stride(0), t.stride(1)
+    q8 = C.byref(p8) if fp8 else None
+    need = L.tfa_fwd_kvcache_window_workspace(C.byref(p), pv, q8, pack, left, num_splits)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty((int(need),), dtype=torch.float32, device=device) if need > 0 else None
+    meta = C.c_void_p(scheduler_metadata.data_ptr()) if scheduler_metadata is not None else None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.tfa_fwd_kvcache_window(C.byref(p), pv, q8, pack, left, num_splits, meta, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
 
 
 def _scheduler_metadata_size(name, B, H, Hk, max_seqlen_q, total_q, pack_gqa, causal):
