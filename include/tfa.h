@@ -148,6 +148,24 @@ typedef struct tfa_fwd_params {
  *                                                              + u * (5 * s + 4) + u * |lse| — derived term by term from the kernel body and tfa_merge
  *                                                              (tests/kvcache_ref.py: lse_bound); both asserted element by element in
  *                                                              tests/test_kvcache_fwd_bounds_gpu.py, proved to fit and to bite in tests/test_kvcache_bounds_cpu.py
+ *   the prefill forward family (tfa_fwd by kernel variant, its _local / _alibi / _softcap / _bias forms, tfa_fwd_varlen and its forms, tfa_fwd_varlen_paged,
+ *   tfa_fwd_splitkv with any split count), 16-bit output vs the exact result:
+ *                                                              |d| <= eps16 * A + 1e-6 + half an ulp16 of the result — the fp32-output bound plus the ONE
+ *                                                              rounding of O (partials and tfa_merge are fp32), on EVERY element; the fp32 output: the
+ *                                                              bound above, on every element.  It holds on rows whose dominant key lies outside their
+ *                                                              first 64-key tile under TFA_RULE_FIRST_TILE too, with and without the 2^40 re-base: asserted on
+ *                                                              the main instantiations of variants 30, 32, 36 and 37 (there the kernels use all of it:
+ *                                                              0.96-0.995 measured and emulated, against 0.5 under the other rules)
+ *   the prefill forward family, LSE (u = 2^-24, T = max_j scale * sum_d |q_d| |k_jd| + slope * |i + shift - j| + |bias_ij|, n keys,
+ *   R = 1 + floor(T / (20 ln 2))):
+ *                                                              |d| <= u * ((D + 15 + 2 [slopes] + 2 [bias]) * T + R * (T + ln n) + 11 * ceil(n / 64)
+ *                                                              + 3 ln n + 13 + 16 * softcap) + 2^-22 * |lse|, merged over s parts + u * (5 * s + 4) + u * |lse|
+ *                                                              — derived term by term from the il / x4 tile loops and their epilogue, the LDS-DMA body and
+ *                                                              tfa_merge (tests/fwd_ref.py: lse_bound); a worst-case sum: 0.04-0.9 of 1e-4 up to D = 136,
+ *                                                              looser at D = 256 and where T is large (steep slopes, saturated caps, peaked rows), so the
+ *                                                              1e-4 bar stays asserted next to it.  All asserted element by element
+ *                                                              in tests/test_fwd_bounds_gpu.py on inputs that put weight on the keys where indexing goes
+ *                                                              wrong, proved to fit and to bite in tests/test_fwd_bounds_cpu.py
  *   default kernels (TFA_RULE_LAZY / TFA_RULE_FIRST_TILE), fp32 output vs the reference's tile loop restated with THEIR rounding points:
  *                                                              |d| <= 1e-3 * |ref| + 1e-4 * A  (<= 1e-4 of the elements may flip one rounding of P)
  *   TFA_FWD_EXACT_MAX, fp32 output vs the reference's own tile loop (main_torch_only.py:160-270), element by element:
