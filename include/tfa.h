@@ -920,6 +920,38 @@ int tfa_fwd_kvcache_window_plan(const tfa_kvcache_params* p, const tfa_kvcache_v
 long long tfa_fwd_kvcache_window_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits);
 int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int window_left);
 
+/* ---- a TREE MASK over the step's new keys (the verification step of a speculative token tree: EAGLE, Medusa, SpecInfer-style drafts) ---------------------------------
+ * One entry point for every form above, as tfa_fwd_kvcache_window: vq == NULL is the 4-D call (k_new / v_new appended first), vq != NULL the packed-q call, metadata !=
+ * NULL its scheduled form (needs vq); q8 != NULL an e4m3 cache.  p->is_causal must be set.
+ * Definition, for row t of sequence b, with len_b and nq_b clamped exactly as the underlying form clamps them and base_b = len_b - nq_b (its shift_b): key j is visible iff
+ *   (1) 0 <= j < len_b,  (2) j <= t + base_b — the causal rule as it stands; trees are stored parents-first —  and  (3) with s = j - base_b:  s < 0, or s >= 64, or
+ *   bit s of the row's 64-bit word is set.  The mask only removes keys from what causal admits, and only among the first 64 new keys of a sequence: the committed
+ *   prefix is always seen, and so is a new key from the 64th on (sequences that bring more than 64 rows; all-ones words make such a sequence plain causal — a
+ *   chunked-prefill sequence beside tree-verify sequences in one batch).  Any sub-causal pattern is legal: it need not be closed under ancestry, and a row whose own
+ *   bit is clear is legal.  A row that sees no key gives out = 0, lse = +inf.  An all-ones word gives the plain causal call's bits for that row.
+ * The words: row t of sequence b reads mask[b * batch_stride + t * row_stride] in the 4-D form, mask[(q0_b + t) * row_stride] in the packed form (q0_b the
+ *   sequence's clamped first packed row; batch_stride is not read), strides in 8-byte elements, >= 0.  Read on the device only, by the lane that owns the row, two dwords once
+ *   per query block, through an index inside the rows the form itself trusts: no access outside B x Nq (total_q) words whatever the lengths hold.  No synchronisation;
+ *   a captured launch replayed after the words were overwritten in place computes with the new words.
+ * Finite keys: a masked new key is multiplied by P = 0, so the new keys must be finite (they were just appended).
+ * The mask removes no tile: chunks, tile bounds, grid, workspace and the split suggestion are the underlying form's (_tree_plan, _tree_workspace, _tree_suggest_splits
+ *   mirror the _window family argument for argument and return the form's numbers).  At most the two 64-key tiles per chunk that hold the new keys take the masked tile body
+ *   on the mask's account.
+ * GQA at Nq == 1 (vq == NULL): as tfa_fwd_kvcache_window — TFA_PACK_GQA_AUTO and _ON run position-major packed rows.
+ * Refused, nothing launched: a NULL tree or mask (TFA_ERR_NULL), a mask that is not 8-byte aligned (TFA_ERR_ALIGN), a negative stride (TFA_ERR_STRIDE), p->is_causal == 0,
+ *   metadata without vq (TFA_ERR_SHAPE); everything the underlying form refuses, with its codes.  No window: a tree mask with a sliding window is not implemented.
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcTree, behind the form's struct; fwd_kernel_dma_kvc_tree) — the causal template, the 16-bit direct output and the fp32 partials,
+ * units of their own (tfa_kvc_inst_tree_*, tfa_kvc8_inst_tree_*), so every other kernel keeps its instructions (profiles/kvcache_tree_isa_unchanged.txt). */
+typedef struct tfa_kvcache_tree {
+  const void* mask;              /* device, 8-byte words (int64): bit s of a row's word = the row sees the s-th new key of its sequence */
+  int64_t batch_stride;          /* words between sequences (4-D form; not read in the packed form) */
+  int64_t row_stride;            /* words between rows (packed form: between packed rows) */
+} tfa_kvcache_tree;
+int tfa_fwd_kvcache_tree(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq /* NULL: 4-D */, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, const tfa_kvcache_tree* tree, int splits, const int32_t* metadata /* NULL: unscheduled; needs vq */, float* workspace, void* stream);
+int tfa_fwd_kvcache_tree_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits, int scheduled, int* grid, int* block, int* lds_bytes);
+long long tfa_fwd_kvcache_tree_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits);
+int tfa_fwd_kvcache_tree_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, const tfa_kvcache_tree* tree);
+
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the
  * same launch (q and k of one step).  16-bit elements, any batch / head / row strides (elements), unit stride along D: a slice of a packed QKV projection works.

@@ -116,6 +116,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_window_plan",
     "tfa_fwd_kvcache_window_workspace",
     "tfa_fwd_kvcache_window_suggest_splits",
+    "tfa_fwd_kvcache_tree",
+    "tfa_fwd_kvcache_tree_plan",
+    "tfa_fwd_kvcache_tree_workspace",
+    "tfa_fwd_kvcache_tree_suggest_splits",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -345,6 +349,16 @@ class TfaKvcacheFp8(C.Structure):
         ("v_descale_stride", C.c_int64 * 2),
         ("format", C.c_int32),
         ("reserved_", C.c_int32),
+    ]
+
+
+class TfaKvcacheTree(C.Structure):
+    """struct tfa_kvcache_tree (include/tfa.h): the visibility words of tfa_fwd_kvcache_tree, handed over beside TfaKvcacheParams."""
+
+    _fields_ = [
+        ("mask", C.c_void_p),
+        ("batch_stride", C.c_int64),
+        ("row_stride", C.c_int64),
     ]
 
 
@@ -628,6 +642,16 @@ def lib():
     L.tfa_fwd_kvcache_window_workspace.argtypes = [PK, PV, P8, C.c_int, C.c_int, C.c_int]
     L.tfa_fwd_kvcache_window_suggest_splits.restype = C.c_int
     L.tfa_fwd_kvcache_window_suggest_splits.argtypes = [PK, PV, C.c_int, C.c_int]
+    # ... and a speculative tree's visibility words over the step's new keys, the same shape of entry point (the window's integer replaced by the tfa_kvcache_tree)
+    PT = C.POINTER(TfaKvcacheTree)
+    L.tfa_fwd_kvcache_tree.restype = C.c_int
+    L.tfa_fwd_kvcache_tree.argtypes = [PK, PV, P8, C.c_int, PT, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_tree_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_tree_plan.argtypes = [PK, PV, P8, C.c_int, PT, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_tree_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_tree_workspace.argtypes = [PK, PV, P8, C.c_int, PT, C.c_int]
+    L.tfa_fwd_kvcache_tree_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_tree_suggest_splits.argtypes = [PK, PV, C.c_int, PT]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

@@ -817,11 +817,12 @@ static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8
 // pack: TFA_PACK_GQA_AUTO — what tfa_fwd_kvcache runs, ON / OFF — tfa_fwd_kvcache_pack's choices
 // win_left >= 0: the windowed form (tfa_fwd_kvcache_window) — the same checks, chunks and workspace; causal only; Nq == 1 packs position-major like Nq > 1
 static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry,
-                       int win_left = -1) {
+                       int win_left = -1, const tfa_kvcache_tree* tree = nullptr) {
   int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   const bool win = win_left >= 0;
-  if (win && !p->is_causal) return TFA_ERR_SHAPE;
+  const bool tr = tree != nullptr;                         // the tree form (tfa_fwd_kvcache_tree): the same checks, chunks, geometry and workspace; causal only; packs as the windowed form
+  if ((win || tr) && !p->is_causal) return TFA_ERR_SHAPE;
   if (!p->q || !p->out) return TFA_ERR_NULL;
   if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
   if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
@@ -856,7 +857,7 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   {
     tfa_fwd_params fp;
     st = TFA_ERR_SHAPE;
-    if (!win && pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
+    if (!win && !tr && pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
       st = validate(&fp, &a, tfa::kSplitVariant);
       if (st == TFA_OK) f = fp;
     }
@@ -866,8 +867,8 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   tfa::KvcPacked<tfa::Kvc8Args> ka;                         // (the 16-bit launch takes its KvcArgs base; the unpacked launches theirs, without the packed form's tail)
   memset(&ka, 0, sizeof(ka));
   // several rows per sequence, packed: the validated problem is the caller's own — its packed description replaces the geometry only
-  // (windowed, one row per sequence: the heads-as-rows packing above is a non-causal problem, which has no window — the position-major one serves it, t = row / G = 0)
-  const bool pack_pos = kvcache_packs_positions(p, pack) || (win && pack != TFA_PACK_GQA_OFF && kvcache_packs(p));
+  // (windowed or tree, one row per sequence: the heads-as-rows packing above is a non-causal problem, which has neither — the position-major one serves it, t = row / G = 0)
+  const bool pack_pos = kvcache_packs_positions(p, pack) || ((win || tr) && pack != TFA_PACK_GQA_OFF && kvcache_packs(p));
   const bool packed_rows = pack_pos && kvcache_pack_args(p, f.is_causal != 0, ns > 1 ? 4 : 2, &a, &ka);
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
@@ -901,8 +902,8 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
   }
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
     using T = typename decltype(k)::T;
-    if (win) {
-      // the arguments of the instantiation that runs: the form's struct with the window behind it
+    if (win || tr) {
+      // the arguments of the instantiation that runs: the form's struct with the window or the tree behind it
       auto run = [&](auto* args) {
         using A = std::remove_pointer_t<decltype(args)>;
         A v;
@@ -910,9 +911,18 @@ static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, i
         static_cast<tfa::KvcArgs&>(v) = ka;
         if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
         if constexpr (tfa::KvcPack<const A>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
-        v.win_left = win_left < p->capacity ? win_left : p->capacity;
-        return tfa::launch_kvc_win<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
+        if constexpr (tfa::KvcTr<const A>::value) {
+          v.tree = static_cast<const unsigned long long*>(tree->mask); v.tree_bs = tree->batch_stride; v.tree_rs = tree->row_stride;
+          return tfa::launch_kvc_tree<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
+        } else {
+          v.win_left = win_left < p->capacity ? win_left : p->capacity;
+          return tfa::launch_kvc_win<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
+        }
       };
+      if (tr) {
+        if (packed_rows) return q8 ? run((tfa::KvcTree<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcTree<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
+        return q8 ? run((tfa::KvcTree<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcTree<tfa::KvcArgs>*)nullptr);
+      }
       if (packed_rows) return q8 ? run((tfa::KvcWindow<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcWindow<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
       return q8 ? run((tfa::KvcWindow<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcWindow<tfa::KvcArgs>*)nullptr);
     }
@@ -1015,10 +1025,12 @@ static_assert(tfa::SCHED_HDR == tfa::SCHEDULE_HDR, "one header size for the kern
 
 // sched: the scheduled form (tfa_fwd_kvcache_varlen_sched) — meta is the list tfa_kvcache_varlen_schedule built (NULL allowed in a dry run)
 static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream,
-                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false, int win_left = -1) {
+                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false, int win_left = -1,
+                          const tfa_kvcache_tree* tree = nullptr) {
   if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
   const bool win = win_left >= 0;                            // the windowed form (tfa_fwd_kvcache_window): the same checks, geometry and workspace; causal only
-  if (win && !p->is_causal) return TFA_ERR_SHAPE;
+  const bool tr = tree != nullptr;                           // the tree form (tfa_fwd_kvcache_tree): likewise
+  if ((win || tr) && !p->is_causal) return TFA_ERR_SHAPE;
   if (sched && !dry) {
     if (!meta) return TFA_ERR_NULL;
     if ((uintptr_t)meta & 7) return TFA_ERR_ALIGN;
@@ -1151,6 +1163,13 @@ static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_
         static_cast<A&>(w) = v;
         w.win_left = win_left < p->capacity ? win_left : p->capacity;
         return tfa::launch_kvc_win<T, W, tfa::KvcWindow<A>>(w, ns > 1, s, geom, dry);
+      }
+      if (tr) {
+        tfa::KvcTree<A> w;
+        memset(&w, 0, sizeof(w));
+        static_cast<A&>(w) = v;
+        w.tree = static_cast<const unsigned long long*>(tree->mask); w.tree_bs = 0; w.tree_rs = tree->row_stride;
+        return tfa::launch_kvc_tree<T, W, tfa::KvcTree<A>>(w, ns > 1, s, geom, dry);
       }
       return tfa::launch_kvc_vq<T, W, A>(v, causal, ns > 1, nt, s, geom, dry);
     };
@@ -1303,6 +1322,44 @@ int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa
   tfa_kvcache_params w = *p;
   if (reach < w.capacity) w.capacity = (int)reach;
   return vq ? tfa_fwd_kvcache_varlen_suggest_splits(&w, vq, pack_gqa) : kvcache_suggest_splits(&w, pack_gqa);
+}
+
+// ---- the tree form (tfa.h: tfa_fwd_kvcache_tree): one entry point over the same three host paths; the mask removes no tile, so everything but the kernel is the form's --------
+static int kvcache_tree_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, const tfa_kvcache_tree* tree, int splits,
+                            const int32_t* meta, bool sched, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+  if (!p || !tree || !tree->mask) return TFA_ERR_NULL;
+  if (!p->is_causal || (sched && !vq)) return TFA_ERR_SHAPE;
+  if ((uintptr_t)tree->mask & 7) return TFA_ERR_ALIGN;
+  if (tree->row_stride < 0 || (!vq && tree->batch_stride < 0)) return TFA_ERR_STRIDE;
+  if (vq) return kvcache_vq_run(p, vq, q8, pack, splits, workspace, stream, geom, dry, meta, sched, -1, tree);
+  return kvcache_run(p, q8, pack, splits, workspace, stream, geom, dry, -1, tree);
+}
+int tfa_fwd_kvcache_tree(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits,
+                         const int32_t* metadata, float* workspace, void* stream) {
+  return kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, metadata, metadata != nullptr, workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_tree_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits,
+                              int scheduled, int* grid, int* block, int* lds_bytes) {
+  tfa::LaunchGeom g{0, 0, 0};
+  const int st = kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, nullptr, scheduled != 0, nullptr, nullptr, &g, true);
+  if (st != TFA_OK) return st;
+  if (grid) *grid = g.grid;
+  if (block) *block = g.block;
+  if (lds_bytes) *lds_bytes = g.lds;
+  return TFA_OK;
+}
+long long tfa_fwd_kvcache_tree_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree,
+                                         int splits) {
+  const int st = kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, nullptr, false, nullptr, nullptr, nullptr, true);
+  if (st != TFA_OK) return st;
+  const int ns = kvcache_chunks(p, splits);
+  if (ns <= 1) return 0;
+  return vq ? (long long)ns * p->H * vq->total_q * (p->D + 1) : (long long)ns * p->B * p->H * p->Nq * (p->D + 1);
+}
+int tfa_fwd_kvcache_tree_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, const tfa_kvcache_tree* tree) {
+  (void)tree;                                              // the underlying form's rule: the mask removes no tile
+  if (!p) return 1;
+  return vq ? tfa_fwd_kvcache_varlen_suggest_splits(p, vq, pack_gqa) : kvcache_suggest_splits(p, pack_gqa);
 }
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {

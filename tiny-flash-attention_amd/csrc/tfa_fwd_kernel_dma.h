@@ -229,6 +229,29 @@ template <bool WIN>
 struct KvcWinView {
   template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
 };
+// The tree form of the KV-cache form (tfa_fwd_kvcache_tree; the verification step of a speculative token tree): on the causal template, with s = j - shift_b the
+// index of key j among the step's new keys, key j is visible to the row at position t iff the causal rule admits it and (s < 0 or s >= 64 or bit s of the row's
+// 64-bit word is set).  The word of row t is tree[b * tree_bs + t * tree_rs] (varlen-q: tree[(q0_b + t) * tree_rs]), loaded once per query block by the lane that
+// owns the row (packed: t = row / G) — two dwords, kept in two VGPRs; a row outside the sequence takes all ones and loads nothing.  In the body's coordinates
+// shift_b is Blk::shift, which decode() has already reduced by the chunk's first key: the new keys are [shift, shift + 64) in every chunk of every split, and
+// nothing is carried across a chunk seam.  The mask removes no tile: chunks, tile bounds, grid and workspace are the underlying form's.  Only the (at most two)
+// tiles that meet [shift, shift + 64) take the masked body on the mask's account.  Masked new keys are multiplied by P = 0, so they must be finite.  The
+// arguments ride BEHIND the form's struct — any of the twelve above — for KvcPacked's reason.
+template <typename Base>
+struct KvcTree : Base {
+  using tree_base = Base;
+  const unsigned long long* tree;   // device, 8-byte words: bit s of a row's word = the row sees the s-th new key of its sequence
+  long long tree_bs, tree_rs;       // words between sequences (unused in the varlen-q form) and between rows
+};
+template <typename B> struct KvcPack<const KvcTree<B>> : KvcPack<const B> {};
+template <typename B> struct KvcVq<const KvcTree<B>> : KvcVq<const B> {};
+template <typename B> struct KvcSc<const KvcTree<B>> : KvcSc<const B> {};
+template <typename A> struct KvcTr { static constexpr bool value = false; };
+template <typename B> struct KvcTr<const KvcTree<B>> { static constexpr bool value = true; };
+template <bool TREE>
+struct KvcTreeView {
+  template <typename A> static __device__ __forceinline__ const A& of(const A& a) { return a; }
+};
 template <bool KV8, typename T> struct KvElem { using type = T; };
 template <typename T> struct KvElem<true, T> { using type = unsigned char; };
 
@@ -313,6 +336,15 @@ __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_vq(const Args p) {
 // (a window's range is small)
 template <typename T, int D, bool F32OUT, typename Args>
 __global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_win(const Args p) {
+  constexpr bool CAUSAL = true;
+  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0);
+#include "tfa_fwd_kernel_dma_body.inc"
+}
+
+// The tree forms of all twelve (a speculative tree's visibility words over the step's new keys: KvcTree above).  Args: KvcTree<> of any form's struct; causal only,
+// no non-temporal twin
+template <typename T, int D, bool F32OUT, typename Args>
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_tree(const Args p) {
   constexpr bool CAUSAL = true;
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0);
 #include "tfa_fwd_kernel_dma_body.inc"

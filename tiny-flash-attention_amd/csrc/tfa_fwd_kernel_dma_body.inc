@@ -13,6 +13,9 @@
   constexpr bool SCHED = VQ && KvcSc<decltype(p)>::value;
   // the windowed form of any of those (KvcWindow: a sliding window of win_left keys in front of a row's own); its argument is read through KvcWinView<WIN>::of(p), as above
   constexpr bool WIN = KVC && KvcWin<decltype(p)>::value;
+  // the tree form of any of the KV-cache forms (KvcTree: one 64-bit visibility word per query row over the step's new keys); its arguments are read through
+  // KvcTreeView<TREE>::of(p), as above
+  constexpr bool TREE = KVC && KvcTr<decltype(p)>::value;
   constexpr int ES = KV8 ? 1 : 2;                  // bytes per K/V element in memory
   using KT = typename KvElem<KV8, T>::type;
   using X8 = typename E::x8;
@@ -33,6 +36,7 @@
   static_assert(!KVC || (!WIDE && AB == 0 && !(VF & (VF_PERSIST | VF_LDSEPI))), "the KV-cache form: 64 / 128 wide, one work item per workgroup");
   static_assert(!SCHED || !(VF & VF_PERSIST), "the scheduled form: one work item per workgroup (an item behind the list's end returns)");
   static_assert(!WIN || (CAUSAL && PAIR), "the windowed form: a form of the causal KV-cache kernel");
+  static_assert(!TREE || (CAUSAL && PAIR && !WIN), "the tree form: a form of the causal KV-cache kernel, without a window");
   static_assert(!KV8 || (KVC && NBUF == 2), "the e4m3 form: a form of the two-buffer KV-cache kernel (one tile staged in registers)");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -400,6 +404,17 @@
       wave_t1 = fd_div(wave_row0 + 31 < last_row ? wave_row0 + 31 : last_row, pp.pk_fd_g);
     }
 
+    // tree form: the row's visibility word over its sequence's new keys — two dwords by the lane that owns the row, once per block; a row outside the
+    // sequence loads nothing and sees what causal admits
+    unsigned long long tree_w = ~0ull;
+    if constexpr (TREE) {
+      const auto& pt = KvcTreeView<TREE>::of(p);
+      int tree_nq = KvcView<KVC>::of(p).nq_pos;
+      long long tree_at = (long long)cur.bt_row * pt.tree_bs;
+      if constexpr (VQ) { tree_nq = cur_nq; tree_at = (long long)cur_q0 * pt.tree_rs; }
+      if (my_t < tree_nq) tree_w = pt.tree[tree_at + (long long)my_t * pt.tree_rs];
+    }
+
     f32x16 oacc[WIDE ? 1 : DT];
     if constexpr (WIDE) g_zero();
     else {
@@ -525,6 +540,7 @@
         bool need_mask = (key0 + BN > cur.nk);
         if (CAUSAL) need_mask = need_mask || (key0 + BN - 1 > wave_t0 + shift);
         if constexpr (WIN) need_mask = need_mask || (key0 < wave_t1 + shift - left);     // some row of the wave has its window's left edge inside the tile or behind it
+        if constexpr (TREE) need_mask = need_mask || (key0 < shift + 64 && key0 + BN > shift);   // the tile holds new keys: [shift, shift + 64) in every chunk
         if (need_mask) {
           int lim = cur.nk - 1;
           if (CAUSAL) { const int c = my_t + shift; lim = c < lim ? c : lim; }
@@ -537,6 +553,21 @@
               for (int r = 0; r < 16; ++r) {
                 const int ko = 32 * t + (r & 3) + 8 * (r >> 2);
                 if (ko > lim || ko < llim) sacc[t][r] = -INFINITY;
+              }
+          } else if constexpr (TREE) {
+            // bit ko of vis: this row sees key key0 + 4 * hi + ko — the row's word moved from the new keys' origin to this lane's, ones in front of the
+            // first new key and from the 64th on (a tile that holds no new key: all ones)
+            const int off = shift - (key0 + 4 * hi);
+            unsigned long long vis = ~0ull;
+            if (off >= 0 && off < 64) vis = (tree_w << off) | ((1ull << off) - 1ull);
+            else if (off < 0 && off > -64) vis = (tree_w >> -off) | ~(~0ull >> -off);
+            const unsigned vis_lo = (unsigned)vis, vis_hi = (unsigned)(vis >> 32);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const int ko = 32 * t + (r & 3) + 8 * (r >> 2);
+                if (ko > lim || !((t ? vis_hi : vis_lo) & (1u << (ko & 31)))) sacc[t][r] = -INFINITY;
               }
           } else {
 #pragma unroll

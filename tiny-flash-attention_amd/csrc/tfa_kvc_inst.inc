@@ -14,6 +14,12 @@
 #ifndef TFA_KVC_WIN
 #define TFA_KVC_WIN 0        // 1 (with any of the above): the unit of the form's windowed form (tfa_kvc_inst_win_*) — fwd_kernel_dma_kvc_win over KvcWindow<> of the form's arguments:
 #endif                       // the causal template only, the 16-bit direct output and the fp32 partials, no non-temporal twin
+#ifndef TFA_KVC_TREE
+#define TFA_KVC_TREE 0       // 1 (with any of the forms, not with TFA_KVC_WIN): the unit of the form's tree form (tfa_kvc_inst_tree_*) — fwd_kernel_dma_kvc_tree over KvcTree<> of the
+#endif                       // form's arguments: the causal template only, the 16-bit direct output and the fp32 partials, no non-temporal twin
+#if TFA_KVC_TREE && TFA_KVC_WIN
+#error "the tree form has no windowed form"
+#endif
 #if TFA_KVC_SCHED && !TFA_KVC_VQ
 #error "the scheduled form is a form of the varlen-q form"
 #endif
@@ -24,7 +30,8 @@ namespace tfa {
 using UnitBase = std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<KvcArgs>, KvcArgs>;
 using UnitVq = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
 using UnitForm = std::conditional_t<TFA_KVC_SCHED != 0, KvcSched<UnitVq>, UnitVq>;     // ... and behind the three the scheduled form's (TFA_KVC_SCHED)
-using UnitArgs = std::conditional_t<TFA_KVC_WIN != 0, KvcWindow<UnitForm>, UnitForm>;  // ... and behind them all the window's (TFA_KVC_WIN)
+using UnitWin = std::conditional_t<TFA_KVC_WIN != 0, KvcWindow<UnitForm>, UnitForm>;   // ... and behind them all the window's (TFA_KVC_WIN)
+using UnitArgs = std::conditional_t<TFA_KVC_TREE != 0, KvcTree<UnitWin>, UnitWin>;     // ... or the tree's (TFA_KVC_TREE)
 
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
@@ -32,6 +39,9 @@ static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, Launc
 #if TFA_KVC_WIN
   static_assert(CAUSAL && !NT, "the windowed form: causal, no non-temporal twin");
   auto kern = fwd_kernel_dma_kvc_win<T, D, F32OUT, UnitArgs>;
+#elif TFA_KVC_TREE
+  static_assert(CAUSAL && !NT, "the tree form: causal, no non-temporal twin");
+  auto kern = fwd_kernel_dma_kvc_tree<T, D, F32OUT, UnitArgs>;
 #elif TFA_KVC_VQ
   auto kern = fwd_kernel_dma_kvc_vq<T, D, CAUSAL, F32OUT, NT, UnitArgs>;
 #elif TFA_KVC_PACK
@@ -55,6 +65,11 @@ static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, Launc
 #if TFA_KVC_WIN
 template <>
 hipError_t launch_kvc_win<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
+  return f32out ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry);
+}
+#elif TFA_KVC_TREE
+template <>
+hipError_t launch_kvc_tree<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
   return f32out ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry);
 }
 #else

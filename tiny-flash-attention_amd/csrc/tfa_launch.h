@@ -244,6 +244,17 @@ TFA_KVCW_UNITS(__bf16, 64) TFA_KVCW_UNITS(__bf16, 128) TFA_KVCW_UNITS(_Float16, 
 #undef TFA_KVCW_UNITS
 #undef TFA_KVCW_FORMS
 #undef TFA_KVCW_UNIT
+// ... and the tree forms of all of them (tfa_fwd_kvcache_tree; fwd_kernel_dma_kvc_tree over KvcTree<> of the form's struct): tfa_kvc_inst_tree_* and tfa_kvc8_inst_tree_* —
+// the same .inc files compiled with TFA_KVC_TREE besides the form's own defines.  Causal only; f32out: the fp32 partials of a split launch
+template <typename T, int D, typename Args>
+hipError_t launch_kvc_tree(const Args& a, bool f32out, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVCT_UNIT(T, D, A) template <> hipError_t launch_kvc_tree<T, D, KvcTree<A>>(const KvcTree<A>&, bool, hipStream_t, LaunchGeom*, bool);
+#define TFA_KVCT_FORMS(T, D, A) TFA_KVCT_UNIT(T, D, A) TFA_KVCT_UNIT(T, D, KvcVarlenQ<A>) TFA_KVCT_UNIT(T, D, KvcSched<KvcVarlenQ<A>>)
+#define TFA_KVCT_UNITS(T, D) TFA_KVCT_FORMS(T, D, KvcArgs) TFA_KVCT_FORMS(T, D, Kvc8Args) TFA_KVCT_FORMS(T, D, KvcPacked<KvcArgs>) TFA_KVCT_FORMS(T, D, KvcPacked<Kvc8Args>)
+TFA_KVCT_UNITS(__bf16, 64) TFA_KVCT_UNITS(__bf16, 128) TFA_KVCT_UNITS(_Float16, 64) TFA_KVCT_UNITS(_Float16, 128)
+#undef TFA_KVCT_UNITS
+#undef TFA_KVCT_FORMS
+#undef TFA_KVCT_UNIT
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

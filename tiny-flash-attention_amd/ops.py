@@ -902,8 +902,8 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
-                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, scheduler_metadata=None,
-                            sliding_window=None, k_descale=None, v_descale=None):
+                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, tree_mask=None,
+                            scheduler_metadata=None, sliding_window=None, k_descale=None, v_descale=None):
     """FlashAttention-2's ``flash_attn_with_kvcache`` (tfa_fwd_kvcache): one inference step over a K/V cache whose lengths live on the device.
 
     ``q`` (B, Nq, H, D); ``k_cache`` / ``v_cache`` (B, Nk_max, Hk, D) with any strides and unit stride along D, or paged (num_blocks, page_size, Hk, D)
@@ -960,6 +960,21 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     tfa_fwd_kvcache_window_suggest_splits (the window's reach stands in for the lengths).  With w - 1 >= the capacity the window reaches every key a row can see and the
     call is the plain causal one, through its entry points.  None (the default): the call is exactly what it was.  Refused before any launch: a tensor or
     non-integer (TypeError), w < 1 (ValueError), ``causal=False`` (ValueError).
+    ``tree_mask`` (keyword-only; tfa_fwd_kvcache_tree): the verification step of a speculative token tree (EAGLE, Medusa, SpecInfer-style drafts), with
+    ``causal=True`` required.  With base_b = len_b - nq_b (len_b and nq_b clamped as above, Nq in the 4-D form; the step's new keys are [base_b, len_b)), key j
+    is visible to row t of sequence b iff 0 <= j < len_b, j <= t + base_b (the causal rule as it stands: trees are stored parents-first) and, with s = j - base_b:
+    s < 0, or s >= 64, or bit s of ``tree_mask[b, t]`` is set.  The mask only removes keys from what ``causal`` admits, and only among the first 64 new keys of a
+    sequence; every row sees the whole committed prefix.  Any sub-causal pattern is legal — it need not be closed under ancestry, a row's own bit may be clear; a
+    row that sees no key gives out = 0, lse = +inf; an all-ones word (-1) is plain causal attention for that row, bit for bit.  4-D form: an int64 device tensor
+    (B, Nq) with any strides, or a ``torch.bool`` tensor (B, Nq, Nq), True = row t sees new key s, packed into the int64 form by elementwise device ops (no host
+    read); Nq <= 64.  Packed form (``cu_seqlens_q``): int64 (total_q,), one word per packed row; a sequence that brings more than 64 rows sees its new keys from
+    the 64th on causally (all-ones words on its rows: a chunked-prefill sequence beside tree-verify sequences).  The words are read on the device only: no
+    synchronisation, and a captured step replayed after the mask, the lengths and ``cu_seqlens_q`` were overwritten in place computes with the new values.  Masked
+    new keys are multiplied by P = 0 and must be finite (they were just appended).  Both layouts, ``scheduler_metadata`` (``get_scheduler_metadata`` does not learn
+    about the mask), paged / contiguous / fp8 caches, ``pack_gqa`` (at Nq == 1 the default and True run position-major packed rows), ``k`` / ``v`` appended first,
+    every ``num_splits`` (0 asks tfa_fwd_kvcache_tree_suggest_splits: the underlying form's rule — the mask removes no tile), ``return_softmax_lse``: as without it.
+    None (the default): the call is exactly what it was.  Refused before any launch: a non-tensor (TypeError); a dtype other than int64 / bool, a wrong shape or
+    device, Nq > 64 in the 4-D form, a bool mask in the packed form, ``causal=False``, ``tree_mask`` together with ``sliding_window`` (ValueError).
     Not implemented (refused by name before any launch): rotary_cos / rotary_sin, cache_batch_idx, cache_leftpad, window_size (``sliding_window`` is this call's
     window), softcap, alibi_slopes, fp32 inputs, head dims above 128, float8_e5m2 / float8_e4m3fnuz caches, an fp8 q / k / v."""
     name = "flash_attn_with_kvcache"
@@ -977,6 +992,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
             raise ValueError(f"{name}: sliding_window must be >= 1 (w tokens, the row's own included; got {sliding_window})")
         if not causal:
             raise ValueError(f"{name}: sliding_window needs causal=True (a window without causal is not implemented)")
+    if tree_mask is not None:
+        if not isinstance(tree_mask, torch.Tensor):
+            raise TypeError(f"{name}: tree_mask must be a tensor (got {type(tree_mask).__name__})")
+        if not causal:
+            raise ValueError(f"{name}: tree_mask needs causal=True (the mask removes keys from what causal admits)")
+        if sliding_window is not None:
+            raise ValueError(f"{name}: tree_mask together with sliding_window is not implemented")
     if isinstance(softcap, torch.Tensor) or float(softcap) != 0.0:
         raise NotImplementedError(f"{name}: softcap is not implemented in the K/V-cache path")
     if cu_seqlens_q is None and max_seqlen_q is not None:
@@ -985,7 +1007,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise ValueError(f"{name}: scheduler_metadata belongs to cu_seqlens_q (packed (total_q, H, D) query rows), which was not given")
     if cu_seqlens_q is not None:
         return _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse,
-                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata, sliding_window)
+                                                 pack_gqa, k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata, sliding_window, tree_mask)
     for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{name}: {n} must be a 4-D tensor")
@@ -1065,6 +1087,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
+    tree = _tree_words(name, tree_mask, q.device, B, Nq) if tree_mask is not None else None
 
     L = _lib.lib()
     lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device) if return_softmax_lse else None
@@ -1072,8 +1095,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     p = _kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal)
     pack = None if pack_gqa is None else (_lib.TFA_PACK_GQA_ON if pack_gqa else _lib.TFA_PACK_GQA_OFF)   # None: the entry points without the argument
     left = _window_left(sliding_window, capacity)
-    if left is not None:
-        _kvcache_window_call(L, p, None, k_descale, v_descale, fp8, _lib.TFA_PACK_GQA_AUTO if pack is None else pack, left, num_splits, None, q.device)
+    if left is not None or tree is not None:
+        _kvcache_window_call(L, p, None, k_descale, v_descale, fp8, _lib.TFA_PACK_GQA_AUTO if pack is None else pack, left, num_splits, None, q.device, tree)
         out = dense.transpose(1, 2)
         return (out, lse) if return_softmax_lse else out
     if num_splits == 0:
@@ -1109,7 +1132,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
 
 
 def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, block_table, softmax_scale, causal, num_splits, return_softmax_lse, pack_gqa,
-                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata=None, sliding_window=None):
+                                      k_descale, v_descale, cu_seqlens_q, max_seqlen_q, scheduler_metadata=None, sliding_window=None,
+                                      tree_mask=None):
     """``flash_attn_with_kvcache(cu_seqlens_q=, max_seqlen_q=)`` (tfa_fwd_kvcache_varlen; with ``scheduler_metadata`` tfa_fwd_kvcache_varlen_sched): the checks of the
     packed form, then the calls.  Every refusal comes before any launch."""
     name = "flash_attn_with_kvcache"
@@ -1202,6 +1226,7 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
         if scheduler_metadata.dtype != torch.int32 or scheduler_metadata.device != q.device or not scheduler_metadata.is_contiguous():
             raise ValueError(f"{name}: scheduler_metadata must be a contiguous int32 tensor on q's device (got {scheduler_metadata.dtype} on "
                              f"{scheduler_metadata.device})")
+    tree = _tree_words(name, tree_mask, q.device, None, total_q) if tree_mask is not None else None
 
     L = _lib.lib()
     if scheduler_metadata is not None:
@@ -1234,8 +1259,8 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
     vq.max_seqlen_q, vq.total_q = int(max_seqlen_q), total_q
     pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
     left = _window_left(sliding_window, capacity)
-    if left is not None:
-        _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, q.device)
+    if left is not None or tree is not None:
+        _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, q.device, tree)
         out = dense.transpose(0, 1)
         return (out, lse) if return_softmax_lse else out
     if num_splits == 0:
@@ -1272,11 +1297,42 @@ def _window_left(sliding_window, capacity):
     return sliding_window - 1
 
 
-def _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, device):
-    """The one dispatch to tfa_fwd_kvcache_window, from the 4-D (``vq`` None) and the packed-q host paths: split count, fp8 block, workspace, launch."""
+def _tree_words(name, tree_mask, device, B, rows):
+    """The int64 visibility words of a checked ``tree_mask``: (B, Nq) with its own strides in the 4-D form (``rows`` = Nq), (total_q,) in the packed form (``B``
+    None, ``rows`` = total_q).  A bool (B, Nq, Nq) mask is packed by elementwise ops on its device — word[b, t] = sum_s mask[b, t, s] << s, bit 63 the sign bit."""
+    if tree_mask.device != device:
+        raise ValueError(f"{name}: tree_mask must be on q's device (got {tree_mask.device})")
+    if B is None:
+        if tree_mask.dtype == torch.bool:
+            raise ValueError(f"{name}: with cu_seqlens_q, tree_mask is the int64 layout (total_q,) — one 64-bit word per packed row; a bool mask belongs to the 4-D form")
+        if tree_mask.dtype != torch.int64 or tuple(tree_mask.shape) != (rows,):
+            raise ValueError(f"{name}: with cu_seqlens_q, tree_mask must be an int64 tensor of shape ({rows},) (got {tree_mask.dtype} {tuple(tree_mask.shape)})")
+        return tree_mask
+    if rows > 64:
+        raise ValueError(f"{name}: tree_mask covers the first 64 new keys of a sequence: Nq <= 64 in the 4-D form (got {rows})")
+    if tree_mask.dtype == torch.bool:
+        if tuple(tree_mask.shape) != (B, rows, rows):
+            raise ValueError(f"{name}: a bool tree_mask must have shape ({B}, {rows}, {rows}) (got {tuple(tree_mask.shape)})")
+        bits = torch.arange(rows, dtype=torch.int64, device=tree_mask.device)
+        return torch.bitwise_left_shift(tree_mask.to(torch.int64), bits).sum(dim=-1)
+    if tree_mask.dtype != torch.int64 or tuple(tree_mask.shape) != (B, rows):
+        raise ValueError(f"{name}: tree_mask must be an int64 tensor of shape ({B}, {rows}) or a bool tensor of shape ({B}, {rows}, {rows}) "
+                         f"(got {tree_mask.dtype} {tuple(tree_mask.shape)})")
+    return tree_mask
+
+
+def _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, device, tree=None):
+    """The one dispatch to tfa_fwd_kvcache_window — or, with ``tree`` (the int64 words; ``left`` is then None), to tfa_fwd_kvcache_tree, whose arguments are the
+    same but for the window — from the 4-D (``vq`` None) and the packed-q host paths: split count, fp8 block, workspace, launch."""
     pv = C.byref(vq) if vq is not None else None
+    fam, rider = "tfa_fwd_kvcache_window", left
+    if tree is not None:
+        pt = _lib.TfaKvcacheTree()
+        pt.mask = tree.data_ptr()
+        pt.batch_stride, pt.row_stride = (tree.stride(0), tree.stride(1)) if tree.dim() == 2 else (0, tree.stride(0))
+        fam, rider = "tfa_fwd_kvcache_tree", C.byref(pt)
     if num_splits == 0:
-        num_splits = max(1, int(L.tfa_fwd_kvcache_window_suggest_splits(C.byref(p), pv, pack, left)))
+        num_splits = max(1, int(getattr(L, fam + "_suggest_splits")(C.byref(p), pv, pack, rider)))
     p8 = None
     if fp8:
         p8 = _lib.TfaKvcacheFp8()
@@ -1286,14 +1342,14 @@ def _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_sp
                 setattr(p8, ptr, t.data_ptr())
                 strides[0], strides[1] = t.stride(0), t.stride(1)
     q8 = C.byref(p8) if fp8 else None
-    need = L.tfa_fwd_kvcache_window_workspace(C.byref(p), pv, q8, pack, left, num_splits)
+    need = getattr(L, fam + "_workspace")(C.byref(p), pv, q8, pack, rider, num_splits)
     if need < 0:
         _lib.check(int(need))
     ws = torch.empty((int(need),), dtype=torch.float32, device=device) if need > 0 else None
     meta = C.c_void_p(scheduler_metadata.data_ptr()) if scheduler_metadata is not None else None
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(L.tfa_fwd_kvcache_window(C.byref(p), pv, q8, pack, left, num_splits, meta, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        _lib.check(getattr(L, fam)(C.byref(p), pv, q8, pack, rider, num_splits, meta, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
 
 
 def _scheduler_metadata_size(name, B, H, Hk, max_seqlen_q, total_q, pack_gqa, causal):
