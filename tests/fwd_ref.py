@@ -386,6 +386,28 @@ BY_ID = {c["id"]: c for c in CASES}
 assert len(BY_ID) == len(CASES), "case ids must be unique"
 
 
+def _bhnd_cases():
+    """The flat entry points tfa_fwd_bhnd / tfa_fwd_bhnd_f32out (tests/test_boundary_gpu.py) and the C host that calls them: contiguous (B,H,N,D), Hk = H,
+    Nq = Nk, automatic variant — the smallest shapes that cross the second 256-row block (N 320), a head dim below the kernel's width (D 40, one row into the
+    second block) and the 256-wide kernel (D 256).  A list of its own: the GPU parametrisation over CASES does not change."""
+    cs = []
+    for i, (dt, B, H, N, D, causal) in enumerate([(BF16, 2, 4, 320, 128, True), (FP16, 1, 2, 192, 64, False), (BF16, 1, 2, 257, 40, True),
+                                                  (FP16, 1, 2, 200, 256, True)]):
+        cs.append(_case(f"bhnd-{'bf16' if dt == BF16 else 'fp16'}-b{B}h{H}-d{D}-{'c' if causal else 'f'}-{N}", D=D, dtype=dt, B=B, H=H, Hk=H, Nq=N, Nk=N, causal=causal,
+                        seed=2700 + i))
+    return cs
+
+
+BHND_CASES = _bhnd_cases()
+# the fixed-length forward + backward problem tests/test_threads_gpu.py runs from several threads and streams (GQA, second blocks on both sides)
+THREADS_CASE = _case("threads-bf16-h4hk2-d128-c-320x385", D=128, dtype=BF16, B=1, H=4, Hk=2, Nq=320, Nk=385, causal=True, seed=2710)
+# ... and the split-KV problem of test_chunk_route_side_streams_and_graph_capture (head dim 256: one launch per key chunk over the calling thread's side streams)
+THREADS_SPLITKV_CASE = _case("threads-splitkv-bf16-h8hk4-d256-c-s4-3x6000", kind="splitkv", D=256, dtype=BF16, B=1, H=8, Hk=4, Nq=3, Nk=6000, causal=True, splits=4,
+                             seed=2711)
+BOUNDARY_BY_ID = {c["id"]: c for c in BHND_CASES + [THREADS_CASE, THREADS_SPLITKV_CASE]}
+assert not set(BOUNDARY_BY_ID) & set(BY_ID), "case ids must be unique"
+
+
 def sweep_case(seed):
     """test_seeded_sweep's draw: dtype, D (a multiple of 8 up to 128; one draw in eight, fixed-length ones, from 136..256 without a form), G, B, Nq and Nk in
     1..450, fixed / packed / paged, a random legal form (form_ref.sweep_case's), a forced or the automatic variant."""
@@ -411,6 +433,8 @@ def sweep_case(seed):
 
 
 def case_of(case_id):
+    if case_id in BOUNDARY_BY_ID:
+        return BOUNDARY_BY_ID[case_id]
     return BY_ID[case_id] if case_id in BY_ID else sweep_case(int(case_id[len("sweep"):]))
 
 

@@ -4,7 +4,8 @@
   2. the correct algorithm fits: a 16-bit emulation of the kernels' algorithm — fp32 scores, P rounded to 16 bits against every row reference the library
      has (oracle.tiled_emulation / _lazy / _first_tile / ksplit_emulation; for the forms a score-matrix-driven restatement of the same loops, checked against
      those four at "no form"), fp32 sums, the chunks' merge, O rounded once — stays below 1.0 of the fp32 out bound, of the 16-bit out bound and of the LSE
-     bound on every element, in both dtypes, on every case of the GPU list and every draw of its seeded sweep;
+     bound on every element, in both dtypes, on every case of the GPU list and every draw of its seeded sweep — and on the cases of the flat entry points
+     (tests/test_boundary_gpu.py) and of the thread test (tests/test_threads_gpu.py), fwd_ref.BOUNDARY_BY_ID;
   3. the bounds bite: every mutant a case names (fwd_ref.MUTANTS) misses the out bound or the LSE bound by at least 10x in some element; every mutant is named
      by at least two cases; a mutant a case does not name is in its `na` with a structural reason; every sweep draw has a mutant that bites;
   4. on the record (printed, not asserted; profiles/fwd_bounds.txt): which (case, mutant) pairs the bars the suite asserted before — 1e-2 on the 16-bit out,
@@ -23,6 +24,7 @@ import fwd_ref as R
 import kvcache_ref as K
 
 IDS = [c["id"] for c in R.CASES]
+BHND_IDS = list(R.BOUNDARY_BY_ID)   # the flat entry points' cases (tests/test_boundary_gpu.py) and the threads' forward problem (tests/test_threads_gpu.py)
 SWEEP = [f"sweep{s}" for s in range(48)]
 BITE = 10.0
 LN2 = 0.6931471805599453
@@ -228,7 +230,7 @@ def _fit(oracle, case_id, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
-@pytest.mark.parametrize("case_id", IDS + SWEEP)
+@pytest.mark.parametrize("case_id", IDS + BHND_IDS + SWEEP)
 def test_emulation_fits(oracle, case_id, dtype):
     w, who = _fit(oracle, case_id, dtype)
     print(f"{case_id}: emulation at {w['out32']:.3f} of the fp32 out bound ({who['out32']}), {w['out16']:.3f} of the 16-bit one ({who['out16']}), "
@@ -339,9 +341,9 @@ def _mutant_ratios(t, parts, ref, mutant, dtype):
     return wo, wl, old
 
 
-@pytest.mark.parametrize("case_id,mutant", [(c["id"], m) for c in R.CASES for m in c["mutants"]])
+@pytest.mark.parametrize("case_id,mutant", [(c["id"], m) for c in R.CASES + list(R.BOUNDARY_BY_ID.values()) for m in c["mutants"]])
 def test_mutant_misses_a_bound(case_id, mutant):
-    dtype = R.BY_ID[case_id]["dtype"]
+    dtype = R.case_of(case_id)["dtype"]
     wo, wl, _ = _mutant_ratios(*_reference(case_id, dtype), mutant, dtype)
     print(f"{case_id} / {mutant}: misses the out bound by {wo:.1f}x, the LSE bound by {wl:.1f}x")
     assert max(wo, wl) >= BITE, f"{case_id}: mutant {mutant} is only {wo:.2f}x / {wl:.2f}x outside the bounds — the case's inputs do not tell it from the definition"

@@ -32,7 +32,7 @@ int num_cus() { return tfa::num_cus_current_device(); }
 // every (b,h) slice of q, k, v and out fits ONE buffer descriptor (< 2 GiB including the rows a ragged block may reach past the
 // end): what the key-split, split-KV, backward and x4 kernels need; larger slices run the windowed il4 / il8 instantiations
 bool one_descriptor(const tfa_fwd_params* p) {
-  const auto small = [&](int64_t n, const int64_t* st, int es) { return ((n + 512) * st[2] + p->D) * es < (int64_t)0x7fffffff; };
+  const auto small = [&](int64_t n, const int64_t* st, int es) { return tfa::span_bytes(n + 512, st[2], p->D, es) < (int64_t)0x7fffffff; };
   return small(p->Nq, p->q_stride, 2) && small(p->Nk, p->k_stride, 2) && small(p->Nk, p->v_stride, 2) && small(p->Nq, p->o_stride, 4);
 }
 
@@ -50,7 +50,7 @@ bool out_aliases_itself(const tfa_fwd_params* p) {
   for (int i = 0; i < 3; ++i) {
     if (ext[i] <= 1) continue;
     if (st[i] < span) return true;
-    span = (ext[i] - 1) * st[i] + span;
+    span = tfa::span_bytes(ext[i] - 1, st[i], span, 1);      // (INT64_MAX when it leaves 64 bit: every stride above it then aliases)
   }
   return false;
 }
@@ -77,8 +77,9 @@ int pick_variant(const tfa_fwd_params* p) {
   // CU) waste less of the causal diagonal and fill the chip on small problems (BASELINE config 2:
   // B4 H8 N1024 has only 128 blocks of 256 rows).
   // The issue-interleaved kernel (tfa_fwd_kernel_il.h) wins wherever the grid fills the chip (+5..11% at D=128).
-  const long long blocks256 = (long long)p->B * p->H * ((p->Nq + 255) / 256);
-  const long long blocks128 = (long long)p->B * p->H * ((p->Nq + 127) / 128);
+  if (p->B <= 0 || p->H <= 0 || p->Nq <= 0) return tfa::kDefaultVariant;   // (validate refuses these: any answer serves)
+  const long long blocks256 = tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 255) / 256);
+  const long long blocks128 = tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
   const int cus = num_cus();
   // (partial passes — kv_offset / nk_total — reach the kernels as a causal shift only: every rule below applies to them too)
   // Grids of at most one 128-row block per CU: the 4-wave kernel would run one wave per SIMD (causal: paired, on half the CUs) —
@@ -111,9 +112,9 @@ int pick_variant(const tfa_fwd_params* p) {
 // slice through per-block / per-tile windows (rsrc_at), so only a WINDOW (a 256-row query block or a 64-row tile plus the
 // rows a ragged tail may reach past it) has to fit 2 GiB — long (B,N,H,D) tensors whose head slices span more are fine.
 bool slice_bytes(int64_t n, int64_t row_stride, int d, int esize, bool windowed, unsigned long long* out, int* big) {
-  const int64_t bytes = ((n - 1) * row_stride + d) * esize;
-  const int64_t whole = ((n + 512) * row_stride + d) * esize;       // one descriptor per slice
-  const int64_t window = (768 * row_stride + d) * esize;            // one per query block / tile
+  const int64_t bytes = tfa::span_bytes(n - 1, row_stride, d, esize);
+  const int64_t whole = tfa::span_bytes(n + 512, row_stride, d, esize);       // one descriptor per slice
+  const int64_t window = tfa::span_bytes(768, row_stride, d, esize);          // one per query block / tile
   if (bytes <= 0) return false;
   if (whole >= (int64_t)0x7fffffff) {
     if (!windowed || window >= (int64_t)0x7fffffff) return false;
@@ -145,7 +146,7 @@ int validate(const tfa_fwd_params* p, tfa::KArgs* a, int variant, int row_mod = 
     const int es = (t == 3) ? osz : esz;
     for (int i = 0; i < 3; ++i) {
       if (st[t][i] < 0) return TFA_ERR_STRIDE;
-      if ((st[t][i] * es) % 16 != 0) return TFA_ERR_STRIDE;   // 16-byte vector access on every row
+      if (st[t][i] % (16 / es) != 0) return TFA_ERR_STRIDE;   // 16-byte vector access on every row
     }
     if (st[t][2] < p->D) return TFA_ERR_STRIDE;               // rows must not overlap
   }
@@ -157,7 +158,7 @@ int validate(const tfa_fwd_params* p, tfa::KArgs* a, int variant, int row_mod = 
   a->q = p->q; a->k = p->k; a->v = p->v; a->o = p->out; a->lse = p->lse;
   a->B = p->B; a->H = p->H; a->Hk = p->Hk; a->Nq = p->Nq; a->Nk = p->Nk;
   {
-    if (p->kv_offset < 0 || p->nk_total < 0) return TFA_ERR_SHAPE;
+    if (p->kv_offset < 0 || p->nk_total < 0 || p->kv_offset >= (int64_t)0x3fffffff) return TFA_ERR_SHAPE;   // (kv_offset + Nk <= total < 2^30 below)
     const int64_t total = p->nk_total ? p->nk_total : (p->kv_offset + p->Nk);
     if (p->kv_offset + p->Nk > total || total - p->Nq - p->kv_offset < -(int64_t)0x3fffffff || total >= (int64_t)0x3fffffff) return TFA_ERR_SHAPE;
     a->shift = (int)(total - p->Nq - p->kv_offset);
@@ -187,7 +188,7 @@ int validate(const tfa_fwd_params* p, tfa::KArgs* a, int variant, int row_mod = 
   a->dbg = g_dbg_flags;
   // K and V together beyond 768 MiB: the cache will not survive in the memory-side cache until the next call -> decode kernels may
   // stream it with the non-temporal hint (tfa_fwd_kernel_il.h / tfa_fwd_kernel_dma.h: kv_private, VF_DMA_NT)
-  a->kv_stream = ((long long)p->B * p->Hk * p->Nk * p->D * 4 >= (768ll << 20)) ? 1 : 0;
+  a->kv_stream = (tfa::sat_mul((long long)p->B * p->Hk, (long long)p->Nk * p->D * 4) >= (768ll << 20)) ? 1 : 0;
   a->row_mod = row_mod;
   a->dv = p->D;
   return TFA_OK;
@@ -208,11 +209,14 @@ bool pack_gqa_rows(const tfa_fwd_params* p, tfa_fwd_params* o, int* row_mod = nu
   if (p->kv_offset != 0 || p->nk_total != 0) return false;
   const int G = p->H / p->Hk;
   const bool one_row = p->Nq == 1;
-  const bool adjacent = p->q_stride[1] == (int64_t)p->Nq * p->q_stride[2] && p->o_stride[1] == (int64_t)p->Nq * p->o_stride[2];
+  if ((long long)G * p->Nq > 128) return false;          // beyond one query block nothing is shared any more
+  int64_t q_rows = 0, o_rows = 0, q_head = 0, o_head = 0;   // (strides near INT64_MAX / 2 are refused by validate, not packed: every product checked)
+  if (__builtin_mul_overflow((int64_t)p->Nq, p->q_stride[2], &q_rows) || __builtin_mul_overflow((int64_t)p->Nq, p->o_stride[2], &o_rows) ||
+      __builtin_mul_overflow((int64_t)G, p->q_stride[1], &q_head) || __builtin_mul_overflow((int64_t)G, p->o_stride[1], &o_head)) return false;
+  const bool adjacent = p->q_stride[1] == q_rows && p->o_stride[1] == o_rows;
   const bool with_positions = !one_row && p->is_causal;
   if (!one_row && !adjacent) return false;
   if (with_positions && !(causal_rows && row_mod && p->D <= 128 && p->Nk >= p->Nq)) return false;
-  if ((long long)G * p->Nq > 128) return false;          // beyond one query block nothing is shared any more
   *o = *p;
   o->H = p->Hk;
   o->Nq = G * p->Nq;
@@ -225,8 +229,8 @@ bool pack_gqa_rows(const tfa_fwd_params* p, tfa_fwd_params* o, int* row_mod = nu
     *row_mod = p->Nq;
     o->nk_total = (int64_t)p->Nk + (int64_t)(G - 1) * p->Nq;   // shift = nk_total - G*Nq = Nk - Nq
   }
-  o->q_stride[1] = (int64_t)G * p->q_stride[1];
-  o->o_stride[1] = (int64_t)G * p->o_stride[1];
+  o->q_stride[1] = q_head;
+  o->o_stride[1] = o_head;
   return true;
 }
 
@@ -252,7 +256,7 @@ int run_f32(const tfa_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool d
   const int64_t* st[4] = {p->q_stride, p->k_stride, p->v_stride, p->o_stride};
   for (int t = 0; t < 4; ++t) {
     for (int i = 0; i < 3; ++i)
-      if (st[t][i] < 0 || (st[t][i] * 4) % 16 != 0) return TFA_ERR_STRIDE;
+      if (st[t][i] < 0 || st[t][i] % 4 != 0) return TFA_ERR_STRIDE;
     if (st[t][2] < p->D) return TFA_ERR_STRIDE;
   }
   if (out_aliases_itself(p)) return TFA_ERR_STRIDE;
@@ -263,7 +267,7 @@ int run_f32(const tfa_fwd_params* p, void* stream, tfa::LaunchGeom* geom, bool d
   memset(&a, 0, sizeof(a));
   a.q = p->q; a.k = p->k; a.v = p->v; a.o = p->out; a.lse = p->lse;
   a.B = p->B; a.H = p->H; a.Hk = p->Hk; a.Nq = p->Nq; a.Nk = p->Nk;
-  if (p->kv_offset < 0 || p->nk_total < 0) return TFA_ERR_SHAPE;
+  if (p->kv_offset < 0 || p->nk_total < 0 || p->kv_offset >= (int64_t)0x3fffffff) return TFA_ERR_SHAPE;
   const int64_t total = p->nk_total ? p->nk_total : (p->kv_offset + p->Nk);
   if (p->kv_offset + p->Nk > total || total - p->Nq - p->kv_offset < -(int64_t)0x3fffffff || total >= (int64_t)0x3fffffff) return TFA_ERR_SHAPE;
   a.shift = (int)(total - p->Nq - p->kv_offset);
@@ -589,10 +593,11 @@ static int splitkv_geometry(const tfa_fwd_params* p, int splits, int* nsplit, in
   if (!p || splits < 1) return TFA_ERR_SHAPE;
   if (p->dtype == TFA_F32) return TFA_ERR_DTYPE;                             // fp32 q, k, v: tfa_fwd only (tfa.h) — whichever route the call would take
   if (p->kv_offset != 0 || p->nk_total != 0) return TFA_ERR_SHAPE;          // the call splits the WHOLE key sequence
-  int c = (p->Nk + splits - 1) / splits;
-  c = (c + 63) / 64 * 64;
-  *chunk = c;
-  *nsplit = (p->Nk + c - 1) / c;
+  if (p->B <= 0 || p->H <= 0 || p->Nq <= 0 || p->Nk <= 0 || p->D <= 0) return TFA_ERR_SHAPE;   // (no key: the chunk below would be 0 and divide; the others size the workspace)
+  long long c = (((long long)p->Nk + splits - 1) / splits + 63) / 64 * 64;   // 64 bit: Nk + splits - 1 leaves int for splits near INT32_MAX
+  if (c > INT32_MAX / 64 * 64) c = INT32_MAX / 64 * 64;                       // (Nk within 63 of INT32_MAX: the largest chunk an int holds, two of them)
+  *chunk = (int)c;
+  *nsplit = (int)((p->Nk + c - 1) / c);
   return TFA_OK;
 }
 
@@ -600,8 +605,7 @@ long long tfa_fwd_splitkv_workspace(const tfa_fwd_params* p, int splits) {
   int ns = 0, ch = 0;
   const int st = splitkv_geometry(p, splits, &ns, &ch);
   if (st != TFA_OK) return st;
-  const long long rows = (long long)p->B * p->H * p->Nq;
-  return (long long)ns * rows * (p->D + 1);
+  return tfa::size_product({ns, p->B, p->H, p->Nq, (long long)p->D + 1});
 }
 
 int tfa_fwd_splitkv(const tfa_fwd_params* p, int splits, float* workspace, void* stream) {
@@ -711,9 +715,9 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   // ((b,h) slices of 2 GiB and more take tfa_fwd_splitkv's one-launch-per-chunk route, the launches spread over side streams: a
   //  small chunk count, below)
   if (p->kv_offset != 0 || p->nk_total != 0 || p->B <= 0 || p->H <= 0 || p->Nq <= 0) return 1;
-  const long long blocks = (long long)p->B * p->H * ((p->Nq + 127) / 128);
+  const long long blocks = tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
   const int cus = num_cus();
-  if (blocks * 2 > cus || p->Nk < 4096) return 1;
+  if (blocks > cus / 2 || p->Nk < 4096) return 1;        // (blocks * 2 > cus, without the product)
   if (p->is_causal && (long long)p->Nq * 4 > p->Nk) return 1;   // causal prefill: the late chunks serve few rows (measured 0.93-1.06x)
   // up to a quarter of the CUs: one chunk per idle CU (measured 3-9x).  Between a quarter and a half: the split kernel fits two
   // workgroups per CU, fill those (blocks 96: 226 -> 141 us with 4 chunks, 128: 230-240 -> 165-175 us; at 160-192 blocks a split
@@ -986,10 +990,10 @@ static int kvcache_suggest_splits(const tfa_kvcache_params* p, int pack) {
   // tfa_fwd_suggest_splits' rule on host-known sizes: the capacity stands in for the lengths (which live on the device)
   const bool packed = pack != TFA_PACK_GQA_OFF && kvcache_packs(p);     // one row per sequence: a non-causal problem
   const bool packed_rows = kvcache_packs_positions(p, pack);            // several: workgroups counted from the packed geometry
-  const long long blocks = (packed || packed_rows) ? (long long)p->B * p->Hk * (((long long)p->Nq * (p->H / p->Hk) + 127) / 128)
-                                                   : (long long)p->B * p->H * ((p->Nq + 127) / 128);
+  const long long blocks = (packed || packed_rows) ? tfa::sat_mul((long long)p->B * p->Hk, ((long long)p->Nq * (p->H / p->Hk) + 127) / 128)
+                                                   : tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
   const int cus = num_cus();
-  if (blocks * 2 > cus || p->capacity < 4096) return 1;
+  if (blocks > cus / 2 || p->capacity < 4096) return 1;   // (blocks * 2 > cus, without the product)
   if (p->is_causal && !packed && (long long)p->Nq * 4 > p->capacity) return 1;
   long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
   if (s > p->capacity / 1024) s = p->capacity / 1024;
@@ -1212,9 +1216,9 @@ int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa
   const int gp = packed ? p->H / p->Hk : 1;
   const long long nmb = ((long long)vq->max_seqlen_q * gp + 127) / 128;
   const long long launched = (long long)p->B * nmb, filled = ((long long)vq->total_q * gp + 127) / 128 + p->B;
-  const long long blocks = (long long)(packed ? p->Hk : p->H) * (launched < filled ? launched : filled);
+  const long long blocks = tfa::sat_mul(packed ? p->Hk : p->H, launched < filled ? launched : filled);
   const int cus = num_cus();
-  if (blocks * 2 > cus || p->capacity < 4096) return 1;
+  if (blocks > cus / 2 || p->capacity < 4096) return 1;   // (blocks * 2 > cus, without the product)
   if (p->is_causal && vq->max_seqlen_q > 1 && (long long)vq->max_seqlen_q * 4 > p->capacity) return 1;
   long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
   if (s > p->capacity / 1024) s = p->capacity / 1024;

@@ -42,9 +42,9 @@ thread_local int g_bwd_split = 0;   // tfa_debug_bwd_split: bit 3 = delta by a l
 // inside int32; the BIG instantiations (windowed descriptors, tfa_bwd_kernel.h) only need a window — 768 rows — to fit, and are
 // launched when *big comes back set.  big == nullptr: the caller has no windowed form.
 bool slice_bytes(int64_t n, int64_t row_stride, int d, int esize, unsigned* out, unsigned long long* full = nullptr, int* big = nullptr) {
-  const int64_t bytes = ((n - 1) * row_stride + d) * esize;
-  const int64_t reach = ((n + 512) * row_stride + d) * esize;   // every byte offset a kernel forms stays inside int32
-  const int64_t window = (768 * row_stride + d) * esize;
+  const int64_t bytes = tfa::span_bytes(n - 1, row_stride, d, esize);      // (INT64_MAX when a product leaves 64 bit: refused by size below)
+  const int64_t reach = tfa::span_bytes(n + 512, row_stride, d, esize);    // every byte offset a kernel forms stays inside int32
+  const int64_t window = tfa::span_bytes(768, row_stride, d, esize);
   if (bytes <= 0) return false;
   if (reach >= (int64_t)0x7fffffff) {
     if (!big || window >= (int64_t)0x7fffffff) return false;
@@ -64,7 +64,7 @@ bool fill(tfa::BTensor* t, const void* ptr, const int64_t* st, int64_t n, int d,
 int check_strides(const int64_t* st, int d, int esize) {
   for (int i = 0; i < 3; ++i) {
     if (st[i] < 0) return TFA_ERR_STRIDE;
-    if ((st[i] * esize) % 16 != 0) return TFA_ERR_STRIDE;
+    if (st[i] % (16 / esize) != 0) return TFA_ERR_STRIDE;
   }
   if (st[2] < d) return TFA_ERR_STRIDE;
   return TFA_OK;
@@ -129,14 +129,14 @@ long long ws_bytes(const tfa_bwd_params* p, int* nk_pad, int* nq_pad) {
   if (nk_pad) *nk_pad = (int)nk;
   if (nq_pad) *nq_pad = (int)nq;
   if (nk * nq * 2 >= (long long)0x7fffffff) return 0;
-  return (long long)p->B * p->H * nk * nq * 2;
+  return tfa::size_product({p->B, p->H, nk, nq, 2});
 }
 
 // ws_need (optional): receives the bytes of dS scratch the 5-GEMM form would use for *p, 0 when this problem never takes that form
 int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need = nullptr) {
   if (ws_need) *ws_need = 0;
   if (!p) return TFA_ERR_NULL;
-  int st = check_bwd(*p, true, true, 256, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
+  int st = check_bwd(*p, true, true, 256, TFA_OK, 16, tfa::sat_mul((int64_t)p->B * p->H, p->Nq));
   if (st) return st;
   const int gsz = (p->grad_dtype == TFA_F32) ? 4 : 2;
   tfa::BArgs a;
@@ -242,7 +242,7 @@ int run_bwd(const tfa_bwd_params* p, void* stream, bool dry, long long* ws_need 
   if (!slice_bytes(p->Nk, p->dk_stride[2], p->D, gsz, &m.g_bytes, &m.g_full, bigp) ||
       !slice_bytes(p->Nk, p->dv_stride[2], p->D, gsz, &m.g2_bytes, &m.g2_full, bigp)) return TFA_ERR_STRIDE;
   constexpr int kv_keys = 32 * TFA_BWD_KV_KG_OF(false);   // resident keys per workgroup of the fused launch
-  m.nrb = (p->Nk + kv_keys - 1) / kv_keys;
+  m.nrb = (int)(((int64_t)p->Nk + kv_keys - 1) / kv_keys);
   const int64_t grid = (int64_t)p->B * p->Hk * m.nrb;
   if (grid >= (int64_t)0x7fffffff) return TFA_ERR_SHAPE;
   return (int)launch_kv(m, (int)grid);
@@ -296,7 +296,7 @@ int run_bwd_local(const tfa_bwd_params* p, const int* w, const tfa::AlibiArg* al
     f.is_causal = form == tfa::WIN_CAUSAL;
     return run_bwd(&f, stream, dry);
   }
-  int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, (int64_t)p->B * p->H * p->Nq);
+  int st = check_bwd(*p, true, (int64_t)p->Nq + p->Nk < (1 << 28), 128, TFA_OK, 16, tfa::sat_mul((int64_t)p->B * p->H, p->Nq));
   if (st) return st;
   if (al && (st = al->biased ? tfa::check_bias(al->bias, p->dtype, p->Nq, p->Nk) : tfa::check_alibi(*al, p->H, p->softmax_scale)) != TFA_OK) return st;
   tfa::BArgs a;

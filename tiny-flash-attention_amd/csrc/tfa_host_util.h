@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <initializer_list>
 #include <stdint.h>
 
 #include "tfa.h"
@@ -35,6 +36,28 @@ static inline int num_cus_current_device() {
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
   if (cacheable) cache[dev].store(n, std::memory_order_relaxed);
   return n;
+}
+
+// A workspace size as the *_workspace entry points answer it: the product of non-negative counts, or TFA_ERR_SHAPE when it does not fit a long long (sizes
+// near INT32_MAX in every dimension) — never a wrapped, negative or otherwise meaningless number.
+static inline long long size_product(std::initializer_list<long long> f) {
+  long long r = 1;
+  for (long long x : f)
+    if (x < 0 || __builtin_mul_overflow(r, x, &r)) return TFA_ERR_SHAPE;
+  return r;
+}
+
+// a * b for non-negative counts, INT64_MAX when it does not fit: grids and byte counts that are only compared with a threshold
+static inline long long sat_mul(long long a, long long b) {
+  long long r;
+  return __builtin_mul_overflow(a, b, &r) ? INT64_MAX : r;
+}
+// (rows * stride + d) * es in 64 bit, INT64_MAX when it does not fit: strides near INT64_MAX / 2 are arguments a caller can pass — they are refused by
+// their size, never by an overflow on the way to the comparison
+static inline int64_t span_bytes(int64_t rows, int64_t stride, int64_t d, int64_t es) {
+  int64_t r;
+  if (__builtin_mul_overflow(rows, stride, &r) || __builtin_add_overflow(r, d, &r) || __builtin_mul_overflow(r, es, &r)) return INT64_MAX;
+  return r;
 }
 
 // The kernel shape a launch instantiates: element type T, compiled head-dim width W.
@@ -96,9 +119,9 @@ enum { WIN_FULL = 0, WIN_CAUSAL = 1, WIN_LOCAL = 2 };
 static inline int window_form(int* left, int* right, bool causal, int nq, int nk) {
   if (*left < -1 || *right < -1) return TFA_ERR_SHAPE;
   if (causal) *right = 0;
-  if (*left >= nk - 1) *left = -1;
+  if (*left >= (int64_t)nk - 1) *left = -1;                 // (64 bit: the caller may not have checked nq / nk yet)
   if (*left < 0 && *right == 0) return WIN_CAUSAL;
-  if (*right >= nq - 1) *right = -1;
+  if (*right >= (int64_t)nq - 1) *right = -1;
   return (*left < 0 && *right < 0) ? WIN_FULL : WIN_LOCAL;
 }
 // the window as the kernels read it (KArgs / BArgs::win_left, win_right): both sides >= 0, an unbounded one as nq + nk
@@ -133,7 +156,7 @@ static inline int check_bias(const tfa_attn_bias* bi, int q_dtype, int Nq, int N
   if (bi->stride[2] != 0 && bi->stride[2] < Nk) return TFA_ERR_STRIDE;              // (rows that overlap)
   const int esize = bi->dtype == TFA_F32 ? 4 : 2;
   if (bi->stride[2] > (int64_t)0x7fffffff / esize) return TFA_ERR_STRIDE;
-  if (((int64_t)(Nq - 1) * bi->stride[2] + Nk) * esize >= ((int64_t)1 << 31)) return TFA_ERR_STRIDE;
+  if (((int64_t)Nq - 1) * bi->stride[2] + Nk >= ((int64_t)1 << 31) / esize) return TFA_ERR_STRIDE;   // (64 bit throughout: the caller may not have checked Nq yet)
   return TFA_OK;
 }
 // ... and into the kernel arguments (KArgs / BArgs: bytes no bias launch reads — after everything else has been written)
@@ -144,7 +167,7 @@ static inline void set_bias(Args* a, const tfa_attn_bias& bi, int Nq, int Nk) {
   a->bias_sb = bi.stride[0];
   a->bias_sh = bi.stride[1];
   a->bias_sn = (int)bi.stride[2] * esize;                                           // (bytes)
-  a->bias_bytes = (unsigned)(((int64_t)(Nq - 1) * bi.stride[2] + Nk) * esize);
+  a->bias_bytes = (unsigned)((((int64_t)Nq - 1) * bi.stride[2] + Nk) * esize);
   a->bias_f32 = bi.dtype == TFA_F32;
 }
 static inline int check_alibi(const AlibiArg& al, int H, float scale) {

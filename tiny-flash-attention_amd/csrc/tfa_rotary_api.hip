@@ -9,7 +9,7 @@
 
 namespace {
 
-bool bad_stride(int64_t s) { return s < 0 || (s * 2) % 16 != 0; }     // 16-bit elements: every row, head and batch a whole number of 16-byte chunks on
+bool bad_stride(int64_t s) { return s < 0 || s % 8 != 0; }         // 16-bit elements: every row, head and batch a whole number of 16-byte chunks on
 bool bad_stride8(int64_t s) { return s < 0 || s % 16 != 0; }          // the strides of an e4m3 cache: bytes
 
 // the tables of both entry points: (seqlen_ro, rotary_dim / 2) of cs_dtype, 16-byte aligned rows
@@ -18,7 +18,7 @@ int check_tables(const void* cos, const void* sin, int dtype, int cs_dtype, int 
   if (rotary_dim < 16 || rotary_dim > D || (rotary_dim % 16) != 0) return TFA_ERR_HEAD_DIM;
   if (seqlen_ro <= 0 || (interleaved != 0 && interleaved != 1)) return TFA_ERR_SHAPE;
   const int es = cs_dtype == TFA_F32 ? 4 : 2;
-  if (cos_stride < rotary_dim / 2 || sin_stride < rotary_dim / 2 || (cos_stride * es) % 16 != 0 || (sin_stride * es) % 16 != 0) return TFA_ERR_STRIDE;
+  if (cos_stride < rotary_dim / 2 || sin_stride < rotary_dim / 2 || cos_stride % (16 / es) != 0 || sin_stride % (16 / es) != 0) return TFA_ERR_STRIDE;
   if (((uintptr_t)cos | (uintptr_t)sin) & 15) return TFA_ERR_ALIGN;
   return TFA_OK;
 }
@@ -68,12 +68,13 @@ int rotary_run(const tfa_rotary_params* p, void* stream, int* grid, int* block, 
   a.rows = packed ? (long long)p->N : (long long)p->B * p->N;
   a.rd8 = p->rotary_dim / 8;
   a.ipr = p->interleaved ? p->D / 8 : p->rotary_dim / 16 + (p->D - p->rotary_dim) / 8;
-  a.total = a.rows * (p->H + p->H2) * a.ipr;
+  // (checked products: B * N * (H + H2) * items leaves 64 bit for sizes near INT32_MAX — a grid of 2^31 blocks or more either way)
+  if (__builtin_mul_overflow(a.rows, (long long)p->H + p->H2, &a.total) || __builtin_mul_overflow(a.total, (long long)a.ipr, &a.total)) return TFA_ERR_SHAPE;
+  if (a.total > 0x7ffffffell * 256) return TFA_ERR_SHAPE;                     // the grid stays below 2^31 blocks
   a.seqlen_ro = p->seqlen_ro;
   a.interleaved = p->interleaved; a.conjugate = p->conjugate;
   a.bf16 = p->dtype == TFA_BF16 ? 1 : 0;
   a.cos_f32 = p->cs_dtype == TFA_F32 ? 1 : 0;
-  if ((a.total + 255) / 256 >= (long long)0x7fffffff) return TFA_ERR_SHAPE;   // the grid stays below 2^31 blocks
   return (int)tfa::launch_rotary(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
 }
 
@@ -129,7 +130,7 @@ int append_varlen_run(const tfa_kvcache_append_varlen_params* p, const tfa_kvcac
   a.kn_h = p->k_stride[0]; a.kn_n = p->k_stride[1];
   a.vn_h = p->v_stride[0]; a.vn_n = p->v_stride[1];
   a.B = p->B; a.Hk = p->Hk; a.cpr = p->D / 8;
-  a.total = (long long)p->total_new * p->Hk * a.cpr;
+  if (__builtin_mul_overflow((long long)p->total_new * p->Hk, (long long)a.cpr, &a.total) || a.total > 0x7ffffffell * 256) return TFA_ERR_SHAPE;   // (2^31 blocks or more)
   a.capacity = p->capacity;
   a.page_size = paged ? p->page_size : 1;
   a.num_pages = paged ? p->num_pages : 1;
@@ -154,7 +155,7 @@ int append_varlen_run(const tfa_kvcache_append_varlen_params* p, const tfa_kvcac
     a.q = rq->q; a.H = rq->H;
     a.q_h = rq->q_stride[0]; a.q_n = rq->q_stride[1];
     a.q_ipr = p->rotary_interleaved ? a.rd8 : a.rd8 / 2;
-    a.q_total = (long long)p->total_new * rq->H * a.q_ipr;
+    if (__builtin_mul_overflow((long long)p->total_new * rq->H, (long long)a.q_ipr, &a.q_total) || a.q_total > 0x7ffffffell * 256) return TFA_ERR_SHAPE;
   }
   if ((a.total + a.q_total + 255) / 256 >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
   return (int)tfa::launch_kvcache_append_varlen_ex(a, reinterpret_cast<hipStream_t>(stream), grid, block, dry);
