@@ -56,9 +56,9 @@ def form_kwargs(t, dev):
     return kw
 
 
-def call(t, dev):
+def call(t, dev, place=None):
     """The public call of a case, 16-bit and fp32 out: (out16, out32 or None, [the LSE of each launch]) on the CPU, out as (B,H,Nq,D) / packed (total_q,H,D), the
-    LSEs as the call returns them."""
+    LSEs as the call returns them.  place (paged cases): (k_pool, v_pool, block_table) on the device to use instead of copies of the case's."""
     from tiny_flash_attention_amd import ops
 
     c, sc = t["case"], t["sc"]
@@ -86,7 +86,8 @@ def call(t, dev):
         cq, ck = d(t["cu_q"]), d(t["cu_k"])
         mq, mk = max(1, max(c["lq"])), max(1, max(c["lk"]))
         if c["kind"] == "paged":
-            k, v, kw = d(t["k_pool"]), d(t["v_pool"]), dict(block_table=d(t["bt"]))
+            k, v, bt = (d(t["k_pool"]), d(t["v_pool"]), d(t["bt"])) if place is None else place
+            kw = dict(block_table=bt)
         else:
             k, v, kw = d(t["k"]), d(t["v"]), form_kwargs(t, dev)
         q = d(t["q"])
@@ -116,7 +117,8 @@ def call(t, dev):
     return o16.cpu(), o32.cpu(), [lse.cpu(), lse32.cpu()]
 
 
-def run_case(case_id, dev, lib):
+def run_case(case_id, dev, lib, place=None):
+    """The case against its bounds; returns what call() returned.  place: a function of the case's tensors that returns call()'s place."""
     t, parts, ref = reference(case_id)
     c, dtype = t["case"], t["dtype"]
     lib.set_variant(c["variant"])
@@ -124,7 +126,7 @@ def run_case(case_id, dev, lib):
         if c["peak"] is not None:                           # what the case is in the list for: the library says it rounds against the first tile's maximum
             rule = lib.rule_for(c["B"], c["H"], c["Hk"], c["Nq"], c["Nk"], c["D"], c["causal"], lib.TFA_BF16)
             assert rule == lib.RULE_FIRST_TILE, f"{case_id}: rounding rule {rule}, not TFA_RULE_FIRST_TILE"
-        o16, o32, lses = call(t, dev)
+        o16, o32, lses = call(t, dev, None if place is None else place(t))
     finally:
         lib.set_variant(-1)
     worst = {"out32": 0.0, "out16": 0.0, "lse": 0.0, "lse_old": 0.0}
@@ -167,6 +169,7 @@ def run_case(case_id, dev, lib):
     assert worst["out16"] <= 1.0, f"{case_id}: the 16-bit out is at {worst['out16']:.3f} of its per-element bound"
     assert worst["lse"] <= 1.0, f"{case_id}: the LSE is at {worst['lse']:.3f} of its derived bound"
     assert worst["lse_old"] <= 1.0, f"{case_id}: the LSE is at {worst['lse_old']:.3f} of the earlier bar, 1e-4 (the forms: * max(1, |lse|))"
+    return o16, o32, lses
 
 
 def ids(pred):

@@ -43,14 +43,16 @@ def same_values(a, b):
     return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
-def call(t, dev, mask="words", sched=None):
+def call(t, dev, mask="words", sched=None, place=None):
     """The public call of a case.  mask: "words" (the case's int64 words, contiguous), "strided" (the same words inside a wider tensor), "bool" (4-D: the bool
-    form), "ones" (all-ones words) or None (the plain causal call).  Returns per sequence with rows (out (nq, H, D), lse (H, nq)) on the CPU."""
+    form), "ones" (all-ones words) or None (the plain causal call).  place: (k_cache, v_cache, block_table) on the device to use instead of fresh copies of the case's
+    (tests/test_far_pool_gpu.py; what an append leaves in them is then its caller's to compare).  Returns per sequence with rows (out (nq, H, D), lse (H, nq)) on the CPU."""
     import tiny_flash_attention_amd as tfa
 
     c = t["case"]
     d = lambda x: None if x is None else x.to(dev)     # noqa: E731  (a fresh device copy: an append writes it)
-    kc, vc, bt, q = d(t["k_cache"]), d(t["v_cache"]), d(t["bt"]), d(t["q_call"])
+    kc, vc, bt = (d(t["k_cache"]), d(t["v_cache"]), d(t["bt"])) if place is None else place
+    q = d(t["q_call"])
     kd, vd = (d(t["kd"]), d(t["vd"])) if c["fp8"] else (None, None)
     B, packed = t["B"], c["form"] == "packed"
     words = t["words"] if packed else t["words"].view(B, c["Nq"])
@@ -91,7 +93,7 @@ def call(t, dev, mask="words", sched=None):
             assert tuple(out.shape) == tuple(q.shape) and tuple(lse.shape) == (c["H"], t["total_q"]) and lse.dtype == torch.float32
             out, lse = out.cpu(), lse.cpu()
             res = {b: (out[q0:q0 + nq], lse[:, q0:q0 + nq]) for b, (q0, nq) in enumerate(t["rows"]) if nq > 0}
-    if c["append"] is not None:
+    if c["append"] is not None and place is None:
         assert same_values(kc, t["k_final"]) and same_values(vc, t["v_final"]), "the caches behind the append are not what the append is defined to store"
     return res
 

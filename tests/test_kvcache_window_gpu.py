@@ -43,13 +43,15 @@ def same_values(a, b):
     return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
-def call(t, dev, window="case", kc=None, vc=None, bt=None, splits=None):
+def call(t, dev, window="case", kc=None, vc=None, bt=None, splits=None, place=None):
     """The public call of a case (window: the case's w, None = the plain causal call, or another w; kc / vc / bt: device tensors to use instead of fresh copies of
-    the case's); returns per sequence with rows (out (nq, H, D), lse (H, nq)) on the CPU."""
+    the case's; place: all three at once, as tests/test_far_pool_gpu.py hands them over — what an append leaves in them is then its caller's to compare); returns per sequence with rows (out (nq, H, D), lse (H, nq)) on the CPU."""
     import tiny_flash_attention_amd as tfa
 
     c = t["case"]
     d = lambda x: None if x is None else x.to(dev)     # noqa: E731  (a fresh device copy: an append writes it)
+    if place is not None:
+        kc, vc, bt = place
     kc = d(t["k_cache"]) if kc is None else kc
     vc = d(t["v_cache"]) if vc is None else vc
     bt = d(t["bt"]) if bt is None else bt
@@ -74,7 +76,7 @@ def call(t, dev, window="case", kc=None, vc=None, bt=None, splits=None):
             assert tuple(out.shape) == tuple(q.shape) and tuple(lse.shape) == (c["H"], t["total_q"]) and lse.dtype == torch.float32
             out, lse = out.cpu(), lse.cpu()
             res = {b: (out[q0:q0 + nq], lse[:, q0:q0 + nq]) for b, (q0, nq) in enumerate(t["rows"]) if nq > 0}
-    if c["append"] is not None:
+    if c["append"] is not None and place is None:
         assert same_values(kc, t["k_final"]) and same_values(vc, t["v_final"]), "the caches behind the append are not what the append is defined to store"
     return res
 
