@@ -5,9 +5,11 @@ functions; the compute is the hand-written HIP kernel in csrc/.  Nothing here fa
 PyTorch or the CPU: if the library is missing or the device is not a GPU the call raises.
 """
 import ctypes as C
+import functools
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -531,6 +533,37 @@ def flash_attn(q, k, v, is_causal, softmax_scale):
 naive_attn = flash_attn
 
 
+def _once_differentiable(backward):
+    """``torch.autograd.function.once_differentiable`` for a backward whose result also depends on tensors the forward SAVED: the gradients come out of ctypes
+    launches, with no graph behind them, so under ``create_graph=True`` a second derivative would silently be that of a constant.  torch's decorator attaches
+    its error node only when an incoming gradient requires grad; the gradient of a linear loss does not, yet dq, dk, dv still depend on q, k, v — so under
+    ``create_graph=True`` (the only time a backward runs with grad mode on) the incoming gradients are handed on as views that require grad, and
+    differentiating anything that depends on the results raises RuntimeError."""
+    once = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled():
+            grads = tuple(g.detach().requires_grad_() if isinstance(g, torch.Tensor) and not g.requires_grad else g for g in grads)
+        return once(ctx, *grads)
+
+    return wrapper
+
+
+def _kernel_dout(dout, row_dim):
+    """The upstream gradient autograd hands over, as tfa_bwd / tfa_bwd_varlen read it.  The C ABI's own rule (csrc/tfa_bwd_api.hip: check_strides, check_bwd):
+    unit stride along D, every other stride >= 0 and a multiple of 8 elements, the row stride (dim ``row_dim``) >= D, a 16-byte base.  A gradient that meets
+    it is passed on AS IT IS — ``out.transpose(1, 2)``'s, or the zero batch / head stride of ``out.sum(0)`` / ``out.sum(2)``: the kernels form every address
+    from base + b * stride_b + h * stride_h + row * stride_n and read such a gradient to the bits of its dense copy.  One that misses it — the zero row stride
+    of ``out.sum(1)``, the odd strides and offset base behind a ``torch.cat`` — is copied once.  The handed tensor may be shared with other consumers of the
+    graph: it is read, never written (the copy is this call's own)."""
+    D = dout.shape[-1]
+    st = dout.stride()
+    if st[-1] == 1 and all(s >= 0 and s % 8 == 0 for s in st[:-1]) and st[row_dim] >= D and dout.data_ptr() % 16 == 0:
+        return dout
+    return dout.clone(memory_format=torch.contiguous_format)
+
+
 class _FlashAttnBNHD(torch.autograd.Function):
     """autograd glue for ``flash_attn_func``: forward = tfa_fwd, backward = tfa_bwd, both on (B,N,H,D) views."""
 
@@ -545,10 +578,10 @@ class _FlashAttnBNHD(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dout):
         q, k, v, out, lse, slopes, bias = ctx.saved_tensors
-        if dout.stride(3) != 1:
-            dout = dout.contiguous()
+        dout = _kernel_dout(dout, 1)
         dq, dk, dv = flash_attn_bwd(q, k, v, out, lse, dout, ctx.causal, ctx.scale, layout="bnhd", window_size=ctx.window, attn_bias=bias,
                                     alibi_slopes=slopes, softcap=ctx.softcap)
         return dq, dk, dv, None, None, None, None, None, None   # (causal, scale, window, bias, softcap, slopes: no gradient)
@@ -821,11 +854,11 @@ class _FlashAttnVarlen(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dout):
         q, k, v, out, lse, cu_q, cu_k, slopes = ctx.saved_tensors
         max_q, max_k, causal, scale, window, softcap = ctx.args
-        if dout.stride(2) != 1:
-            dout = dout.contiguous()
+        dout = _kernel_dout(dout, 0)
         dq, dk, dv = flash_attn_varlen_bwd(q, k, v, out, lse, dout, cu_q, cu_k, max_q, max_k, causal, scale, window_size=window, alibi_slopes=slopes,
                                            softcap=softcap)
         return dq, dk, dv, None, None, None, None, None, None, None, None, None
@@ -1530,6 +1563,7 @@ class _ApplyRotaryEmb(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_once_differentiable
     def backward(ctx, dout):
         saved = list(ctx.saved_tensors)
         cos, sin = saved[0], saved[1]
