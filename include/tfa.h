@@ -813,7 +813,7 @@ int tfa_kvcache_append_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q
  * _workspace: the same number of floats whatever pack_gqa.  _plan: the attention launch's geometry — packed, B * Hk * work items * chunks workgroups, work items =
  * query blocks nmb = ceil(Nq * G / 128), or ceil(nmb / 2) causal.  _suggest_splits: tfa_fwd_kvcache_suggest_splits' rule with the workgroups counted from the
  * geometry the mode runs (packed: B * Hk * ceil(Nq * G / 128)); AUTO equals tfa_fwd_kvcache_suggest_splits.
- * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcPacked, fwd_kernel_dma_kvc_pack / _kvc8_pack) — instantiations of their own, so every other kernel keeps its instructions
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcPacked; fwd_kernel_dma_kvc over it) — instantiations of their own, so every other kernel keeps its instructions
  * (profiles/kvcache_packgqa_isa_unchanged.txt).  Measured: profiles/kvcache_packgqa_bench.txt (tools/bench_kvcache_packgqa.py), quoted in README.md. */
 #define TFA_PACK_GQA_AUTO 0
 #define TFA_PACK_GQA_ON   1
@@ -845,7 +845,7 @@ int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gq
  * heads * min(B * nmb, ceil(total_q * G' / 128) + B) — the second term bounds the non-empty blocks from what the host knows.
  * Refused, nothing launched: a NULL vq or cu_seqlens_q (TFA_ERR_NULL); max_seqlen_q <= 0, total_q <= 0, a nonzero reserved field (TFA_ERR_SHAPE); a cu_seqlens_q that
  * is not 4-byte aligned (TFA_ERR_ALIGN); everything tfa_fwd_kvcache_pack refuses.
- * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcVarlenQ, fwd_kernel_dma_kvc_vq) — instantiations and units of their own, so every other kernel keeps its instructions
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcVarlenQ; fwd_kernel_dma_kvc over it) — instantiations and units of their own, so every other kernel keeps its instructions
  * (profiles/kvcache_varlenq_isa_unchanged.txt). */
 typedef struct tfa_kvcache_varlen_q {
   const int32_t* cu_seqlens_q;   /* device, B + 1 entries */
@@ -913,7 +913,7 @@ int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvc
  * _window_plan: the underlying form's grid, block and LDS bytes (the window changes no launch geometry); validates without a GPU.  A plan has no list: `scheduled`
  *   != 0 asks for the scheduled form's geometry (tfa_fwd_kvcache_varlen_sched_plan's; needs vq), 0 for the unscheduled one's.
  * Refused, nothing launched: window_left < 0, p->is_causal == 0, metadata without vq (TFA_ERR_SHAPE); everything the underlying form refuses, with its codes.
- * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcWindow, behind the form's struct; fwd_kernel_dma_kvc_win) — the causal template, the 16-bit direct output and the fp32 partials,
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcWindow, behind the form's struct; fwd_kernel_dma_kvc over it) — the causal template, the 16-bit direct output and the fp32 partials,
  * units of their own (tfa_kvc_inst_win_*, tfa_kvc8_inst_win_*), so every other kernel keeps its instructions (profiles/kvcache_window_isa_unchanged.txt). */
 int tfa_fwd_kvcache_window(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq /* NULL: 4-D */, const tfa_kvcache_fp8* q8 /* NULL: 16-bit cache */, int pack_gqa, int window_left, int splits, const int32_t* metadata /* NULL: unscheduled; needs vq */, float* workspace, void* stream);
 int tfa_fwd_kvcache_window_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, int scheduled, int* grid, int* block, int* lds_bytes);
@@ -940,7 +940,7 @@ int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa
  * GQA at Nq == 1 (vq == NULL): as tfa_fwd_kvcache_window — TFA_PACK_GQA_AUTO and _ON run position-major packed rows.
  * Refused, nothing launched: a NULL tree or mask (TFA_ERR_NULL), a mask that is not 8-byte aligned (TFA_ERR_ALIGN), a negative stride (TFA_ERR_STRIDE), p->is_causal == 0,
  *   metadata without vq (TFA_ERR_SHAPE); everything the underlying form refuses, with its codes.  No window: a tree mask with a sliding window is not implemented.
- * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcTree, behind the form's struct; fwd_kernel_dma_kvc_tree) — the causal template, the 16-bit direct output and the fp32 partials,
+ * Kernels: csrc/tfa_fwd_kernel_dma.h (KvcTree, behind the form's struct; fwd_kernel_dma_kvc over it) — the causal template, the 16-bit direct output and the fp32 partials,
  * units of their own (tfa_kvc_inst_tree_*, tfa_kvc8_inst_tree_*), so every other kernel keeps its instructions (profiles/kvcache_tree_isa_unchanged.txt). */
 typedef struct tfa_kvcache_tree {
   const void* mask;              /* device, 8-byte words (int64): bit s of a row's word = the row sees the s-th new key of its sequence */

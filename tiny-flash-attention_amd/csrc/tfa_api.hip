@@ -513,6 +513,22 @@ int variant_or_rule(const FwdCall& c, bool rule) {
   return rule ? r : v;
 }
 
+// every field any form's kernel reads: the host fills this once, a launch takes the struct of its form out of it (kvc_typed)
+using KvcAll = tfa::KvcTree<tfa::KvcWindow<tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>>>>;
+template <typename A>
+A kvc_typed(const KvcAll& ka) {
+  A v;
+  memset(&v, 0, sizeof(v));
+  static_cast<tfa::KvcArgs&>(v) = ka;
+  if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
+  if constexpr (tfa::KvcPack<const A>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
+  if constexpr (tfa::KvcVq<const A>::value) { v.vq_cu = ka.vq_cu; v.vq_max_q = ka.vq_max_q; v.vq_total_q = ka.vq_total_q; }
+  if constexpr (tfa::KvcSc<const A>::value) { v.sc_meta = ka.sc_meta; v.sc_bound = ka.sc_bound; }
+  if constexpr (tfa::KvcWin<const A>::value) v.win_left = ka.win_left;
+  if constexpr (tfa::KvcTr<const A>::value) { v.tree = ka.tree; v.tree_bs = ka.tree_bs; v.tree_rs = ka.tree_rs; }
+  return v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -706,6 +722,20 @@ int tfa_fwd_splitkv(const tfa_fwd_params* p, int splits, float* workspace, void*
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->out_dtype, p->lse, stream);
 }
 
+// THE split-suggestion rule, on what its caller knows of the problem: `blocks` workgroups of 128 query rows (> 0), `keys` keys per sequence, causal_prefill —
+// a causal problem whose late chunks would serve few rows (measured 0.93-1.06x).
+// Up to a quarter of the CUs: one chunk per idle CU (measured 3-9x).  Between a quarter and a half: the split kernel fits two workgroups per CU, fill those
+// (blocks 96: 226 -> 141 us with 4 chunks, 128: 230-240 -> 165-175 us; at 160-192 blocks a split no longer pays: profiles/r03_decode_nt_ab.txt)
+static int suggest_splits_for(long long blocks, long long keys, bool causal_prefill) {
+  const int cus = num_cus();
+  if (blocks > cus / 2 || keys < 4096) return 1;          // (blocks * 2 > cus, without the product)
+  if (causal_prefill) return 1;
+  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
+  if (s > keys / 1024) s = keys / 1024;
+  if (s > 32) s = 32;
+  return s >= 2 ? (int)s : 1;
+}
+
 int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   if (!p_in || g_variant >= 0) return 1;                  // a forced kernel variant means: run exactly that
   if (p_in->dtype == TFA_F32) return 1;                   // (the fp32 correctness path is one pass)
@@ -716,20 +746,11 @@ int tfa_fwd_suggest_splits(const tfa_fwd_params* p_in) {
   //  small chunk count, below)
   if (p->kv_offset != 0 || p->nk_total != 0 || p->B <= 0 || p->H <= 0 || p->Nq <= 0) return 1;
   const long long blocks = tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
-  const int cus = num_cus();
-  if (blocks > cus / 2 || p->Nk < 4096) return 1;        // (blocks * 2 > cus, without the product)
-  if (p->is_causal && (long long)p->Nq * 4 > p->Nk) return 1;   // causal prefill: the late chunks serve few rows (measured 0.93-1.06x)
-  // up to a quarter of the CUs: one chunk per idle CU (measured 3-9x).  Between a quarter and a half: the split kernel fits two
-  // workgroups per CU, fill those (blocks 96: 226 -> 141 us with 4 chunks, 128: 230-240 -> 165-175 us; at 160-192 blocks a split
-  // no longer pays: profiles/r03_decode_nt_ab.txt)
-  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
-  if (s > p->Nk / 1024) s = p->Nk / 1024;
-  if (s > 32) s = 32;
+  const int s = suggest_splits_for(blocks, p->Nk, p->is_causal && (long long)p->Nq * 4 > p->Nk);
   // one launch per chunk (slices of 2 GiB and more): every chunk costs a launch on the host and the four side
   // streams overlap about two launches' worth — measured 1.4-1.8x over one pass at four chunks, less at eight or sixteen
   // (tools/bench_decode_wide.py, profiles/r03_decode_wide.txt)
-  if (!one_descriptor(p_in) && s > 4) s = 4;            // (the caller's strides, as tfa_fwd_splitkv tests them — not the packed ones)
-  return s >= 2 ? (int)s : 1;
+  return (s > 4 && !one_descriptor(p_in)) ? 4 : s;        // (the caller's strides, as tfa_fwd_splitkv tests them — not the packed ones)
 }
 
 // ---- attention over a K/V cache (tfa.h: tfa_fwd_kvcache) ----------------------------------------------------------------------------------
@@ -817,194 +838,7 @@ static bool kvcache_pack_args(const tfa_kvcache_params* p, bool causal, int o_es
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream);
 
-// one host path for the 16-bit cache (q8 == nullptr: tfa_fwd_kvcache) and the e4m3 cache (tfa_fwd_kvcache_fp8): validation, chunking, packing and the three launches
-// pack: TFA_PACK_GQA_AUTO — what tfa_fwd_kvcache runs, ON / OFF — tfa_fwd_kvcache_pack's choices
-// win_left >= 0: the windowed form (tfa_fwd_kvcache_window) — the same checks, chunks and workspace; causal only; Nq == 1 packs position-major like Nq > 1
-static int kvcache_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry,
-                       int win_left = -1, const tfa_kvcache_tree* tree = nullptr) {
-  int st = kvcache_check_cache(p, q8);
-  if (st != TFA_OK) return st;
-  const bool win = win_left >= 0;
-  const bool tr = tree != nullptr;                         // the tree form (tfa_fwd_kvcache_tree): the same checks, chunks, geometry and workspace; causal only; packs as the windowed form
-  if ((win || tr) && !p->is_causal) return TFA_ERR_SHAPE;
-  if (!p->q || !p->out) return TFA_ERR_NULL;
-  if (p->H <= 0 || p->Nq <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
-  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
-  const bool paged = p->block_table != nullptr;
-  const int ns = kvcache_chunks(p, splits);
-  const long long rows = (long long)p->B * p->H * p->Nq;
-  tfa_fwd_params f;
-  memset(&f, 0, sizeof(f));
-  f.q = p->q; f.k = p->k_cache; f.v = p->v_cache; f.out = p->out; f.lse = p->lse;
-  f.B = p->B; f.H = p->H; f.Hk = p->Hk; f.Nq = p->Nq; f.D = p->D;
-  f.Nk = paged ? p->page_size : p->capacity;              // the rows one K/V descriptor spans (validate: slice_bytes)
-  for (int i = 0; i < 3; ++i) { f.q_stride[i] = p->q_stride[i]; f.k_stride[i] = p->k_stride[i]; f.v_stride[i] = p->v_stride[i]; f.o_stride[i] = p->o_stride[i]; }
-  f.softmax_scale = p->softmax_scale;
-  f.is_causal = p->is_causal ? 1 : 0;
-  f.dtype = f.out_dtype = p->dtype;
-  float* ws_o = workspace;
-  float* ws_l = workspace ? workspace + (long long)ns * rows * p->D : nullptr;
-  if (ns > 1) {
-    // the merge writes contiguous rows: out must be a contiguous (B,H,Nq,D) tensor; the partial pass writes fp32 O and LSE of every chunk into the workspace
-    if (p->o_stride[2] != p->D || p->o_stride[1] != (int64_t)p->Nq * p->D || p->o_stride[0] != (int64_t)p->H * p->Nq * p->D) return TFA_ERR_STRIDE;
-    if (((uintptr_t)p->out & 15)) return TFA_ERR_ALIGN;
-    if (p->lse && ((uintptr_t)p->lse & 3)) return TFA_ERR_ALIGN;
-    if (!dry) {
-      if (!workspace) return TFA_ERR_NULL;
-      if ((uintptr_t)workspace & 15) return TFA_ERR_ALIGN;
-    }
-    f.out = dry ? (void*)p->out : (void*)ws_o;            // (a plan has no workspace: any aligned address stands in)
-    f.lse = dry ? nullptr : ws_l;
-    f.out_dtype = TFA_F32;
-  }
-  tfa::KArgs a;
-  {
-    tfa_fwd_params fp;
-    st = TFA_ERR_SHAPE;
-    if (!win && !tr && pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(&f, &fp)) {      // as in tfa_fwd_splitkv: the packed description is an optimisation, never a requirement
-      st = validate(&fp, &a, tfa::kSplitVariant);
-      if (st == TFA_OK) f = fp;
-    }
-    if (st != TFA_OK) st = validate(&f, &a, tfa::kSplitVariant);
-  }
-  if (st != TFA_OK) return st;
-  tfa::KvcPacked<tfa::Kvc8Args> ka;                         // (the 16-bit launch takes its KvcArgs base; the unpacked launches theirs, without the packed form's tail)
-  memset(&ka, 0, sizeof(ka));
-  // several rows per sequence, packed: the validated problem is the caller's own — its packed description replaces the geometry only
-  // (windowed or tree, one row per sequence: the heads-as-rows packing above is a non-causal problem, which has neither — the position-major one serves it, t = row / G = 0)
-  const bool pack_pos = kvcache_packs_positions(p, pack) || ((win || tr) && pack != TFA_PACK_GQA_OFF && kvcache_packs(p));
-  const bool packed_rows = pack_pos && kvcache_pack_args(p, f.is_causal != 0, ns > 1 ? 4 : 2, &a, &ka);
-  static_cast<tfa::KArgs&>(ka) = a;
-  ka.nsplit = ns;
-  ka.chunk = 0;                                            // (formed per sequence on the device)
-  ka.o_part_stride = ns > 1 ? rows * p->D : 0;
-  ka.lse_part_stride = ns > 1 ? rows : 0;
-  ka.trace = nullptr;
-  ka.seqlens = p->cache_seqlens;
-  ka.block_table = p->block_table;
-  ka.bt_stride = p->block_table_stride;
-  ka.n_new = p->n_new;
-  ka.capacity = p->capacity;
-  ka.num_pages = paged ? p->num_pages : 1;
-  ka.nq_pos = p->Nq;
-  ka.tpp = paged ? p->page_size / 64 : 1;
-  ka.fd_nsplit = tfa::fastdiv_of((unsigned)ns);
-  ka.fd_tpp = tfa::fastdiv_of((unsigned)ka.tpp);
-  ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * (q8 ? 2 : 4) >= (768ll << 20)) ? 1 : 0;
-  if ((long long)ka.nbh * ka.nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
-  const bool causal = f.is_causal != 0;                    // (the packed one-row problem is non-causal)
-  const bool nt = ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;   // tfa_fwd_splitkv's rule for the non-temporal hint
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!dry && p->k_new) {                                  // this step's keys first, on the same stream
-    st = kvcache_append_run(p, q8, stream);
-    if (st != TFA_OK) return st;
-  }
-  if (q8) {
-    ka.k_descale = q8->k_descale; ka.v_descale = q8->v_descale;
-    ka.kd_b = q8->k_descale_stride[0]; ka.kd_h = q8->k_descale_stride[1];
-    ka.vd_b = q8->v_descale_stride[0]; ka.vd_h = q8->v_descale_stride[1];
-  }
-  const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
-    using T = typename decltype(k)::T;
-    if (win || tr) {
-      // the arguments of the instantiation that runs: the form's struct with the window or the tree behind it
-      auto run = [&](auto* args) {
-        using A = std::remove_pointer_t<decltype(args)>;
-        A v;
-        memset(&v, 0, sizeof(v));
-        static_cast<tfa::KvcArgs&>(v) = ka;
-        if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
-        if constexpr (tfa::KvcPack<const A>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
-        if constexpr (tfa::KvcTr<const A>::value) {
-          v.tree = static_cast<const unsigned long long*>(tree->mask); v.tree_bs = tree->batch_stride; v.tree_rs = tree->row_stride;
-          return tfa::launch_kvc_tree<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
-        } else {
-          v.win_left = win_left < p->capacity ? win_left : p->capacity;
-          return tfa::launch_kvc_win<T, decltype(k)::W, A>(v, ns > 1, s, geom, dry);
-        }
-      };
-      if (tr) {
-        if (packed_rows) return q8 ? run((tfa::KvcTree<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcTree<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
-        return q8 ? run((tfa::KvcTree<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcTree<tfa::KvcArgs>*)nullptr);
-      }
-      if (packed_rows) return q8 ? run((tfa::KvcWindow<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcWindow<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
-      return q8 ? run((tfa::KvcWindow<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcWindow<tfa::KvcArgs>*)nullptr);
-    }
-    if (packed_rows) {
-      if (q8) return tfa::launch_kvc8_pack<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
-      tfa::KvcPacked<tfa::KvcArgs> k16;
-      static_cast<tfa::KvcArgs&>(k16) = ka;
-      k16.pk_g = ka.pk_g; k16.pk_fd_g = ka.pk_fd_g; k16.pk_pad_ = 0; k16.q_hs = ka.q_hs; k16.o_hs = ka.o_hs;
-      return tfa::launch_kvc_pack<T, decltype(k)::W>(k16, causal, ns > 1, nt, s, geom, dry);
-    }
-    if (q8) return tfa::launch_kvc8<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
-    return tfa::launch_kvc<T, decltype(k)::W>(ka, causal, ns > 1, nt, s, geom, dry);
-  });
-  if (e != hipSuccess) return (int)e;
-  if (dry || ns == 1) return TFA_OK;
-  return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
-}
-
-static int kvcache_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits, int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_run(p, q8, pack, splits, nullptr, nullptr, &g, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
-}
-
-static long long kvcache_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits) {
-  const int st = kvcache_run(p, q8, pack, splits, nullptr, nullptr, nullptr, true);
-  if (st != TFA_OK) return st;
-  const int ns = kvcache_chunks(p, splits);
-  return ns > 1 ? (long long)ns * p->B * p->H * p->Nq * (p->D + 1) : 0;
-}
-
-int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) { return kvcache_run(p, nullptr, TFA_PACK_GQA_AUTO, splits, workspace, stream, nullptr, false); }
-int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) { return kvcache_plan(p, nullptr, TFA_PACK_GQA_AUTO, splits, grid, block, lds_bytes); }
-long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) { return kvcache_workspace(p, nullptr, TFA_PACK_GQA_AUTO, splits); }
-
-// the e4m3 cache: the second struct is required (its NULL descale pointers mean 1.0)
-int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream) {
-  return q8 ? kvcache_run(p, q8, TFA_PACK_GQA_AUTO, splits, workspace, stream, nullptr, false) : TFA_ERR_NULL;
-}
-int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
-  return q8 ? kvcache_plan(p, q8, TFA_PACK_GQA_AUTO, splits, grid, block, lds_bytes) : TFA_ERR_NULL;
-}
-long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) { return q8 ? kvcache_workspace(p, q8, TFA_PACK_GQA_AUTO, splits) : (long long)TFA_ERR_NULL; }
-
-// the same calls with the GQA packing chosen by the caller (q8 == NULL: the 16-bit cache)
-int tfa_fwd_kvcache_pack(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
-  return kvcache_run(p, q8, pack_gqa, splits, workspace, stream, nullptr, false);
-}
-int tfa_fwd_kvcache_pack_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
-  return kvcache_plan(p, q8, pack_gqa, splits, grid, block, lds_bytes);
-}
-long long tfa_fwd_kvcache_pack_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) { return kvcache_workspace(p, q8, pack_gqa, splits); }
-
-static int kvcache_suggest_splits(const tfa_kvcache_params* p, int pack) {
-  if (!p || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->capacity <= 0 || p->H % p->Hk != 0) return 1;
-  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return 1;
-  // tfa_fwd_suggest_splits' rule on host-known sizes: the capacity stands in for the lengths (which live on the device)
-  const bool packed = pack != TFA_PACK_GQA_OFF && kvcache_packs(p);     // one row per sequence: a non-causal problem
-  const bool packed_rows = kvcache_packs_positions(p, pack);            // several: workgroups counted from the packed geometry
-  const long long blocks = (packed || packed_rows) ? tfa::sat_mul((long long)p->B * p->Hk, ((long long)p->Nq * (p->H / p->Hk) + 127) / 128)
-                                                   : tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
-  const int cus = num_cus();
-  if (blocks > cus / 2 || p->capacity < 4096) return 1;   // (blocks * 2 > cus, without the product)
-  if (p->is_causal && !packed && (long long)p->Nq * 4 > p->capacity) return 1;
-  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
-  if (s > p->capacity / 1024) s = p->capacity / 1024;
-  if (s > 32) s = 32;
-  return s >= 2 ? (int)s : 1;
-}
-int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) { return kvcache_suggest_splits(p, TFA_PACK_GQA_AUTO); }
-int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa) { return kvcache_suggest_splits(p, pack_gqa); }
-
-// ---- the varlen-q form (tfa.h: tfa_fwd_kvcache_varlen): q packed (total_q, H, D), sequence b's rows read from cu_seqlens_q on the device ----------------------------
-// packed iff asked (AUTO = ON) and the heads group: Hk < H, G <= 128.  G = 1 and G > 128 run the unpacked instantiations
+// the packed-q layout (tfa_fwd_kvcache_varlen) packs iff asked (AUTO = ON) and the heads group: Hk < H, G <= 128.  G = 1 and G > 128 run the unpacked instantiations
 static bool kvcache_vq_packs(const tfa_kvcache_params* p, int pack) { return pack != TFA_PACK_GQA_OFF && p->Hk > 0 && p->H > p->Hk && p->H % p->Hk == 0 && p->H / p->Hk <= 128; }
 
 // the launch geometry of max_q rows of gp heads each per (sequence, K/V head or head): query blocks, work items (causal blocks pair heavy / light on the launch-level index)
@@ -1027,185 +861,308 @@ static long long kvcache_sched_bound(int B, int max_q, int total_q, int gp, bool
 }
 static_assert(tfa::SCHED_HDR == tfa::SCHEDULE_HDR, "one header size for the kernel that writes the list and the one that reads it");
 
-// sched: the scheduled form (tfa_fwd_kvcache_varlen_sched) — meta is the list tfa_kvcache_varlen_schedule built (NULL allowed in a dry run)
-static int kvcache_vq_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, float* workspace, void* stream,
-                          tfa::LaunchGeom* geom, bool dry, const int32_t* meta = nullptr, bool sched = false, int win_left = -1,
-                          const tfa_kvcache_tree* tree = nullptr) {
-  if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
-  const bool win = win_left >= 0;                            // the windowed form (tfa_fwd_kvcache_window): the same checks, geometry and workspace; causal only
-  const bool tr = tree != nullptr;                           // the tree form (tfa_fwd_kvcache_tree): likewise
-  if ((win || tr) && !p->is_causal) return TFA_ERR_SHAPE;
-  if (sched && !dry) {
-    if (!meta) return TFA_ERR_NULL;
-    if ((uintptr_t)meta & 7) return TFA_ERR_ALIGN;
+// One K/V-cache call as an entry point names it — the K/V-cache counterpart of FwdCall — and the one host path that runs it: the 16-bit cache (q8 == nullptr) or
+// the e4m3 one, q 4-D or packed (vq: tfa_fwd_kvcache_varlen and, sched, its scheduled form over the list `meta`), with a rider (a window of win_left keys, a tree)
+// or without.  The _plan and _workspace entry points are dry runs of it (no GPU needed).
+struct KvcCall {
+  const tfa_kvcache_params* p = nullptr;
+  const tfa_kvcache_varlen_q* vq = nullptr;
+  const tfa_kvcache_fp8* q8 = nullptr;
+  int pack = TFA_PACK_GQA_AUTO;         // AUTO: what tfa_fwd_kvcache runs (packed q: ON); ON / OFF: the caller's choice
+  int splits = 1;
+  const int32_t* meta = nullptr;        // the list tfa_kvcache_varlen_schedule built (NULL allowed in a dry run)
+  bool sched = false;
+  int win_left = -1;
+  const tfa_kvcache_tree* tree = nullptr;
+  int rider = tfa::KVC_NONE;            // the entry point's: KVC_WIN wants win_left >= 0, KVC_TREE a tree — their absence is then an error, not "no rider"
+  bool packed_q = false;                // the entry point takes a packed q: a NULL vq is then an error, not "4-D"
+};
+static KvcCall kvc_call(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits) {
+  KvcCall c;
+  c.p = p; c.q8 = q8; c.pack = pack; c.splits = splits;
+  return c;
+}
+static KvcCall kvc_varlen_call(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int splits, const int32_t* meta, bool sched) {
+  KvcCall c = kvc_call(p, q8, pack, splits);
+  c.vq = vq; c.packed_q = true; c.meta = meta; c.sched = sched;
+  return c;
+}
+// the rider entry points take either layout: a vq makes the call a packed-q one
+static KvcCall kvc_window_call(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int left, int splits, const int32_t* meta,
+                               bool sched) {
+  KvcCall c = kvc_varlen_call(p, vq, q8, pack, splits, meta, sched);
+  c.packed_q = vq != nullptr; c.rider = tfa::KVC_WIN; c.win_left = left;
+  return c;
+}
+static KvcCall kvc_tree_call(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, const tfa_kvcache_tree* tree, int splits,
+                             const int32_t* meta, bool sched) {
+  KvcCall c = kvc_varlen_call(p, vq, q8, pack, splits, meta, sched);
+  c.packed_q = vq != nullptr; c.rider = tfa::KVC_TREE; c.tree = tree;
+  return c;
+}
+
+// the rows of out and lse: (B, H, Nq) or, packed q, (H, total_q)
+static long long kvcache_rows(const KvcCall& c) { return c.vq ? (long long)c.p->H * c.vq->total_q : (long long)c.p->B * c.p->H * c.p->Nq; }
+
+// The geometry and packing of the 4-D layout: *f is validated into *a.  One row per sequence packs heads-as-rows (pack_gqa_rows: a non-causal problem, run by the
+// unpacked kernels) — as in tfa_fwd_splitkv the packed description is an optimisation, never a requirement: when it does not validate the problem runs as the caller
+// gave it.  Several rows per sequence, asked for, pack position-major (*packed: the KvcPacked<> kernels): the validated problem is the caller's own — its packed
+// description replaces the geometry only.  With a rider, one row per sequence packs position-major too: heads-as-rows is a non-causal problem, which has no rider —
+// the position-major one serves it, t = row / G = 0.
+static int kvcache_geom_4d(const KvcCall& c, int ns, tfa_fwd_params* f, tfa::KArgs* a, KvcAll* ka, bool* packed) {
+  const tfa_kvcache_params* p = c.p;
+  const bool rider = c.rider != tfa::KVC_NONE;
+  tfa_fwd_params fp;
+  int st = TFA_ERR_SHAPE;
+  if (!rider && c.pack != TFA_PACK_GQA_OFF && kvcache_packs(p) && pack_gqa_rows(f, &fp)) {
+    st = validate(&fp, a, tfa::kSplitVariant);
+    if (st == TFA_OK) *f = fp;
+  }
+  if (st != TFA_OK) st = validate(f, a, tfa::kSplitVariant);
+  if (st != TFA_OK) return st;
+  const bool pack_pos = kvcache_packs_positions(p, c.pack) || (rider && c.pack != TFA_PACK_GQA_OFF && kvcache_packs(p));
+  *packed = pack_pos && kvcache_pack_args(p, f->is_causal != 0, ns > 1 ? 4 : 2, a, ka);
+  return TFA_OK;
+}
+
+// The geometry and packing of the packed-q layout: *f — one sequence of min(max_seqlen_q, total_q) rows — is validated into *a, which then takes the launch's
+// geometry: max_seqlen_q * G' rows per (sequence, head) or, scheduled, heads * bound work items
+static int kvcache_geom_vq(const KvcCall& c, int ns, const tfa_fwd_params* f, tfa::KArgs* a, KvcAll* ka, bool* packed_out) {
+  const tfa_kvcache_params* p = c.p;
+  const tfa_kvcache_varlen_q* vq = c.vq;
+  const int st = validate(f, a, tfa::kSplitVariant);
+  if (st != TFA_OK) return st;
+  const bool causal = f->is_causal != 0;
+  const int G = p->H / p->Hk, mq = f->Nq;
+  const int osz = ns > 1 ? 4 : 2;
+  bool packed = kvcache_vq_packs(p, c.pack);
+  if (packed) {      // a head group's rows must fit the 32-bit byte offsets of one descriptor; else unpacked — packing is an optimisation, never a requirement
+    const long long q_ext = ((long long)(mq - 1) * a->qs_n + (long long)(G - 1) * a->qs_h + p->D) * 2;
+    const long long o_ext = ((long long)(mq - 1) * a->os_n + (long long)(G - 1) * a->os_h + p->D) * osz;
+    if ((long long)vq->max_seqlen_q * G >= 0x3fffffffll || q_ext >= 0x7fffffffll || o_ext >= 0x7fffffffll) packed = false;
+    if (c.sched && !packed) return TFA_ERR_STRIDE;       // the list was sized and built for the packing the caller named (tfa_kvcache_varlen_schedule_size): no silent change of it
+  }
+  const int gp = packed ? G : 1, heads = packed ? p->Hk : p->H;
+  if ((long long)vq->max_seqlen_q * gp >= 0x3fffffffll) return TFA_ERR_SHAPE;
+  long long nmb, nwork;
+  kvcache_vq_blocks(vq->max_seqlen_q, gp, causal, &nmb, &nwork);
+  const long long bound = c.sched ? kvcache_sched_bound(p->B, vq->max_seqlen_q, vq->total_q, gp, causal) : 0;
+  if ((long long)p->B * heads * nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  if (c.sched && (long long)heads * bound * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  if (packed) {
+    ka->pk_g = G;
+    ka->pk_fd_g = tfa::fastdiv_of((unsigned)G);
+    ka->q_hs = a->qs_h;
+    ka->o_hs = a->os_h;
+    a->qs_h *= G;
+    a->os_h *= G;
+    a->H = p->Hk;
+  }
+  a->B = p->B;
+  a->Nq = (int)((long long)vq->max_seqlen_q * gp);          // sizes the grid; the kernels take every sequence's own row count
+  a->nmb = (int)nmb;
+  a->nwork = (int)nwork;
+  a->nbh = p->B * heads;
+  if (c.sched) {                                             // heads * bound work items: the item decomposition runs over (head, row of the list)
+    a->nbh = heads;
+    a->nwork = (int)bound;
+  }
+  ka->vq_cu = vq->cu_seqlens_q;
+  ka->vq_max_q = vq->max_seqlen_q;
+  ka->vq_total_q = vq->total_q;
+  ka->sc_meta = c.meta;
+  ka->sc_bound = (int)bound;
+  *packed_out = packed;
+  return TFA_OK;
+}
+
+static int kvcache_run(const KvcCall& c, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
+  const tfa_kvcache_params* p = c.p;
+  const tfa_kvcache_varlen_q* vq = c.vq;
+  const tfa_kvcache_fp8* q8 = c.q8;
+  // the rider's own checks: both are forms of the causal template, over any layout
+  if (c.rider != tfa::KVC_NONE) {
+    if (!p || (c.rider == tfa::KVC_TREE && (!c.tree || !c.tree->mask))) return TFA_ERR_NULL;
+    if ((c.rider == tfa::KVC_WIN && c.win_left < 0) || !p->is_causal || (c.sched && !vq)) return TFA_ERR_SHAPE;
+    if (c.rider == tfa::KVC_TREE) {
+      if ((uintptr_t)c.tree->mask & 7) return TFA_ERR_ALIGN;
+      if (c.tree->row_stride < 0 || (!vq && c.tree->batch_stride < 0)) return TFA_ERR_STRIDE;
+    }
+  }
+  if (c.packed_q) {
+    if (!p || !vq || !vq->cu_seqlens_q) return TFA_ERR_NULL;
+    if (c.sched && !dry) {
+      if (!c.meta) return TFA_ERR_NULL;
+      if ((uintptr_t)c.meta & 7) return TFA_ERR_ALIGN;
+    }
   }
   int st = kvcache_check_cache(p, q8);
   if (st != TFA_OK) return st;
   if (!p->q || !p->out) return TFA_ERR_NULL;
-  if (p->H <= 0 || p->H % p->Hk != 0 || splits < 1) return TFA_ERR_SHAPE;
-  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
-  if (vq->max_seqlen_q <= 0 || vq->total_q <= 0 || vq->reserved_[0] != 0 || vq->reserved_[1] != 0) return TFA_ERR_SHAPE;
-  if (p->k_new || p->v_new || p->n_new != 0) return TFA_ERR_SHAPE;      // the append for packed rows is tfa_kvcache_append_varlen
-  if ((uintptr_t)vq->cu_seqlens_q & 3) return TFA_ERR_ALIGN;
+  if (p->H <= 0 || (!vq && p->Nq <= 0) || p->H % p->Hk != 0 || c.splits < 1) return TFA_ERR_SHAPE;
+  if (c.pack != TFA_PACK_GQA_AUTO && c.pack != TFA_PACK_GQA_ON && c.pack != TFA_PACK_GQA_OFF) return TFA_ERR_SHAPE;
+  if (vq) {
+    if (vq->max_seqlen_q <= 0 || vq->total_q <= 0 || vq->reserved_[0] != 0 || vq->reserved_[1] != 0) return TFA_ERR_SHAPE;
+    if (p->k_new || p->v_new || p->n_new != 0) return TFA_ERR_SHAPE;      // the append for packed rows is tfa_kvcache_append_varlen
+    if ((uintptr_t)vq->cu_seqlens_q & 3) return TFA_ERR_ALIGN;
+  }
   const bool paged = p->block_table != nullptr;
-  const int ns = kvcache_chunks(p, splits);
-  const int tq = vq->total_q;
-  const int mq = vq->max_seqlen_q < tq ? vq->max_seqlen_q : tq;          // the most rows a sequence can own after the device's clamp: what the descriptors must reach
-  const long long rows = (long long)p->H * tq;
-  // validate() sees one sequence of mq rows: strides, alignment, the 2 GiB bounds of the q / out descriptors (which start at the sequence's first row)
+  const int ns = kvcache_chunks(p, c.splits);
+  const long long rows = kvcache_rows(c);
+  // the problem validate() sees (strides, alignment, the 2 GiB bounds of the q / out descriptors): the caller's or, packed q, ONE sequence of the most rows a
+  // sequence can own after the device's clamp — its descriptors start at the sequence's first row
   tfa_fwd_params f;
   memset(&f, 0, sizeof(f));
   f.q = p->q; f.k = p->k_cache; f.v = p->v_cache; f.out = p->out; f.lse = p->lse;
-  f.B = 1; f.H = p->H; f.Hk = p->Hk; f.Nq = mq; f.D = p->D;
-  f.Nk = paged ? p->page_size : p->capacity;
+  f.B = vq ? 1 : p->B; f.H = p->H; f.Hk = p->Hk; f.D = p->D;
+  f.Nq = !vq ? p->Nq : vq->max_seqlen_q < vq->total_q ? vq->max_seqlen_q : vq->total_q;
+  f.Nk = paged ? p->page_size : p->capacity;              // the rows one K/V descriptor spans (validate: slice_bytes)
   for (int i = 0; i < 3; ++i) { f.q_stride[i] = p->q_stride[i]; f.k_stride[i] = p->k_stride[i]; f.v_stride[i] = p->v_stride[i]; f.o_stride[i] = p->o_stride[i]; }
-  f.q_stride[0] = f.o_stride[0] = 0;                                     // {ignored, head, row}
+  if (vq) f.q_stride[0] = f.o_stride[0] = 0;              // {ignored, head, row}
   f.softmax_scale = p->softmax_scale;
   f.is_causal = p->is_causal ? 1 : 0;
   f.dtype = f.out_dtype = p->dtype;
   float* ws_o = workspace;
   float* ws_l = workspace ? workspace + (long long)ns * rows * p->D : nullptr;
   if (ns > 1) {
-    // the merge writes contiguous rows: out must be the contiguous (H, total_q, D); the partial pass writes fp32 O and LSE of every chunk into the workspace
-    if (p->o_stride[2] != p->D || p->o_stride[1] != (int64_t)tq * p->D) return TFA_ERR_STRIDE;
+    // the merge writes contiguous rows: out must be a contiguous (B,H,Nq,D) or (H,total_q,D) tensor; the partial pass writes fp32 O and LSE of every chunk into the workspace
+    const int64_t head_rows = vq ? vq->total_q : p->Nq;
+    if (p->o_stride[2] != p->D || p->o_stride[1] != head_rows * p->D || (!vq && p->o_stride[0] != (int64_t)p->H * p->Nq * p->D)) return TFA_ERR_STRIDE;
     if (((uintptr_t)p->out & 15)) return TFA_ERR_ALIGN;
     if (p->lse && ((uintptr_t)p->lse & 3)) return TFA_ERR_ALIGN;
     if (!dry) {
       if (!workspace) return TFA_ERR_NULL;
       if ((uintptr_t)workspace & 15) return TFA_ERR_ALIGN;
     }
-    f.out = dry ? (void*)p->out : (void*)ws_o;
+    f.out = dry ? (void*)p->out : (void*)ws_o;            // (a plan has no workspace: any aligned address stands in)
     f.lse = dry ? nullptr : ws_l;
     f.out_dtype = TFA_F32;
   }
   tfa::KArgs a;
-  st = validate(&f, &a, tfa::kSplitVariant);
-  if (st != TFA_OK) return st;
-  const bool causal = f.is_causal != 0;
-  const int G = p->H / p->Hk;
-  const int osz = ns > 1 ? 4 : 2;
-  bool packed = kvcache_vq_packs(p, pack);
-  if (packed) {      // a head group's rows must fit the 32-bit byte offsets of one descriptor; else unpacked — packing is an optimisation, never a requirement
-    const long long q_ext = ((long long)(mq - 1) * a.qs_n + (long long)(G - 1) * a.qs_h + p->D) * 2;
-    const long long o_ext = ((long long)(mq - 1) * a.os_n + (long long)(G - 1) * a.os_h + p->D) * osz;
-    if ((long long)vq->max_seqlen_q * G >= 0x3fffffffll || q_ext >= 0x7fffffffll || o_ext >= 0x7fffffffll) packed = false;
-    if (sched && !packed) return TFA_ERR_STRIDE;         // the list was sized and built for the packing the caller named (tfa_kvcache_varlen_schedule_size): no silent change of it
-  }
-  const int gp = packed ? G : 1, heads = packed ? p->Hk : p->H;
-  if ((long long)vq->max_seqlen_q * gp >= 0x3fffffffll) return TFA_ERR_SHAPE;
-  long long nmb, nwork;
-  kvcache_vq_blocks(vq->max_seqlen_q, gp, causal, &nmb, &nwork);
-  const long long bound = sched ? kvcache_sched_bound(p->B, vq->max_seqlen_q, tq, gp, causal) : 0;
-  if ((long long)p->B * heads * nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
-  if (sched && (long long)heads * bound * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
-  tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>> ka;        // (every launch takes the bases it has: vq_launch below)
+  KvcAll ka;
   memset(&ka, 0, sizeof(ka));
-  if (packed) {
-    ka.pk_g = G;
-    ka.pk_fd_g = tfa::fastdiv_of((unsigned)G);
-    ka.q_hs = a.qs_h;
-    ka.o_hs = a.os_h;
-    a.qs_h *= G;
-    a.os_h *= G;
-    a.H = p->Hk;
-  }
-  a.B = p->B;
-  a.Nq = (int)((long long)vq->max_seqlen_q * gp);           // sizes the grid; the kernels take every sequence's own row count
-  a.nmb = (int)nmb;
-  a.nwork = (int)nwork;
-  a.nbh = p->B * heads;
-  if (sched) {                                               // heads * bound work items: the item decomposition runs over (head, row of the list)
-    a.nbh = heads;
-    a.nwork = (int)bound;
-  }
+  bool packed = false;                                     // the KvcPacked<> kernels run
+  st = vq ? kvcache_geom_vq(c, ns, &f, &a, &ka, &packed) : kvcache_geom_4d(c, ns, &f, &a, &ka, &packed);
+  if (st != TFA_OK) return st;
   static_cast<tfa::KArgs&>(ka) = a;
   ka.nsplit = ns;
-  ka.chunk = 0;
+  ka.chunk = 0;                                            // (formed per sequence on the device)
   ka.o_part_stride = ns > 1 ? rows * p->D : 0;
   ka.lse_part_stride = ns > 1 ? rows : 0;
   ka.trace = nullptr;
   ka.seqlens = p->cache_seqlens;
   ka.block_table = p->block_table;
   ka.bt_stride = p->block_table_stride;
-  ka.n_new = 0;
+  ka.n_new = p->n_new;
   ka.capacity = p->capacity;
   ka.num_pages = paged ? p->num_pages : 1;
-  ka.nq_pos = vq->max_seqlen_q;                              // (not read: the shift is len_b - nq_b)
+  ka.nq_pos = vq ? vq->max_seqlen_q : p->Nq;               // (packed q: not read — the shift is len_b - nq_b)
   ka.tpp = paged ? p->page_size / 64 : 1;
   ka.fd_nsplit = tfa::fastdiv_of((unsigned)ns);
   ka.fd_tpp = tfa::fastdiv_of((unsigned)ka.tpp);
   ka.kv_stream = ((long long)p->B * p->Hk * p->capacity * p->D * (q8 ? 2 : 4) >= (768ll << 20)) ? 1 : 0;
-  ka.vq_cu = vq->cu_seqlens_q;
-  ka.vq_max_q = vq->max_seqlen_q;
-  ka.vq_total_q = tq;
-  ka.sc_meta = meta;
-  ka.sc_bound = (int)bound;
+  if ((long long)ka.nbh * ka.nwork * ns >= (long long)0x7fffffff) return TFA_ERR_SHAPE;
+  const bool causal = f.is_causal != 0;                    // (the packed one-row problem is non-causal)
+  // tfa_fwd_splitkv's rule for the non-temporal hint; a rider's range is small: no such twin
+  const bool nt = c.rider == tfa::KVC_NONE && ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;
+  if (!dry && p->k_new) {                                  // this step's keys first, on the same stream
+    st = kvcache_append_run(p, q8, stream);
+    if (st != TFA_OK) return st;
+  }
   if (q8) {
     ka.k_descale = q8->k_descale; ka.v_descale = q8->v_descale;
     ka.kd_b = q8->k_descale_stride[0]; ka.kd_h = q8->k_descale_stride[1];
     ka.vd_b = q8->v_descale_stride[0]; ka.vd_h = q8->v_descale_stride[1];
   }
-  const bool nt = ns > 1 && ka.kv_stream && ka.nmb == 1 && ka.H == ka.Hk;
+  if (c.rider == tfa::KVC_WIN) ka.win_left = c.win_left < p->capacity ? c.win_left : p->capacity;
+  if (c.rider == tfa::KVC_TREE) {
+    ka.tree = static_cast<const unsigned long long*>(c.tree->mask);
+    ka.tree_bs = vq ? 0 : c.tree->batch_stride;
+    ka.tree_rs = c.tree->row_stride;
+  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int layout = !vq ? tfa::KVC_PLAIN : c.sched ? tfa::KVC_SCHED : tfa::KVC_VQ;
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
-    using T = typename decltype(k)::T;
-    constexpr int W = decltype(k)::W;
-    // the arguments of the instantiation that runs: the same fields, without the bases it does not have
-    auto run = [&](auto* args) {
-      using A = std::remove_pointer_t<decltype(args)>;
-      using Base = typename A::vq_base;
-      A v;
-      memset(&v, 0, sizeof(v));
-      static_cast<tfa::KvcArgs&>(v) = ka;
-      if constexpr (std::is_base_of<tfa::Kvc8Args, A>::value) static_cast<tfa::Kvc8Args&>(v) = ka;
-      if constexpr (tfa::KvcPack<const Base>::value) { v.pk_g = ka.pk_g; v.pk_fd_g = ka.pk_fd_g; v.pk_pad_ = 0; v.q_hs = ka.q_hs; v.o_hs = ka.o_hs; }
-      v.vq_cu = ka.vq_cu; v.vq_max_q = ka.vq_max_q; v.vq_total_q = ka.vq_total_q;
-      if constexpr (tfa::KvcSc<const A>::value) { v.sc_meta = ka.sc_meta; v.sc_bound = ka.sc_bound; v.sc_pad_ = 0; }
-      if (win) {
-        tfa::KvcWindow<A> w;
-        memset(&w, 0, sizeof(w));
-        static_cast<A&>(w) = v;
-        w.win_left = win_left < p->capacity ? win_left : p->capacity;
-        return tfa::launch_kvc_win<T, W, tfa::KvcWindow<A>>(w, ns > 1, s, geom, dry);
-      }
-      if (tr) {
-        tfa::KvcTree<A> w;
-        memset(&w, 0, sizeof(w));
-        static_cast<A&>(w) = v;
-        w.tree = static_cast<const unsigned long long*>(tree->mask); w.tree_bs = 0; w.tree_rs = tree->row_stride;
-        return tfa::launch_kvc_tree<T, W, tfa::KvcTree<A>>(w, ns > 1, s, geom, dry);
-      }
-      return tfa::launch_kvc_vq<T, W, A>(v, causal, ns > 1, nt, s, geom, dry);
-    };
-    if (sched) {
-      if (packed) return q8 ? run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>>*)nullptr) : run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcPacked<tfa::KvcArgs>>>*)nullptr);
-      return q8 ? run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcSched<tfa::KvcVarlenQ<tfa::KvcArgs>>*)nullptr);
-    }
-    if (packed) return q8 ? run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::Kvc8Args>>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcPacked<tfa::KvcArgs>>*)nullptr);
-    return q8 ? run((tfa::KvcVarlenQ<tfa::Kvc8Args>*)nullptr) : run((tfa::KvcVarlenQ<tfa::KvcArgs>*)nullptr);
+    return tfa::by_kvc_form(q8 != nullptr, packed, layout, c.rider, [&](auto form) {
+      using A = typename decltype(form)::Args;
+      return tfa::launch_kvc<typename decltype(k)::T, decltype(k)::W, A>(kvc_typed<A>(ka), causal, ns > 1, nt, s, geom, dry);
+    });
   });
   if (e != hipSuccess) return (int)e;
   if (dry || ns == 1) return TFA_OK;
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
 }
 
-int tfa_fwd_kvcache_varlen(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
-  return kvcache_vq_run(p, vq, q8, pack_gqa, splits, workspace, stream, nullptr, false);
-}
-int tfa_fwd_kvcache_varlen_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
+static int kvcache_plan(const KvcCall& c, int* grid, int* block, int* lds_bytes) {
   tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, &g, true);
+  const int st = kvcache_run(c, nullptr, nullptr, &g, true);
   if (st != TFA_OK) return st;
   if (grid) *grid = g.grid;
   if (block) *block = g.block;
   if (lds_bytes) *lds_bytes = g.lds;
   return TFA_OK;
 }
-long long tfa_fwd_kvcache_varlen_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) {
-  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, nullptr, true);
+
+// fp32 words: every chunk's partial O rows and LSEs
+static long long kvcache_workspace(const KvcCall& c) {
+  const int st = kvcache_run(c, nullptr, nullptr, nullptr, true);
   if (st != TFA_OK) return st;
-  const int ns = kvcache_chunks(p, splits);
-  return ns > 1 ? (long long)ns * p->H * vq->total_q * (p->D + 1) : 0;
+  const int ns = kvcache_chunks(c.p, c.splits);
+  return ns > 1 ? ns * kvcache_rows(c) * (c.p->D + 1) : 0;
+}
+
+int tfa_fwd_kvcache(const tfa_kvcache_params* p, int splits, float* workspace, void* stream) {
+  return kvcache_run(kvc_call(p, nullptr, TFA_PACK_GQA_AUTO, splits), workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_plan(const tfa_kvcache_params* p, int splits, int* grid, int* block, int* lds_bytes) {
+  return kvcache_plan(kvc_call(p, nullptr, TFA_PACK_GQA_AUTO, splits), grid, block, lds_bytes);
+}
+long long tfa_fwd_kvcache_workspace(const tfa_kvcache_params* p, int splits) { return kvcache_workspace(kvc_call(p, nullptr, TFA_PACK_GQA_AUTO, splits)); }
+
+// the e4m3 cache: the second struct is required (its NULL descale pointers mean 1.0)
+int tfa_fwd_kvcache_fp8(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, float* workspace, void* stream) {
+  return q8 ? kvcache_run(kvc_call(p, q8, TFA_PACK_GQA_AUTO, splits), workspace, stream, nullptr, false) : TFA_ERR_NULL;
+}
+int tfa_fwd_kvcache_fp8_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits, int* grid, int* block, int* lds_bytes) {
+  return q8 ? kvcache_plan(kvc_call(p, q8, TFA_PACK_GQA_AUTO, splits), grid, block, lds_bytes) : TFA_ERR_NULL;
+}
+long long tfa_fwd_kvcache_fp8_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int splits) {
+  return q8 ? kvcache_workspace(kvc_call(p, q8, TFA_PACK_GQA_AUTO, splits)) : (long long)TFA_ERR_NULL;
+}
+
+// the same calls with the GQA packing chosen by the caller (q8 == NULL: the 16-bit cache)
+int tfa_fwd_kvcache_pack(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
+  return kvcache_run(kvc_call(p, q8, pack_gqa, splits), workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_pack_plan(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
+  return kvcache_plan(kvc_call(p, q8, pack_gqa, splits), grid, block, lds_bytes);
+}
+long long tfa_fwd_kvcache_pack_workspace(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) {
+  return kvcache_workspace(kvc_call(p, q8, pack_gqa, splits));
+}
+
+static int kvcache_suggest_splits(const tfa_kvcache_params* p, int pack) {
+  if (!p || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->Nq <= 0 || p->capacity <= 0 || p->H % p->Hk != 0) return 1;
+  if (pack != TFA_PACK_GQA_AUTO && pack != TFA_PACK_GQA_ON && pack != TFA_PACK_GQA_OFF) return 1;
+  // tfa_fwd_suggest_splits' rule on host-known sizes: the capacity stands in for the lengths (which live on the device)
+  const bool packed = pack != TFA_PACK_GQA_OFF && kvcache_packs(p);     // one row per sequence: a non-causal problem
+  const bool packed_rows = kvcache_packs_positions(p, pack);            // several: workgroups counted from the packed geometry
+  const long long blocks = (packed || packed_rows) ? tfa::sat_mul((long long)p->B * p->Hk, ((long long)p->Nq * (p->H / p->Hk) + 127) / 128)
+                                                   : tfa::sat_mul((long long)p->B * p->H, ((long long)p->Nq + 127) / 128);
+  return suggest_splits_for(blocks, p->capacity, p->is_causal && !packed && (long long)p->Nq * 4 > p->capacity);
+}
+int tfa_fwd_kvcache_suggest_splits(const tfa_kvcache_params* p) { return kvcache_suggest_splits(p, TFA_PACK_GQA_AUTO); }
+int tfa_fwd_kvcache_pack_suggest_splits(const tfa_kvcache_params* p, int pack_gqa) { return kvcache_suggest_splits(p, pack_gqa); }
+
+// ---- the varlen-q form (tfa.h: tfa_fwd_kvcache_varlen): q packed (total_q, H, D), sequence b's rows read from cu_seqlens_q on the device ----------------------------
+int tfa_fwd_kvcache_varlen(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, float* workspace, void* stream) {
+  return kvcache_run(kvc_varlen_call(p, vq, q8, pack_gqa, splits, nullptr, false), workspace, stream, nullptr, false);
+}
+int tfa_fwd_kvcache_varlen_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block, int* lds_bytes) {
+  return kvcache_plan(kvc_varlen_call(p, vq, q8, pack_gqa, splits, nullptr, false), grid, block, lds_bytes);
+}
+long long tfa_fwd_kvcache_varlen_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits) {
+  return kvcache_workspace(kvc_varlen_call(p, vq, q8, pack_gqa, splits, nullptr, false));
 }
 int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa) {
   if (!p || !vq || p->B <= 0 || p->H <= 0 || p->Hk <= 0 || p->capacity <= 0 || p->H % p->Hk != 0 || vq->max_seqlen_q <= 0 || vq->total_q <= 0) return 1;
@@ -1217,13 +1174,7 @@ int tfa_fwd_kvcache_varlen_suggest_splits(const tfa_kvcache_params* p, const tfa
   const long long nmb = ((long long)vq->max_seqlen_q * gp + 127) / 128;
   const long long launched = (long long)p->B * nmb, filled = ((long long)vq->total_q * gp + 127) / 128 + p->B;
   const long long blocks = tfa::sat_mul(packed ? p->Hk : p->H, launched < filled ? launched : filled);
-  const int cus = num_cus();
-  if (blocks > cus / 2 || p->capacity < 4096) return 1;   // (blocks * 2 > cus, without the product)
-  if (p->is_causal && vq->max_seqlen_q > 1 && (long long)vq->max_seqlen_q * 4 > p->capacity) return 1;
-  long long s = blocks * 4 > cus ? 2 * cus / blocks : cus / blocks;
-  if (s > p->capacity / 1024) s = p->capacity / 1024;
-  if (s > 32) s = 32;
-  return s >= 2 ? (int)s : 1;
+  return suggest_splits_for(blocks, p->capacity, p->is_causal && vq->max_seqlen_q > 1 && (long long)vq->max_seqlen_q * 4 > p->capacity);
 }
 
 // ---- the scheduled form (tfa.h: tfa_kvcache_varlen_schedule, tfa_fwd_kvcache_varlen_sched): the work items of a list built on the device ---------------------------
@@ -1276,47 +1227,24 @@ int tfa_kvcache_varlen_schedule_plan(const tfa_kvcache_params* p, const tfa_kvca
 }
 int tfa_fwd_kvcache_varlen_sched(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, const int32_t* metadata,
                                  float* workspace, void* stream) {
-  return kvcache_vq_run(p, vq, q8, pack_gqa, splits, workspace, stream, nullptr, false, metadata, true);
+  return kvcache_run(kvc_varlen_call(p, vq, q8, pack_gqa, splits, metadata, true), workspace, stream, nullptr, false);
 }
 int tfa_fwd_kvcache_varlen_sched_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int splits, int* grid, int* block,
                                       int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_vq_run(p, vq, q8, pack_gqa, splits, nullptr, nullptr, &g, true, nullptr, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
+  return kvcache_plan(kvc_varlen_call(p, vq, q8, pack_gqa, splits, nullptr, true), grid, block, lds_bytes);
 }
 
-// ---- the windowed form (tfa.h: tfa_fwd_kvcache_window): one entry point over the 4-D, packed-q and scheduled host paths above ------------------------------------
-static int kvcache_window_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, int left, int splits, const int32_t* meta,
-                              bool sched, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
-  if (!p) return TFA_ERR_NULL;
-  if (left < 0 || !p->is_causal || (sched && !vq)) return TFA_ERR_SHAPE;
-  if (vq) return kvcache_vq_run(p, vq, q8, pack, splits, workspace, stream, geom, dry, meta, sched, left);
-  return kvcache_run(p, q8, pack, splits, workspace, stream, geom, dry, left);
-}
+// ---- the windowed form (tfa.h: tfa_fwd_kvcache_window): one entry point over the 4-D, packed-q and scheduled layouts ------------------------------------------------
 int tfa_fwd_kvcache_window(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, const int32_t* metadata,
                            float* workspace, void* stream) {
-  return kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, metadata, metadata != nullptr, workspace, stream, nullptr, false);
+  return kvcache_run(kvc_window_call(p, vq, q8, pack_gqa, window_left, splits, metadata, metadata != nullptr), workspace, stream, nullptr, false);
 }
 int tfa_fwd_kvcache_window_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits, int scheduled,
                                 int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, nullptr, scheduled != 0, nullptr, nullptr, &g, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
+  return kvcache_plan(kvc_window_call(p, vq, q8, pack_gqa, window_left, splits, nullptr, scheduled != 0), grid, block, lds_bytes);
 }
 long long tfa_fwd_kvcache_window_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, int window_left, int splits) {
-  const int st = kvcache_window_run(p, vq, q8, pack_gqa, window_left, splits, nullptr, false, nullptr, nullptr, nullptr, true);
-  if (st != TFA_OK) return st;
-  const int ns = kvcache_chunks(p, splits);
-  if (ns <= 1) return 0;
-  return vq ? (long long)ns * p->H * vq->total_q * (p->D + 1) : (long long)ns * p->B * p->H * p->Nq * (p->D + 1);
+  return kvcache_workspace(kvc_window_call(p, vq, q8, pack_gqa, window_left, splits, nullptr, false));
 }
 int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, int window_left) {
   if (!p || window_left < 0 || p->capacity <= 0) return 1;
@@ -1328,37 +1256,18 @@ int tfa_fwd_kvcache_window_suggest_splits(const tfa_kvcache_params* p, const tfa
   return vq ? tfa_fwd_kvcache_varlen_suggest_splits(&w, vq, pack_gqa) : kvcache_suggest_splits(&w, pack_gqa);
 }
 
-// ---- the tree form (tfa.h: tfa_fwd_kvcache_tree): one entry point over the same three host paths; the mask removes no tile, so everything but the kernel is the form's --------
-static int kvcache_tree_run(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack, const tfa_kvcache_tree* tree, int splits,
-                            const int32_t* meta, bool sched, float* workspace, void* stream, tfa::LaunchGeom* geom, bool dry) {
-  if (!p || !tree || !tree->mask) return TFA_ERR_NULL;
-  if (!p->is_causal || (sched && !vq)) return TFA_ERR_SHAPE;
-  if ((uintptr_t)tree->mask & 7) return TFA_ERR_ALIGN;
-  if (tree->row_stride < 0 || (!vq && tree->batch_stride < 0)) return TFA_ERR_STRIDE;
-  if (vq) return kvcache_vq_run(p, vq, q8, pack, splits, workspace, stream, geom, dry, meta, sched, -1, tree);
-  return kvcache_run(p, q8, pack, splits, workspace, stream, geom, dry, -1, tree);
-}
+// ---- the tree form (tfa.h: tfa_fwd_kvcache_tree): one entry point over the same three layouts; the mask removes no tile, so everything but the kernel is the form's --------
 int tfa_fwd_kvcache_tree(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits,
                          const int32_t* metadata, float* workspace, void* stream) {
-  return kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, metadata, metadata != nullptr, workspace, stream, nullptr, false);
+  return kvcache_run(kvc_tree_call(p, vq, q8, pack_gqa, tree, splits, metadata, metadata != nullptr), workspace, stream, nullptr, false);
 }
 int tfa_fwd_kvcache_tree_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits,
                               int scheduled, int* grid, int* block, int* lds_bytes) {
-  tfa::LaunchGeom g{0, 0, 0};
-  const int st = kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, nullptr, scheduled != 0, nullptr, nullptr, &g, true);
-  if (st != TFA_OK) return st;
-  if (grid) *grid = g.grid;
-  if (block) *block = g.block;
-  if (lds_bytes) *lds_bytes = g.lds;
-  return TFA_OK;
+  return kvcache_plan(kvc_tree_call(p, vq, q8, pack_gqa, tree, splits, nullptr, scheduled != 0), grid, block, lds_bytes);
 }
 long long tfa_fwd_kvcache_tree_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree,
                                          int splits) {
-  const int st = kvcache_tree_run(p, vq, q8, pack_gqa, tree, splits, nullptr, false, nullptr, nullptr, nullptr, true);
-  if (st != TFA_OK) return st;
-  const int ns = kvcache_chunks(p, splits);
-  if (ns <= 1) return 0;
-  return vq ? (long long)ns * p->H * vq->total_q * (p->D + 1) : (long long)ns * p->B * p->H * p->Nq * (p->D + 1);
+  return kvcache_workspace(kvc_tree_call(p, vq, q8, pack_gqa, tree, splits, nullptr, false));
 }
 int tfa_fwd_kvcache_tree_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, const tfa_kvcache_tree* tree) {
   (void)tree;                                              // the underlying form's rule: the mask removes no tile

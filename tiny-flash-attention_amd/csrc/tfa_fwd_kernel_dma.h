@@ -281,7 +281,7 @@ static __device__ __forceinline__ u32x4 kv8_decode(u32x2 s) {
 // requested BEFORE the current block's epilogue, so its prologue latency hides behind the O stores.
 // With G = number of items the same code degenerates to one item per workgroup.
 // The kernel's body is tfa_fwd_kernel_dma_body.inc, included by its two entry points: fwd_kernel_dma (KArgs: every launch up to tfa_fwd_splitkv) and the KV-cache form
-// fwd_kernel_dma_kvc (KvcArgs, VF_KVCACHE) at the end of this file.  The KV-cache statements of the body sit in `if constexpr (KVC)` and read their arguments through
+// fwd_kernel_dma_kvc (KvcArgs and the structs behind it, VF_KVCACHE) at the end of this file.  The KV-cache statements of the body sit in `if constexpr (KVC)` and read their arguments through
 // KvcView<KVC>::of(p) — a dependent expression in fwd_kernel_dma, never instantiated there: its instantiations compile to the instructions they had before the form existed.
 template <bool KVC>
 struct KvcView {
@@ -297,56 +297,14 @@ __global__ __launch_bounds__(NW * 64, D > 128 ? 1 : 2) void fwd_kernel_dma(const
 #include "tfa_fwd_kernel_dma_body.inc"
 }
 
-// The KV-cache form (tfa_fwd_kvcache): the split-KV instantiation's tile loop — four waves, two LDS buffers — with the lengths, the chunks and the pages formed on
-// the device.  NT: K/V streamed with the non-temporal hint (caches beyond the memory-side cache, every byte read by one workgroup — the host decides)
-template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc(const KvcArgs p) {
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (NT ? VF_DMA_NT : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-
-// The e4m3 form of the KV-cache form (tfa_fwd_kvcache_fp8): T is the type of q, out and of the decoded tiles
-template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8(const Kvc8Args p) {
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-
-// The packed forms of the two (GQA query heads as position-major rows: KvcPacked above)
-template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_pack(const KvcPacked<KvcArgs> p) {
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (NT ? VF_DMA_NT : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc8_pack(const KvcPacked<Kvc8Args> p) {
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | VF_KV_E4M3 | (NT ? VF_DMA_NT : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-
-// The varlen-q forms of the four (packed ragged query rows: KvcVarlenQ above).  Args: KvcVarlenQ<> of KvcArgs, Kvc8Args or their KvcPacked<>; the e4m3 cache side
-// is the Args' own (Kvc8Args among its bases).  The scheduled forms (KvcSched<KvcVarlenQ<>>) are further instantiations of this entry point
+// The KV-cache form (tfa_fwd_kvcache and every entry point behind it): the split-KV instantiation's tile loop — four waves, two LDS buffers — with the lengths, the
+// chunks and the pages formed on the device.  ONE entry point for every form: Args is any of the argument structs above (tfa_launch.h: TFA_KVC_FORMS names them) and
+// the body reads what the form adds through the traits beside each struct; the e4m3 cache side is the Args' own (Kvc8Args among its bases; T is then the type of q,
+// out and of the decoded tiles).  NT: K/V streamed with the non-temporal hint (caches beyond the memory-side cache, every byte read by one workgroup — the host
+// decides).  The windowed and tree forms are instantiated causal and without the hint only (tfa_kvc_inst.inc)
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT, typename Args>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_vq(const Args p) {
+__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc(const Args p) {
   constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0) | (NT ? VF_DMA_NT : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-
-// The windowed forms of all twelve (a sliding window over the cache: KvcWindow above).  Args: KvcWindow<> of any form's struct; causal only, no non-temporal twin
-// (a window's range is small)
-template <typename T, int D, bool F32OUT, typename Args>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_win(const Args p) {
-  constexpr bool CAUSAL = true;
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0);
-#include "tfa_fwd_kernel_dma_body.inc"
-}
-
-// The tree forms of all twelve (a speculative tree's visibility words over the step's new keys: KvcTree above).  Args: KvcTree<> of any form's struct; causal only,
-// no non-temporal twin
-template <typename T, int D, bool F32OUT, typename Args>
-__global__ __launch_bounds__(256, 2) void fwd_kernel_dma_kvc_tree(const Args p) {
-  constexpr bool CAUSAL = true;
-  constexpr int NW = 4, AB = 0, VF = VF_PAIR | VF_2BUF | VF_KVCACHE | (std::is_base_of<Kvc8Args, Args>::value ? VF_KV_E4M3 : 0);
 #include "tfa_fwd_kernel_dma_body.inc"
 }
 

@@ -1,22 +1,26 @@
-// tfa_kvc_inst.inc — instantiates the KV-cache form of the LDS-DMA kernel (tfa_fwd_kernel_dma.h: fwd_kernel_dma_kvc) for one (TFA_T, TFA_D): causal and not,
-// fp32 partials (split) with and without the non-temporal hint, and the 16-bit direct output of a single chunk.  Compiled as the units tfa_kvc_inst_<dtype>_<W>.
+// tfa_kvc_inst.inc — instantiates one form of the KV-cache kernel (tfa_fwd_kernel_dma.h: fwd_kernel_dma_kvc; tfa_launch.h: TFA_KVC_FORMS) for one (TFA_T, TFA_D):
+// causal and not, fp32 partials (split) with and without the non-temporal hint, and the 16-bit direct output of a single chunk.  Compiled as the units
+// tfa_<kvc|kvc8>_inst[_win|_tree][_pack][_vq[_sched]]_<dtype>_<W>: every word of the name is one define below (Makefile: W_<word>).
 #include "tfa_launch.h"
 #include "tfa_kvcache.h"
+#ifndef TFA_KVC_FP8
+#define TFA_KVC_FP8 0        // 1: the e4m3 cache (tfa_kvc8_inst_*) — Kvc8Args in KvcArgs' place; T is the type of q and out
+#endif
 #ifndef TFA_KVC_PACK
-#define TFA_KVC_PACK 0       // 1: the unit of the packed form (tfa_kvc_inst_pack_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc_pack and its arguments
+#define TFA_KVC_PACK 0       // 1: the packed form (*_pack_*) — KvcPacked<> of the cache side's struct
 #endif
 #ifndef TFA_KVC_VQ
-#define TFA_KVC_VQ 0         // 1: the unit of the varlen-q form (tfa_kvc_inst_vq_<dtype>_<W>, tfa_kvc_inst_pack_vq_<dtype>_<W>) — the same launchers over fwd_kernel_dma_kvc_vq
+#define TFA_KVC_VQ 0         // 1: the varlen-q form (*_vq_*) — KvcVarlenQ<> behind that
 #endif
 #ifndef TFA_KVC_SCHED
-#define TFA_KVC_SCHED 0      // 1 (with TFA_KVC_VQ): the unit of the scheduled form (tfa_kvc_inst_vq_sched_<dtype>_<W>, tfa_kvc_inst_pack_vq_sched_<dtype>_<W>) — fwd_kernel_dma_kvc_vq over KvcSched<>
+#define TFA_KVC_SCHED 0      // 1 (with TFA_KVC_VQ): the scheduled form (*_vq_sched_*) — KvcSched<> behind that
 #endif
 #ifndef TFA_KVC_WIN
-#define TFA_KVC_WIN 0        // 1 (with any of the above): the unit of the form's windowed form (tfa_kvc_inst_win_*) — fwd_kernel_dma_kvc_win over KvcWindow<> of the form's arguments:
-#endif                       // the causal template only, the 16-bit direct output and the fp32 partials, no non-temporal twin
+#define TFA_KVC_WIN 0        // 1 (with any of the above): the form's windowed form (*_inst_win_*) — KvcWindow<> behind them all: the causal template only, the 16-bit
+#endif                       // direct output and the fp32 partials, no non-temporal twin
 #ifndef TFA_KVC_TREE
-#define TFA_KVC_TREE 0       // 1 (with any of the forms, not with TFA_KVC_WIN): the unit of the form's tree form (tfa_kvc_inst_tree_*) — fwd_kernel_dma_kvc_tree over KvcTree<> of the
-#endif                       // form's arguments: the causal template only, the 16-bit direct output and the fp32 partials, no non-temporal twin
+#define TFA_KVC_TREE 0       // 1 (with any of the forms, not with TFA_KVC_WIN): the form's tree form (*_inst_tree_*) — KvcTree<> behind them all: the causal template only,
+#endif                       // the 16-bit direct output and the fp32 partials, no non-temporal twin
 #if TFA_KVC_TREE && TFA_KVC_WIN
 #error "the tree form has no windowed form"
 #endif
@@ -26,29 +30,19 @@
 
 namespace tfa {
 
-// the arguments of this unit's kernels: the form's struct, behind it the packed form's (TFA_KVC_PACK), behind both the varlen-q form's (TFA_KVC_VQ)
-using UnitBase = std::conditional_t<TFA_KVC_PACK != 0, KvcPacked<KvcArgs>, KvcArgs>;
-using UnitVq = std::conditional_t<TFA_KVC_VQ != 0, KvcVarlenQ<UnitBase>, UnitBase>;
-using UnitForm = std::conditional_t<TFA_KVC_SCHED != 0, KvcSched<UnitVq>, UnitVq>;     // ... and behind the three the scheduled form's (TFA_KVC_SCHED)
-using UnitWin = std::conditional_t<TFA_KVC_WIN != 0, KvcWindow<UnitForm>, UnitForm>;   // ... and behind them all the window's (TFA_KVC_WIN)
-using UnitArgs = std::conditional_t<TFA_KVC_TREE != 0, KvcTree<UnitWin>, UnitWin>;     // ... or the tree's (TFA_KVC_TREE)
+// the arguments of this unit's kernels
+using UnitArgs = KvcForm<TFA_KVC_FP8 != 0, TFA_KVC_PACK != 0, TFA_KVC_SCHED ? KVC_SCHED : TFA_KVC_VQ ? KVC_VQ : KVC_PLAIN,
+                         TFA_KVC_WIN ? KVC_WIN : TFA_KVC_TREE ? KVC_TREE : KVC_NONE>::Args;
 
 template <typename T, int D, bool CAUSAL, bool F32OUT, bool NT>
 static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, LaunchGeom* geom, bool dry) {
   constexpr int lds = 4 * 64 * D * 2;                          // two K and two V tile buffers
 #if TFA_KVC_WIN
   static_assert(CAUSAL && !NT, "the windowed form: causal, no non-temporal twin");
-  auto kern = fwd_kernel_dma_kvc_win<T, D, F32OUT, UnitArgs>;
 #elif TFA_KVC_TREE
   static_assert(CAUSAL && !NT, "the tree form: causal, no non-temporal twin");
-  auto kern = fwd_kernel_dma_kvc_tree<T, D, F32OUT, UnitArgs>;
-#elif TFA_KVC_VQ
-  auto kern = fwd_kernel_dma_kvc_vq<T, D, CAUSAL, F32OUT, NT, UnitArgs>;
-#elif TFA_KVC_PACK
-  auto kern = fwd_kernel_dma_kvc_pack<T, D, CAUSAL, F32OUT, NT>;
-#else
-  auto kern = fwd_kernel_dma_kvc<T, D, CAUSAL, F32OUT, NT>;
 #endif
+  auto kern = fwd_kernel_dma_kvc<T, D, CAUSAL, F32OUT, NT, UnitArgs>;
   const int grid = a_in.nbh * a_in.nwork * (a_in.nsplit > 1 ? a_in.nsplit : 1);
   if (geom) { geom->grid = grid; geom->block = 256; geom->lds = lds; }
   if (dry) return hipSuccess;
@@ -62,30 +56,16 @@ static hipError_t launch_kvc_one(const UnitArgs& a_in, hipStream_t stream, Launc
   return hipGetLastError();
 }
 
-#if TFA_KVC_WIN
 template <>
-hipError_t launch_kvc_win<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
+hipError_t launch_kvc<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool causal, bool f32out, bool nt, hipStream_t s, LaunchGeom* g, bool dry) {
+#if TFA_KVC_WIN || TFA_KVC_TREE
+  if (!causal || nt) return hipErrorInvalidValue;
   return f32out ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry);
-}
-#elif TFA_KVC_TREE
-template <>
-hipError_t launch_kvc_tree<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a, bool f32out, hipStream_t s, LaunchGeom* g, bool dry) {
-  return f32out ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry);
-}
 #else
-template <>
-#if TFA_KVC_VQ
-hipError_t launch_kvc_vq<TFA_T, TFA_D, UnitArgs>(const UnitArgs& a,
-#elif TFA_KVC_PACK
-hipError_t launch_kvc_pack<TFA_T, TFA_D>(const KvcPacked<KvcArgs>& a,
-#else
-hipError_t launch_kvc<TFA_T, TFA_D>(const KvcArgs& a,
-#endif
-                                        bool causal, bool f32out, bool nt, hipStream_t s, LaunchGeom* g, bool dry) {
   if (!f32out) return causal ? launch_kvc_one<TFA_T, TFA_D, true, false, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, false, false>(a, s, g, dry);
   if (nt) return causal ? launch_kvc_one<TFA_T, TFA_D, true, true, true>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, true, true>(a, s, g, dry);
   return causal ? launch_kvc_one<TFA_T, TFA_D, true, true, false>(a, s, g, dry) : launch_kvc_one<TFA_T, TFA_D, false, true, false>(a, s, g, dry);
-}
 #endif
+}
 
 }  // namespace tfa

@@ -1,6 +1,6 @@
 // tfa_kvcache.h — host-side declarations of the K/V-cache path (include/tfa.h: tfa_fwd_kvcache, tfa_kvcache_append): the append kernel's
-// arguments and the launchers of the KV-cache form of the LDS-DMA kernel (tfa_fwd_kernel_dma.h: VF_KVCACHE, KvcArgs), one translation unit
-// per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.
+// arguments, beside the launcher of the KV-cache form of the LDS-DMA kernel (tfa_launch.h: launch_kvc over TFA_KVC_FORMS; tfa_fwd_kernel_dma.h: VF_KVCACHE,
+// KvcArgs), one translation unit per (form, dtype, width) — tfa_kvc_inst.inc.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

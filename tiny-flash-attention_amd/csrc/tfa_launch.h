@@ -193,68 +193,47 @@ static hipError_t launch_one_il(const KArgs& a, hipStream_t stream, LaunchGeom* 
 template <typename T>
 hipError_t launch_splitkv_wide(const KArgs& a, bool causal, hipStream_t stream, LaunchGeom* geom, bool dry);
 
-// The KV-cache form of the LDS-DMA kernel (tfa_fwd_kvcache; fwd_kernel_dma_kvc): one translation unit per (dtype, width) — tfa_kvc_inst_<dtype>_<W>.
-// f32out: fp32 partials of a split launch (nt: with the non-temporal hint), else the 16-bit output of a single chunk
-template <typename T, int D>
-hipError_t launch_kvc(const KvcArgs& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVC_UNITS(T, D) template <> hipError_t launch_kvc<T, D>(const KvcArgs&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
-TFA_KVC_UNITS(__bf16, 64) TFA_KVC_UNITS(__bf16, 128) TFA_KVC_UNITS(_Float16, 64) TFA_KVC_UNITS(_Float16, 128)
+// The KV-cache form of the LDS-DMA kernel (tfa_fwd_kvcache and every entry point behind it; fwd_kernel_dma_kvc).  A form is its argument struct
+// (tfa_fwd_kernel_dma.h): the cache side — KvcArgs or, e4m3, Kvc8Args — behind it KvcPacked<> (GQA heads as position-major rows) or not, behind that the q layout —
+// 4-D, KvcVarlenQ<> (packed ragged rows) or KvcSched<KvcVarlenQ<>> (the work items of a device-built list) — and last the rider: none, KvcWindow<> or KvcTree<>.
+enum : int { KVC_PLAIN = 0, KVC_VQ = 1, KVC_SCHED = 2 };   // the q layout
+enum : int { KVC_NONE = 0, KVC_WIN = 1, KVC_TREE = 2 };    // the rider
+template <bool FP8_, bool PACK_, int LAYOUT_, int RIDER_>
+struct KvcForm {
+  using Cache = std::conditional_t<FP8_, Kvc8Args, KvcArgs>;
+  using Base = std::conditional_t<PACK_, KvcPacked<Cache>, Cache>;
+  using Vq = std::conditional_t<LAYOUT_ != KVC_PLAIN, KvcVarlenQ<Base>, Base>;
+  using Layout = std::conditional_t<LAYOUT_ == KVC_SCHED, KvcSched<Vq>, Vq>;
+  using Args = std::conditional_t<RIDER_ == KVC_WIN, KvcWindow<Layout>, std::conditional_t<RIDER_ == KVC_TREE, KvcTree<Layout>, Layout>>;
+  static constexpr int index = ((FP8_ * 2 + PACK_) * 3 + LAYOUT_) * 3 + RIDER_;
+};
+// THE list of the forms, X(fp8, packed, layout, rider): 36 argument structs, each one instantiation unit per (dtype, width) — tfa_kvc_inst.inc compiled as
+// tfa_<kvc|kvc8>_inst[_win|_tree][_pack][_vq[_sched]]_<dtype>_<W>, the Makefile's words of those names carrying the same four choices.  The declarations below and
+// by_kvc_form's switch come from here
+#define TFA_KVC_LAYOUTS_(X, FP8, PACK, RIDER) X(FP8, PACK, KVC_PLAIN, RIDER) X(FP8, PACK, KVC_VQ, RIDER) X(FP8, PACK, KVC_SCHED, RIDER)
+#define TFA_KVC_RIDERS_(X, FP8, PACK) TFA_KVC_LAYOUTS_(X, FP8, PACK, KVC_NONE) TFA_KVC_LAYOUTS_(X, FP8, PACK, KVC_WIN) TFA_KVC_LAYOUTS_(X, FP8, PACK, KVC_TREE)
+#define TFA_KVC_FORMS(X) TFA_KVC_RIDERS_(X, false, false) TFA_KVC_RIDERS_(X, true, false) TFA_KVC_RIDERS_(X, false, true) TFA_KVC_RIDERS_(X, true, true)
+// f32out: fp32 partials of a split launch (nt: with the non-temporal hint), else the 16-bit output of a single chunk.  The windowed and tree forms exist causal and
+// without the hint only: their launchers refuse anything else (hipErrorInvalidValue)
+template <typename T, int D, typename Args>
+hipError_t launch_kvc(const Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
+#define TFA_KVC_UNIT(T, D, FP8, PACK, LAYOUT, RIDER) \
+  template <> hipError_t launch_kvc<T, D, KvcForm<FP8, PACK, LAYOUT, RIDER>::Args>(const KvcForm<FP8, PACK, LAYOUT, RIDER>::Args&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
+#define TFA_KVC_UNITS(FP8, PACK, LAYOUT, RIDER) TFA_FORM_SHAPES(TFA_KVC_UNIT, FP8, PACK, LAYOUT, RIDER)
+TFA_KVC_FORMS(TFA_KVC_UNITS)
 #undef TFA_KVC_UNITS
-// ... and its e4m3 form (tfa_fwd_kvcache_fp8; fwd_kernel_dma_kvc8): tfa_kvc8_inst_<dtype>_<W>, T the type of q and out
-template <typename T, int D>
-hipError_t launch_kvc8(const Kvc8Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVC8_UNITS(T, D) template <> hipError_t launch_kvc8<T, D>(const Kvc8Args&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
-TFA_KVC8_UNITS(__bf16, 64) TFA_KVC8_UNITS(__bf16, 128) TFA_KVC8_UNITS(_Float16, 64) TFA_KVC8_UNITS(_Float16, 128)
-#undef TFA_KVC8_UNITS
-// ... and the packed forms of both (tfa_fwd_kvcache_pack; fwd_kernel_dma_kvc_pack / _kvc8_pack): units of their own, tfa_kvc_inst_pack_<dtype>_<W> and
-// tfa_kvc8_inst_pack_<dtype>_<W> — the same .inc files compiled with TFA_KVC_PACK
-template <typename T, int D>
-hipError_t launch_kvc_pack(const KvcPacked<KvcArgs>& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
-template <typename T, int D>
-hipError_t launch_kvc8_pack(const KvcPacked<Kvc8Args>& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVCP_UNITS(T, D)                                                                                                          \
-  template <> hipError_t launch_kvc_pack<T, D>(const KvcPacked<KvcArgs>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);          \
-  template <> hipError_t launch_kvc8_pack<T, D>(const KvcPacked<Kvc8Args>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
-TFA_KVCP_UNITS(__bf16, 64) TFA_KVCP_UNITS(__bf16, 128) TFA_KVCP_UNITS(_Float16, 64) TFA_KVCP_UNITS(_Float16, 128)
-#undef TFA_KVCP_UNITS
-// ... and the varlen-q forms of the four (tfa_fwd_kvcache_varlen; fwd_kernel_dma_kvc_vq): units of their own, tfa_kvc_inst_vq_*, tfa_kvc_inst_pack_vq_*, tfa_kvc8_inst_vq_*
-// and tfa_kvc8_inst_pack_vq_* — the same .inc files compiled with TFA_KVC_VQ.  Args: KvcVarlenQ<> of the form's struct
-template <typename T, int D, typename Args>
-hipError_t launch_kvc_vq(const Args& a, bool causal, bool f32out, bool nt, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVCVQ_UNIT(T, D, A) template <> hipError_t launch_kvc_vq<T, D, KvcVarlenQ<A>>(const KvcVarlenQ<A>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
-#define TFA_KVCVQ_UNITS(T, D) TFA_KVCVQ_UNIT(T, D, KvcArgs) TFA_KVCVQ_UNIT(T, D, Kvc8Args) TFA_KVCVQ_UNIT(T, D, KvcPacked<KvcArgs>) TFA_KVCVQ_UNIT(T, D, KvcPacked<Kvc8Args>)
-TFA_KVCVQ_UNITS(__bf16, 64) TFA_KVCVQ_UNITS(__bf16, 128) TFA_KVCVQ_UNITS(_Float16, 64) TFA_KVCVQ_UNITS(_Float16, 128)
-#undef TFA_KVCVQ_UNITS
-#undef TFA_KVCVQ_UNIT
-// ... and the scheduled forms of those (tfa_fwd_kvcache_varlen_sched; the same kernel template over KvcSched<KvcVarlenQ<>>): tfa_kvc_inst_vq_sched_*, tfa_kvc_inst_pack_vq_sched_*,
-// tfa_kvc8_inst_vq_sched_* and tfa_kvc8_inst_pack_vq_sched_* — the same .inc files compiled with TFA_KVC_VQ and TFA_KVC_SCHED
-#define TFA_KVCSC_UNIT(T, D, A) template <> hipError_t launch_kvc_vq<T, D, KvcSched<KvcVarlenQ<A>>>(const KvcSched<KvcVarlenQ<A>>&, bool, bool, bool, hipStream_t, LaunchGeom*, bool);
-#define TFA_KVCSC_UNITS(T, D) TFA_KVCSC_UNIT(T, D, KvcArgs) TFA_KVCSC_UNIT(T, D, Kvc8Args) TFA_KVCSC_UNIT(T, D, KvcPacked<KvcArgs>) TFA_KVCSC_UNIT(T, D, KvcPacked<Kvc8Args>)
-TFA_KVCSC_UNITS(__bf16, 64) TFA_KVCSC_UNITS(__bf16, 128) TFA_KVCSC_UNITS(_Float16, 64) TFA_KVCSC_UNITS(_Float16, 128)
-#undef TFA_KVCSC_UNITS
-#undef TFA_KVCSC_UNIT
-// ... and the windowed forms of all of them (tfa_fwd_kvcache_window; fwd_kernel_dma_kvc_win over KvcWindow<> of the form's struct): tfa_kvc_inst_win_* and tfa_kvc8_inst_win_* —
-// the same .inc files compiled with TFA_KVC_WIN besides the form's own defines.  Causal only; f32out: the fp32 partials of a split launch
-template <typename T, int D, typename Args>
-hipError_t launch_kvc_win(const Args& a, bool f32out, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVCW_UNIT(T, D, A) template <> hipError_t launch_kvc_win<T, D, KvcWindow<A>>(const KvcWindow<A>&, bool, hipStream_t, LaunchGeom*, bool);
-#define TFA_KVCW_FORMS(T, D, A) TFA_KVCW_UNIT(T, D, A) TFA_KVCW_UNIT(T, D, KvcVarlenQ<A>) TFA_KVCW_UNIT(T, D, KvcSched<KvcVarlenQ<A>>)
-#define TFA_KVCW_UNITS(T, D) TFA_KVCW_FORMS(T, D, KvcArgs) TFA_KVCW_FORMS(T, D, Kvc8Args) TFA_KVCW_FORMS(T, D, KvcPacked<KvcArgs>) TFA_KVCW_FORMS(T, D, KvcPacked<Kvc8Args>)
-TFA_KVCW_UNITS(__bf16, 64) TFA_KVCW_UNITS(__bf16, 128) TFA_KVCW_UNITS(_Float16, 64) TFA_KVCW_UNITS(_Float16, 128)
-#undef TFA_KVCW_UNITS
-#undef TFA_KVCW_FORMS
-#undef TFA_KVCW_UNIT
-// ... and the tree forms of all of them (tfa_fwd_kvcache_tree; fwd_kernel_dma_kvc_tree over KvcTree<> of the form's struct): tfa_kvc_inst_tree_* and tfa_kvc8_inst_tree_* —
-// the same .inc files compiled with TFA_KVC_TREE besides the form's own defines.  Causal only; f32out: the fp32 partials of a split launch
-template <typename T, int D, typename Args>
-hipError_t launch_kvc_tree(const Args& a, bool f32out, hipStream_t stream, LaunchGeom* geom, bool dry);
-#define TFA_KVCT_UNIT(T, D, A) template <> hipError_t launch_kvc_tree<T, D, KvcTree<A>>(const KvcTree<A>&, bool, hipStream_t, LaunchGeom*, bool);
-#define TFA_KVCT_FORMS(T, D, A) TFA_KVCT_UNIT(T, D, A) TFA_KVCT_UNIT(T, D, KvcVarlenQ<A>) TFA_KVCT_UNIT(T, D, KvcSched<KvcVarlenQ<A>>)
-#define TFA_KVCT_UNITS(T, D) TFA_KVCT_FORMS(T, D, KvcArgs) TFA_KVCT_FORMS(T, D, Kvc8Args) TFA_KVCT_FORMS(T, D, KvcPacked<KvcArgs>) TFA_KVCT_FORMS(T, D, KvcPacked<Kvc8Args>)
-TFA_KVCT_UNITS(__bf16, 64) TFA_KVCT_UNITS(__bf16, 128) TFA_KVCT_UNITS(_Float16, 64) TFA_KVCT_UNITS(_Float16, 128)
-#undef TFA_KVCT_UNITS
-#undef TFA_KVCT_FORMS
-#undef TFA_KVCT_UNIT
+#undef TFA_KVC_UNIT
+// The one run-time -> compile-time switch of the form: calls f(KvcForm<...>{})
+template <typename F>
+static inline auto by_kvc_form(bool fp8, bool packed, int layout, int rider, F&& f) {
+  switch (((fp8 * 2 + packed) * 3 + layout) * 3 + rider) {
+#define TFA_BY_KVC_FORM(FP8, PACK, LAYOUT, RIDER) \
+  case KvcForm<FP8, PACK, LAYOUT, RIDER>::index: return f(KvcForm<FP8, PACK, LAYOUT, RIDER>{});
+    TFA_KVC_FORMS(TFA_BY_KVC_FORM)
+#undef TFA_BY_KVC_FORM
+  }
+  return f(KvcForm<false, false, KVC_PLAIN, KVC_NONE>{});   // (never: layout and rider are the enums above)
+}
 
 // The x4 kernel: one translation unit per (dtype, width, causal, output type) — tfa_x4_inst_<dtype>_<D>_c<0|1>_o<16|32> —
 // each specialising launch_x4_piece; ablate != 0 selects a timing-only ablation (builds with -DTFA_X4_ABLATE).

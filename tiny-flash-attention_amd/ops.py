@@ -933,6 +933,122 @@ def _kvcache_params(q, k_cache, v_cache, out, lse, cache_seqlens, block_table, k
     return p
 
 
+def _kvcache_checks(name, q, k_cache, v_cache, k, v, cache_seqlens, block_table, num_splits, pack_gqa, k_descale, v_descale, B, H, D, packed_q):
+    """The checks the 4-D form of flash_attn_with_kvcache and its packed form (``packed_q``: q (total_q, H, D), B = cu_seqlens_q.numel() - 1) share — dtype, head
+    dim, fp8 pairing, descales, block_table, capacity, k / v, grad, cache_seqlens, num_splits, pack_gqa — in the order their refusals come; where a form has a check
+    or a wording of its own between two shared ones, it stands here under ``packed_q``.  Returns (fp8, Hk, capacity, cache_seqlens as a device tensor, num_splits)."""
+    is_b = " — B = cu_seqlens_q.numel() - 1" if packed_q else ""    # behind a shape that names B
+    is_b_ = is_b + " —" if packed_q else ""                         # ... in the middle of a sentence
+    if q.dtype == torch.float32:
+        raise ValueError(f"{name}: float16 / bfloat16 inputs only (no fp32 K/V-cache path)")
+    if q.dtype not in _DT:
+        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
+    if packed_q and q.shape[0] <= 0:
+        raise ValueError(f"{name}: q holds no row")
+    if D > 128:
+        raise ValueError(f"{name}: head dims up to 128 (got {D})")
+    if D % 8 != 0 or D < 8:
+        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
+        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype, or both caches be torch.float8_e4m3fn (got {q.dtype}, {k_cache.dtype}, "
+                        f"{v_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
+    if fp8 and D % 16 != 0:
+        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError(f"{name}: k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a {k_cache.dtype} cache)")
+    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
+        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    Hk = k_cache.shape[2]
+    if Hk <= 0 or H % Hk != 0:
+        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
+    for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name}: {n} must be a float32 tensor")
+        if tuple(t.shape) != (B, Hk) or t.device != q.device:
+            raise ValueError(f"{name}: {n} must have shape ({B}, {Hk}){is_b_} on q's device (got {tuple(t.shape)} on {t.device})")
+    if packed_q:
+        if q.stride(2) != 1 or k_cache.stride(3) != 1 or v_cache.stride(3) != 1:
+            raise ValueError(f"{name}: q, k_cache and v_cache must have unit stride along the head dim")
+        if (q.stride(0) * 2) % 16 != 0 or (q.stride(1) * 2) % 16 != 0:
+            raise ValueError(f"{name}: the rows of q must be 16-byte aligned (strides {q.stride(0)}, {q.stride(1)} elements)")
+    else:
+        for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+            if t.stride(3) != 1:
+                raise ValueError(f"{name}: {n} must have unit stride along the head dim")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks){is_b}")
+        if block_table.device != q.device or block_table.stride(1) != 1:
+            raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
+        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0:
+            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
+        capacity = block_table.shape[1] * k_cache.shape[1]
+    else:
+        if k_cache.shape[0] != B:
+            batch = f"the batch size cu_seqlens_q.numel() - 1 = {B}" if packed_q else f"q's batch size {B}"
+            raise ValueError(f"{name}: a contiguous cache must have {batch} (got {k_cache.shape[0]}); cache_batch_idx is not implemented")
+        capacity = k_cache.shape[1]
+    if capacity <= 0:
+        raise ValueError(f"{name}: the cache holds no key")
+    if (k is None) != (v is None):                        # (the packed form has refused k / v by now: kvcache_append_varlen is its append)
+        raise ValueError(f"{name}: k and v must be given together")
+    if k is not None:
+        if cache_seqlens is None:
+            raise ValueError(f"{name}: k / v are appended at cache_seqlens, which must then be given")
+        for n, t in (("k", k), ("v", v)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[0] != B or t.shape[2] != Hk or t.shape[3] != D or t.shape[1] < 1:
+                raise ValueError(f"{name}: {n} must have shape ({B}, n_new, {Hk}, {D})")
+            if t.dtype != q.dtype or t.stride(3) != 1 or t.device != q.device:
+                raise ValueError(f"{name}: {n} must have q's dtype and device and unit stride along the head dim")
+        if k.shape != v.shape:
+            raise ValueError(f"{name}: k and v must have one shape")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
+        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
+    if cache_seqlens is None:
+        cache_seqlens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
+    elif isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), int(cache_seqlens), dtype=torch.int32, device=q.device)
+    elif (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
+          or not cache_seqlens.is_contiguous() or cache_seqlens.device != q.device):
+        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},){is_b_} on q's device, a host int, or None")
+    num_splits = int(num_splits)
+    if num_splits < 0:
+        raise ValueError(f"{name}: num_splits must be >= 0 (0 = automatic; got {num_splits})")
+    if pack_gqa is not None and pack_gqa is not True and pack_gqa is not False:
+        raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
+    return fp8, Hk, capacity, cache_seqlens, num_splits
+
+
+def _kvcache_fp8_arg(fp8, k_descale, v_descale):
+    """The ``const tfa_kvcache_fp8*`` of a call: the TfaKvcacheFp8 of an e4m3 cache by reference (a None descale = 1.0), or None — NULL — for a 16-bit cache."""
+    if not fp8:
+        return None
+    p8 = _lib.TfaKvcacheFp8()
+    p8.format = _lib.TFA_KV_E4M3
+    for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
+        if t is not None:
+            setattr(p8, ptr, t.data_ptr())
+            strides[0], strides[1] = t.stride(0), t.stride(1)
+    return C.byref(p8)
+
+
+def _kvcache_launch(suggest, workspace, launch, num_splits, device):
+    """The tail of every K/V-cache call, over its entry-point family: ``suggest()`` answers ``num_splits=0``, ``workspace(splits)`` sizes the fp32 workspace (a
+    negative answer is the call's refusal), ``launch(splits, workspace pointer or None, stream)`` runs on the current stream of ``device``."""
+    if num_splits == 0:
+        num_splits = max(1, int(suggest()))
+    need = workspace(num_splits)
+    if need < 0:
+        _lib.check(int(need))
+    ws = torch.empty((int(need),), dtype=torch.float32, device=device) if need > 0 else None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(launch(num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None, softmax_scale=None, causal=False,
                             num_splits=0, return_softmax_lse=False, *, rotary_cos=None, rotary_sin=None, cache_batch_idx=None, cache_leftpad=None,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, pack_gqa=None, cu_seqlens_q=None, max_seqlen_q=None, tree_mask=None,
@@ -1046,78 +1162,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
             raise ValueError(f"{name}: {n} must be a 4-D tensor")
         if not t.is_cuda:
             raise RuntimeError(f"{n} must be a CUDA tensor")
-    if q.dtype == torch.float32:
-        raise ValueError(f"{name}: float16 / bfloat16 inputs only (no fp32 K/V-cache path)")
-    if q.dtype not in _DT:
-        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
     B, Nq, H, D = q.shape
-    if D > 128:
-        raise ValueError(f"{name}: head dims up to 128 (got {D})")
-    if D % 8 != 0 or D < 8:
-        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
-    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
-        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype, or both caches be torch.float8_e4m3fn (got {q.dtype}, {k_cache.dtype}, "
-                        f"{v_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
-    if fp8 and D % 16 != 0:
-        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
-    if not fp8 and (k_descale is not None or v_descale is not None):
-        raise ValueError(f"{name}: k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a {k_cache.dtype} cache)")
-    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
-        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    Hk = k_cache.shape[2]
-    if Hk <= 0 or H % Hk != 0:
-        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
-    for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"{name}: {n} must be a float32 tensor")
-        if tuple(t.shape) != (B, Hk) or t.device != q.device:
-            raise ValueError(f"{name}: {n} must have shape ({B}, {Hk}) on q's device (got {tuple(t.shape)} on {t.device})")
-    for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.stride(3) != 1:
-            raise ValueError(f"{name}: {n} must have unit stride along the head dim")
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks)")
-        if block_table.device != q.device or block_table.stride(1) != 1:
-            raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
-        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0:
-            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
-        capacity = block_table.shape[1] * k_cache.shape[1]
-    else:
-        if k_cache.shape[0] != B:
-            raise ValueError(f"{name}: a contiguous cache must have q's batch size {B} (got {k_cache.shape[0]}); cache_batch_idx is not implemented")
-        capacity = k_cache.shape[1]
-    if capacity <= 0:
-        raise ValueError(f"{name}: the cache holds no key")
-    if (k is None) != (v is None):
-        raise ValueError(f"{name}: k and v must be given together")
-    if k is not None:
-        if cache_seqlens is None:
-            raise ValueError(f"{name}: k / v are appended at cache_seqlens, which must then be given")
-        for n, t in (("k", k), ("v", v)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[0] != B or t.shape[2] != Hk or t.shape[3] != D or t.shape[1] < 1:
-                raise ValueError(f"{name}: {n} must have shape ({B}, n_new, {Hk}, {D})")
-            if t.dtype != q.dtype or t.stride(3) != 1 or t.device != q.device:
-                raise ValueError(f"{name}: {n} must have q's dtype and device and unit stride along the head dim")
-        if k.shape != v.shape:
-            raise ValueError(f"{name}: k and v must have one shape")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
-        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
-    if cache_seqlens is None:
-        cache_seqlens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
-    elif isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((B,), int(cache_seqlens), dtype=torch.int32, device=q.device)
-    elif (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
-          or not cache_seqlens.is_contiguous() or cache_seqlens.device != q.device):
-        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},) on q's device, a host int, or None")
-    num_splits = int(num_splits)
-    if num_splits < 0:
-        raise ValueError(f"{name}: num_splits must be >= 0 (0 = automatic; got {num_splits})")
-    if pack_gqa is not None and pack_gqa is not True and pack_gqa is not False:
-        raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
+    fp8, Hk, capacity, cache_seqlens, num_splits = _kvcache_checks(name, q, k_cache, v_cache, k, v, cache_seqlens, block_table, num_splits, pack_gqa, k_descale,
+                                                                   v_descale, B, H, D, False)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     tree = _tree_words(name, tree_mask, q.device, B, Nq) if tree_mask is not None else None
@@ -1125,41 +1172,21 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     L = _lib.lib()
     lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device) if return_softmax_lse else None
     dense = torch.empty((B, H, Nq, D), dtype=q.dtype, device=q.device)            # what the merge writes; one chunk: the kernel writes it the same way
-    p = _kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal)
+    p = C.byref(_kvcache_params(q, k_cache, v_cache, dense, lse, cache_seqlens, block_table, k, v, softmax_scale, causal))
+    q8 = _kvcache_fp8_arg(fp8, k_descale, v_descale)
     pack = None if pack_gqa is None else (_lib.TFA_PACK_GQA_ON if pack_gqa else _lib.TFA_PACK_GQA_OFF)   # None: the entry points without the argument
     left = _window_left(sliding_window, capacity)
     if left is not None or tree is not None:
-        _kvcache_window_call(L, p, None, k_descale, v_descale, fp8, _lib.TFA_PACK_GQA_AUTO if pack is None else pack, left, num_splits, None, q.device, tree)
-        out = dense.transpose(1, 2)
-        return (out, lse) if return_softmax_lse else out
-    if num_splits == 0:
-        num_splits = max(1, int(L.tfa_fwd_kvcache_suggest_splits(C.byref(p)) if pack is None else L.tfa_fwd_kvcache_pack_suggest_splits(C.byref(p), pack)))
-    p8 = None
-    if fp8:
-        p8 = _lib.TfaKvcacheFp8()
-        p8.format = _lib.TFA_KV_E4M3
-        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
-            if t is not None:
-                setattr(p8, ptr, t.data_ptr())
-                strides[0], strides[1] = t.stride(0), t.stride(1)
-    q8 = C.byref(p8) if fp8 else None
-    if pack is not None:
-        need = L.tfa_fwd_kvcache_pack_workspace(C.byref(p), q8, pack, num_splits)
+        _kvcache_rider_launch(L, p, None, q8, _lib.TFA_PACK_GQA_AUTO if pack is None else pack, left, tree, num_splits, None, q.device)
+    elif pack is not None:
+        _kvcache_launch(lambda: L.tfa_fwd_kvcache_pack_suggest_splits(p, pack), lambda s: L.tfa_fwd_kvcache_pack_workspace(p, q8, pack, s),
+                        lambda s, ws, stream: L.tfa_fwd_kvcache_pack(p, q8, pack, s, ws, stream), num_splits, q.device)
     elif fp8:
-        need = L.tfa_fwd_kvcache_fp8_workspace(C.byref(p), q8, num_splits)
+        _kvcache_launch(lambda: L.tfa_fwd_kvcache_suggest_splits(p), lambda s: L.tfa_fwd_kvcache_fp8_workspace(p, q8, s),
+                        lambda s, ws, stream: L.tfa_fwd_kvcache_fp8(p, q8, s, ws, stream), num_splits, q.device)
     else:
-        need = L.tfa_fwd_kvcache_workspace(C.byref(p), num_splits)
-    if need < 0:
-        _lib.check(int(need))
-    ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
-    with torch.cuda.device(q.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        if pack is not None:
-            _lib.check(L.tfa_fwd_kvcache_pack(C.byref(p), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
-        elif fp8:
-            _lib.check(L.tfa_fwd_kvcache_fp8(C.byref(p), q8, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
-        else:
-            _lib.check(L.tfa_fwd_kvcache(C.byref(p), num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        _kvcache_launch(lambda: L.tfa_fwd_kvcache_suggest_splits(p), lambda s: L.tfa_fwd_kvcache_workspace(p, s),
+                        lambda s, ws, stream: L.tfa_fwd_kvcache(p, s, ws, stream), num_splits, q.device)
     out = dense.transpose(1, 2)
     return (out, lse) if return_softmax_lse else out
 
@@ -1187,70 +1214,10 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
         raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of B + 1 entries")
     if cu_seqlens_q.device != q.device or not cu_seqlens_q.is_contiguous():
         raise ValueError(f"{name}: cu_seqlens_q must be contiguous and on q's device")
-    if q.dtype == torch.float32:
-        raise ValueError(f"{name}: float16 / bfloat16 inputs only (no fp32 K/V-cache path)")
-    if q.dtype not in _DT:
-        raise TypeError(f"{name}: float16 or bfloat16 only (got {q.dtype})")
     total_q, H, D = q.shape
     B = cu_seqlens_q.numel() - 1
-    if total_q <= 0:
-        raise ValueError(f"{name}: q holds no row")
-    if D > 128:
-        raise ValueError(f"{name}: head dims up to 128 (got {D})")
-    if D % 8 != 0 or D < 8:
-        raise ValueError(f"{name}: the head dim must be a multiple of 8 (got {D})")
-    fp8 = k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn
-    if not fp8 and (k_cache.dtype != q.dtype or v_cache.dtype != q.dtype):
-        raise TypeError(f"{name}: q, k_cache and v_cache must share one dtype, or both caches be torch.float8_e4m3fn (got {q.dtype}, {k_cache.dtype}, "
-                        f"{v_cache.dtype}; float8_e5m2 and float8_e4m3fnuz caches are not supported)")
-    if fp8 and D % 16 != 0:
-        raise ValueError(f"{name}: with an fp8 cache the head dim must be a multiple of 16 (got {D})")
-    if not fp8 and (k_descale is not None or v_descale is not None):
-        raise ValueError(f"{name}: k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a {k_cache.dtype} cache)")
-    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
-        raise ValueError(f"{name}: k_cache and v_cache must have one shape (..., Hk, {D}) (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    Hk = k_cache.shape[2]
-    if Hk <= 0 or H % Hk != 0:
-        raise ValueError(f"{name}: the K/V heads ({Hk}) must divide the query heads ({H})")
-    for n, t in (("k_descale", k_descale), ("v_descale", v_descale)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"{name}: {n} must be a float32 tensor")
-        if tuple(t.shape) != (B, Hk) or t.device != q.device:
-            raise ValueError(f"{name}: {n} must have shape ({B}, {Hk}) — B = cu_seqlens_q.numel() - 1 — on q's device (got {tuple(t.shape)} on {t.device})")
-    if q.stride(2) != 1 or k_cache.stride(3) != 1 or v_cache.stride(3) != 1:
-        raise ValueError(f"{name}: q, k_cache and v_cache must have unit stride along the head dim")
-    if (q.stride(0) * 2) % 16 != 0 or (q.stride(1) * 2) % 16 != 0:
-        raise ValueError(f"{name}: the rows of q must be 16-byte aligned (strides {q.stride(0)}, {q.stride(1)} elements)")
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-            raise ValueError(f"{name}: block_table must be an int32 tensor of shape ({B}, max_blocks) — B = cu_seqlens_q.numel() - 1")
-        if block_table.device != q.device or block_table.stride(1) != 1:
-            raise ValueError(f"{name}: block_table must be on q's device with unit stride along max_blocks")
-        if k_cache.shape[1] % 64 != 0 or k_cache.shape[1] <= 0:
-            raise ValueError(f"{name}: the page size must be a positive multiple of 64 (got {k_cache.shape[1]})")
-        capacity = block_table.shape[1] * k_cache.shape[1]
-    else:
-        if k_cache.shape[0] != B:
-            raise ValueError(f"{name}: a contiguous cache must have the batch size cu_seqlens_q.numel() - 1 = {B} (got {k_cache.shape[0]}); cache_batch_idx is not implemented")
-        capacity = k_cache.shape[1]
-    if capacity <= 0:
-        raise ValueError(f"{name}: the cache holds no key")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k_cache, v_cache)):
-        raise RuntimeError(f"{name} is not differentiable: an input requires grad (run it under torch.no_grad() or detach the inputs)")
-    if cache_seqlens is None:
-        cache_seqlens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
-    elif isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((B,), int(cache_seqlens), dtype=torch.int32, device=q.device)
-    elif (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
-          or not cache_seqlens.is_contiguous() or cache_seqlens.device != q.device):
-        raise ValueError(f"{name}: cache_seqlens must be a contiguous int32 tensor of shape ({B},) — B = cu_seqlens_q.numel() - 1 — on q's device, a host int, or None")
-    num_splits = int(num_splits)
-    if num_splits < 0:
-        raise ValueError(f"{name}: num_splits must be >= 0 (0 = automatic; got {num_splits})")
-    if pack_gqa is not None and pack_gqa is not True and pack_gqa is not False:
-        raise TypeError(f"{name}: pack_gqa must be None, True or False (got {pack_gqa!r})")
+    fp8, Hk, capacity, cache_seqlens, num_splits = _kvcache_checks(name, q, k_cache, v_cache, k, v, cache_seqlens, block_table, num_splits, pack_gqa, k_descale,
+                                                                   v_descale, B, H, D, True)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     if scheduler_metadata is not None:
@@ -1290,34 +1257,19 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
     vq = _lib.TfaKvcacheVarlenQ()
     vq.cu_seqlens_q = cu_seqlens_q.data_ptr()
     vq.max_seqlen_q, vq.total_q = int(max_seqlen_q), total_q
+    p, pv = C.byref(p), C.byref(vq)
+    q8 = _kvcache_fp8_arg(fp8, k_descale, v_descale)
     pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
     left = _window_left(sliding_window, capacity)
     if left is not None or tree is not None:
-        _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, q.device, tree)
-        out = dense.transpose(0, 1)
-        return (out, lse) if return_softmax_lse else out
-    if num_splits == 0:
-        num_splits = max(1, int(L.tfa_fwd_kvcache_varlen_suggest_splits(C.byref(p), C.byref(vq), pack)))
-    p8 = None
-    if fp8:
-        p8 = _lib.TfaKvcacheFp8()
-        p8.format = _lib.TFA_KV_E4M3
-        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
-            if t is not None:
-                setattr(p8, ptr, t.data_ptr())
-                strides[0], strides[1] = t.stride(0), t.stride(1)
-    q8 = C.byref(p8) if fp8 else None
-    need = L.tfa_fwd_kvcache_varlen_workspace(C.byref(p), C.byref(vq), q8, pack, num_splits)
-    if need < 0:
-        _lib.check(int(need))
-    ws = torch.empty((int(need),), dtype=torch.float32, device=q.device) if need > 0 else None
-    with torch.cuda.device(q.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        if scheduler_metadata is not None:
-            _lib.check(L.tfa_fwd_kvcache_varlen_sched(C.byref(p), C.byref(vq), q8, pack, num_splits, C.c_void_p(scheduler_metadata.data_ptr()),
-                                                      ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
-        else:
-            _lib.check(L.tfa_fwd_kvcache_varlen(C.byref(p), C.byref(vq), q8, pack, num_splits, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+        _kvcache_rider_launch(L, p, pv, q8, pack, left, tree, num_splits, scheduler_metadata, q.device)
+    elif scheduler_metadata is not None:
+        meta = C.c_void_p(scheduler_metadata.data_ptr())
+        _kvcache_launch(lambda: L.tfa_fwd_kvcache_varlen_suggest_splits(p, pv, pack), lambda s: L.tfa_fwd_kvcache_varlen_workspace(p, pv, q8, pack, s),
+                        lambda s, ws, stream: L.tfa_fwd_kvcache_varlen_sched(p, pv, q8, pack, s, meta, ws, stream), num_splits, q.device)
+    else:
+        _kvcache_launch(lambda: L.tfa_fwd_kvcache_varlen_suggest_splits(p, pv, pack), lambda s: L.tfa_fwd_kvcache_varlen_workspace(p, pv, q8, pack, s),
+                        lambda s, ws, stream: L.tfa_fwd_kvcache_varlen(p, pv, q8, pack, s, ws, stream), num_splits, q.device)
     out = dense.transpose(0, 1)
     return (out, lse) if return_softmax_lse else out
 
@@ -1354,35 +1306,18 @@ def _tree_words(name, tree_mask, device, B, rows):
     return tree_mask
 
 
-def _kvcache_window_call(L, p, vq, k_descale, v_descale, fp8, pack, left, num_splits, scheduler_metadata, device, tree=None):
+def _kvcache_rider_launch(L, p, pv, q8, pack, left, tree, num_splits, scheduler_metadata, device):
     """The one dispatch to tfa_fwd_kvcache_window — or, with ``tree`` (the int64 words; ``left`` is then None), to tfa_fwd_kvcache_tree, whose arguments are the
-    same but for the window — from the 4-D (``vq`` None) and the packed-q host paths: split count, fp8 block, workspace, launch."""
-    pv = C.byref(vq) if vq is not None else None
+    same but for the window — from the 4-D (``pv`` None) and the packed-q forms: ``p``, ``pv`` and ``q8`` are the structs by reference."""
     fam, rider = "tfa_fwd_kvcache_window", left
     if tree is not None:
         pt = _lib.TfaKvcacheTree()
         pt.mask = tree.data_ptr()
         pt.batch_stride, pt.row_stride = (tree.stride(0), tree.stride(1)) if tree.dim() == 2 else (0, tree.stride(0))
         fam, rider = "tfa_fwd_kvcache_tree", C.byref(pt)
-    if num_splits == 0:
-        num_splits = max(1, int(getattr(L, fam + "_suggest_splits")(C.byref(p), pv, pack, rider)))
-    p8 = None
-    if fp8:
-        p8 = _lib.TfaKvcacheFp8()
-        p8.format = _lib.TFA_KV_E4M3
-        for ptr, strides, t in (("k_descale", p8.k_descale_stride, k_descale), ("v_descale", p8.v_descale_stride, v_descale)):
-            if t is not None:
-                setattr(p8, ptr, t.data_ptr())
-                strides[0], strides[1] = t.stride(0), t.stride(1)
-    q8 = C.byref(p8) if fp8 else None
-    need = getattr(L, fam + "_workspace")(C.byref(p), pv, q8, pack, rider, num_splits)
-    if need < 0:
-        _lib.check(int(need))
-    ws = torch.empty((int(need),), dtype=torch.float32, device=device) if need > 0 else None
     meta = C.c_void_p(scheduler_metadata.data_ptr()) if scheduler_metadata is not None else None
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(getattr(L, fam)(C.byref(p), pv, q8, pack, rider, num_splits, meta, ws.data_ptr() if ws is not None else None, C.c_void_p(stream)))
+    _kvcache_launch(lambda: getattr(L, fam + "_suggest_splits")(p, pv, pack, rider), lambda s: getattr(L, fam + "_workspace")(p, pv, q8, pack, rider, s),
+                    lambda s, ws, stream: getattr(L, fam)(p, pv, q8, pack, rider, s, meta, ws, stream), num_splits, device)
 
 
 def _scheduler_metadata_size(name, B, H, Hk, max_seqlen_q, total_q, pack_gqa, causal):
