@@ -952,6 +952,47 @@ int tfa_fwd_kvcache_tree_plan(const tfa_kvcache_params* p, const tfa_kvcache_var
 long long tfa_fwd_kvcache_tree_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_fp8* q8, int pack_gqa, const tfa_kvcache_tree* tree, int splits);
 int tfa_fwd_kvcache_tree_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, int pack_gqa, const tfa_kvcache_tree* tree);
 
+/* ---- SHARED-PREFIX (cascade) attention over a paged cache: the keys a group of sequences shares are streamed once per group (n-way sampling, beam search, one system
+ * prompt behind many requests) ----------------------------------------------------------------------------------------------------------------------------------------
+ * Two levels over ONE paged 16-bit pool, both in the packed-q layout of tfa_fwd_kvcache_varlen:
+ *   level 1 — *p and *vq as tfa_fwd_kvcache_varlen takes them, over each sequence's OWN keys only: sequence b owns the packed rows [q0_b, q0_b + nq_b) (clamped as
+ *     there) and attends its keys [0, ulen_b), ulen_b = clamp(cache_seqlens[b], 0, capacity), through block_table[b]; p->is_causal: own key j is visible to row t iff
+ *     j <= t + (ulen_b - nq_b).  cache_seqlens counts own keys only and includes this step's rows.  p->k_new must be NULL, p->block_table must not be.
+ *   level 0 — *cs: group g owns the packed rows [pcu[g], pcu[g+1]) of the same q (clamped by the same rule with prefix_max_seqlen_q in max_seqlen_q's place; a group is a
+ *     run of consecutive sequences) and EVERY row of it sees EVERY shared key [0, plen_g), plen_g = clamp(prefix_seqlens[g], 0, prefix_max_blocks * page_size), through
+ *     prefix_block_table[g] into the same pool.  p->is_causal does not act on level 0 (the caller's contract: the shared keys precede all of the step's rows); plen_g
+ *     need not be a multiple of the page size.
+ * A row's result is softmax attention over the disjoint union of its group's shared keys and its sequence's visible own keys, lse the logsumexp over that union.  A row in
+ *   no group takes no shared keys, a row in no sequence no own keys; a row that sees no key at all gives out = 0, lse = +inf — every row of out (H, total_q, D) and lse
+ *   (H, total_q) is written.  Overlapping groups, or anything else the six device arrays may hold, give unspecified values in the rows concerned and never an access
+ *   outside the tensors.  Nothing is read on the host; bytes behind a length read as zeros; a captured call replayed after the arrays were overwritten in place computes
+ *   with the new values.
+ * What runs, all on `stream`: a fill of the workspace's LSE words with +inf; the packed-q kernel over level 0 (non-causal, the groups as its sequences, prefix_splits
+ *   chunks) writing fp32 partials into parts [0, ns0) of the workspace; the same kernel over level 1 (splits chunks) into parts [ns0, ns0 + ns1) — fp32 also when
+ *   ns1 == 1 —; ONE merge over the ns0 + ns1 parts (csrc/tfa_merge.hip: merge_skip_kernel), which SKIPS a part whose LSE is +inf whatever its O words hold: rows no
+ *   group or no sequence owns are never written by a level.  O is rounded to 16 bits once.  ns0 / ns1: the chunk counts after the clamp every call applies
+ *   (min(splits, ceil(capacity / 64)) per level).
+ * metadata / prefix_metadata (NULL: unscheduled): the lists tfa_kvcache_varlen_schedule built for level 1 (from *p, *vq, p->is_causal) and for level 0 (from the level-0
+ *   batch — B = num_groups, prefix_cu_seqlens_q, prefix_max_seqlen_q — with is_causal = 0); each level then runs its scheduled form.  Results are bit for bit those without.
+ * _workspace: (ns0 + ns1) * H * total_q * (D + 1) floats — never 0: this call always merges.  _plan: the launch of one level (level 0 | 1; scheduled / prefix_scheduled
+ *   != 0 ask for that level's scheduled geometry) — equal to the plan of the packed-q call the level stands for.  _suggest_splits: tfa_fwd_kvcache_varlen_suggest_splits
+ *   per level, with each level's geometry.  _plan, _workspace and _suggest_splits need no GPU.
+ * Refused, nothing launched: NULL cs or a NULL member of it, a NULL p->block_table (TFA_ERR_NULL); num_groups, prefix_max_blocks or prefix_max_seqlen_q <= 0, a non-zero
+ *   reserved_, prefix_splits < 1, a level other than 0 / 1 (TFA_ERR_SHAPE); a misaligned index array (TFA_ERR_ALIGN); prefix_block_table_stride < prefix_max_blocks, an
+ *   out that is not dense (H, total_q, D) (TFA_ERR_STRIDE: always checked — this call always merges); everything tfa_fwd_kvcache_varlen refuses, with its codes.
+ * Not here: e4m3 pools, contiguous caches, the 4-D layout, a window or a tree on either level, more than two levels, an append. */
+typedef struct tfa_kvcache_cascade {
+  const int32_t* prefix_cu_seqlens_q;   /* device, num_groups + 1 */
+  const int32_t* prefix_seqlens;        /* device, num_groups */
+  const int32_t* prefix_block_table;    /* device, num_groups x prefix_max_blocks, row stride below */
+  int64_t prefix_block_table_stride;
+  int32_t num_groups, prefix_max_blocks, prefix_max_seqlen_q, reserved_;
+} tfa_kvcache_cascade;
+int tfa_fwd_kvcache_cascade(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits, int prefix_splits, const int32_t* metadata /* NULL: unscheduled */, const int32_t* prefix_metadata /* NULL: unscheduled */, float* workspace, void* stream);
+long long tfa_fwd_kvcache_cascade_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits, int prefix_splits);
+int tfa_fwd_kvcache_cascade_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits, int prefix_splits, int scheduled, int prefix_scheduled, int level /* 0 | 1 */, int* grid, int* block, int* lds_bytes);
+int tfa_fwd_kvcache_cascade_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int* splits, int* prefix_splits);
+
 /* ---- rotary position embedding (FlashAttention-2's apply_rotary_emb; its ROCm build runs a Triton kernel, this one is HIP) ----------------------------
  * Rotates x (B, N, H, D) — or packed (total, H, D) with cu_seqlens — into out; optionally a second tensor x2 -> out2 of H2 heads with strides of its own in the
  * same launch (q and k of one step).  16-bit elements, any batch / head / row strides (elements), unit stride along D: a slice of a packed QKV projection works.

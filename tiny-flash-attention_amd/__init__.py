@@ -15,7 +15,8 @@ FlashAttention-2's training interface: ``flash_attn_func`` / ``flash_attn_varlen
 (GQA, bottom-right aligned masks, a deterministic backward); ``flash_attn_fwd`` / ``_bwd`` and their ``_varlen`` forms underneath.  ``flash_attn_func`` also
 takes ``attn_bias``: a dense additive bias or mask as scaled_dot_product_attention's ``attn_mask`` (fixed-length calls; no gradient for the bias).
 Its inference interface: ``flash_attn_with_kvcache`` (device-side ``cache_seqlens``, paged K/V, in-place append; 16-bit or fp8 e4m3 caches with ``k_descale`` / ``v_descale``;
-packed ragged query rows with ``cu_seqlens_q``, and ``get_scheduler_metadata`` / ``scheduler_metadata=`` for a work list built once per step on the device).
+packed ragged query rows with ``cu_seqlens_q``, and ``get_scheduler_metadata`` / ``scheduler_metadata=`` for a work list built once per step on the device) and
+``flash_attn_with_kvcache_cascade`` (shared-prefix attention: a group's shared pages streamed once per group, each sequence's own once, one merge).
 Around attention: ``apply_rotary_emb`` / ``apply_rotary_emb_qk_`` (rotary embedding at device-side positions) and ``kvcache_append_varlen`` (a unified batch's
 new K/V rows into a paged or contiguous cache — 16-bit or e4m3 with descales —, K optionally rotated on the way in and q in place in the same launch) — with the two attention calls a whole decode or chunked-prefill step.
 """
@@ -35,6 +36,7 @@ from .ops import (  # noqa: F401
     flash_attn_varlen_fwd,
     flash_attn_varlen_bwd,
     flash_attn_with_kvcache,
+    flash_attn_with_kvcache_cascade,
     get_scheduler_metadata,
     apply_rotary_emb,
     apply_rotary_emb_qk_,
@@ -58,6 +60,7 @@ __all__ = [
     "flash_attn_varlen_fwd",
     "flash_attn_varlen_bwd",
     "flash_attn_with_kvcache",
+    "flash_attn_with_kvcache_cascade",
     "get_scheduler_metadata",
     "apply_rotary_emb",
     "apply_rotary_emb_qk_",

@@ -120,6 +120,10 @@ SYMBOLS = (
     "tfa_fwd_kvcache_tree_plan",
     "tfa_fwd_kvcache_tree_workspace",
     "tfa_fwd_kvcache_tree_suggest_splits",
+    "tfa_fwd_kvcache_cascade",
+    "tfa_fwd_kvcache_cascade_workspace",
+    "tfa_fwd_kvcache_cascade_plan",
+    "tfa_fwd_kvcache_cascade_suggest_splits",
     "tfa_rotary",
     "tfa_rotary_plan",
     "tfa_kvcache_append_varlen",
@@ -359,6 +363,21 @@ class TfaKvcacheTree(C.Structure):
         ("mask", C.c_void_p),
         ("batch_stride", C.c_int64),
         ("row_stride", C.c_int64),
+    ]
+
+
+class TfaKvcacheCascade(C.Structure):
+    """struct tfa_kvcache_cascade (include/tfa.h): the groups' shared keys of tfa_fwd_kvcache_cascade, handed over beside TfaKvcacheParams and TfaKvcacheVarlenQ."""
+
+    _fields_ = [
+        ("prefix_cu_seqlens_q", C.c_void_p),
+        ("prefix_seqlens", C.c_void_p),
+        ("prefix_block_table", C.c_void_p),
+        ("prefix_block_table_stride", C.c_int64),
+        ("num_groups", C.c_int32),
+        ("prefix_max_blocks", C.c_int32),
+        ("prefix_max_seqlen_q", C.c_int32),
+        ("reserved_", C.c_int32),
     ]
 
 
@@ -652,6 +671,16 @@ def lib():
     L.tfa_fwd_kvcache_tree_workspace.argtypes = [PK, PV, P8, C.c_int, PT, C.c_int]
     L.tfa_fwd_kvcache_tree_suggest_splits.restype = C.c_int
     L.tfa_fwd_kvcache_tree_suggest_splits.argtypes = [PK, PV, C.c_int, PT]
+    # ... and shared-prefix (cascade) attention: the packed-q call over each sequence's own keys plus the tfa_kvcache_cascade of the groups' shared keys
+    PC = C.POINTER(TfaKvcacheCascade)
+    L.tfa_fwd_kvcache_cascade.restype = C.c_int
+    L.tfa_fwd_kvcache_cascade.argtypes = [PK, PV, PC, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tfa_fwd_kvcache_cascade_workspace.restype = C.c_longlong
+    L.tfa_fwd_kvcache_cascade_workspace.argtypes = [PK, PV, PC, C.c_int, C.c_int, C.c_int]
+    L.tfa_fwd_kvcache_cascade_plan.restype = C.c_int
+    L.tfa_fwd_kvcache_cascade_plan.argtypes = [PK, PV, PC, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP]
+    L.tfa_fwd_kvcache_cascade_suggest_splits.restype = C.c_int
+    L.tfa_fwd_kvcache_cascade_suggest_splits.argtypes = [PK, PV, PC, C.c_int, IP, IP]
     # rotary embedding (tfa_rotary_params) and the packed append (tfa_kvcache_append_varlen_params)
     PR, PA = C.POINTER(TfaRotaryParams), C.POINTER(TfaKvcacheAppendVarlenParams)
     for name, args in (("tfa_rotary", [PR, C.c_void_p]), ("tfa_rotary_plan", [PR, IP, IP]),

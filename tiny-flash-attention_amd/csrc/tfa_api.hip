@@ -17,6 +17,9 @@ namespace tfa {
 hipError_t launch_f32(const KArgs& a, bool causal, hipStream_t stream, int* grid_out, bool dry);
 template <> hipError_t launch_splitkv_wide<__bf16>(const KArgs&, bool, hipStream_t, LaunchGeom*, bool);
 template <> hipError_t launch_splitkv_wide<_Float16>(const KArgs&, bool, hipStream_t, LaunchGeom*, bool);
+// tfa_merge.hip, the merge of tfa_fwd_kvcache_cascade: tfa_merge's arguments and checks; a part whose LSE is +inf contributes nothing whatever its O words hold
+int merge_skip(const float* o_parts, const float* lse_parts, int nparts, int64_t rows, int D, int64_t o_part_stride, int64_t lse_part_stride, void* out, int out_dtype,
+               float* lse_out, void* stream);
 }  // namespace tfa
 
 namespace {
@@ -876,6 +879,9 @@ struct KvcCall {
   const tfa_kvcache_tree* tree = nullptr;
   int rider = tfa::KVC_NONE;            // the entry point's: KVC_WIN wants win_left >= 0, KVC_TREE a tree — their absence is then an error, not "no rider"
   bool packed_q = false;                // the entry point takes a packed q: a NULL vq is then an error, not "4-D"
+  // one level of tfa_fwd_kvcache_cascade (parts > 0): the call is a partial pass only — fp32 O and LSE at every chunk count, one included, into parts
+  // [part0, part0 + chunks) of a workspace of `parts` parts; the merge over all parts is the caller's.  A base-pointer offset: the kernels do not learn of it
+  int part0 = 0, parts = 0;
 };
 static KvcCall kvc_call(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, int pack, int splits) {
   KvcCall c;
@@ -934,7 +940,7 @@ static int kvcache_geom_vq(const KvcCall& c, int ns, const tfa_fwd_params* f, tf
   if (st != TFA_OK) return st;
   const bool causal = f->is_causal != 0;
   const int G = p->H / p->Hk, mq = f->Nq;
-  const int osz = ns > 1 ? 4 : 2;
+  const int osz = (ns > 1 || c.parts > 0) ? 4 : 2;
   bool packed = kvcache_vq_packs(p, c.pack);
   if (packed) {      // a head group's rows must fit the 32-bit byte offsets of one descriptor; else unpacked — packing is an optimisation, never a requirement
     const long long q_ext = ((long long)(mq - 1) * a->qs_n + (long long)(G - 1) * a->qs_h + p->D) * 2;
@@ -1022,9 +1028,13 @@ static int kvcache_run(const KvcCall& c, float* workspace, void* stream, tfa::La
   f.softmax_scale = p->softmax_scale;
   f.is_causal = p->is_causal ? 1 : 0;
   f.dtype = f.out_dtype = p->dtype;
-  float* ws_o = workspace;
-  float* ws_l = workspace ? workspace + (long long)ns * rows * p->D : nullptr;
-  if (ns > 1) {
+  const bool partial = c.parts > 0;                        // a level of the cascade call: its parts of a larger workspace, no merge here
+  if (partial && (!vq || c.part0 < 0 || c.part0 + ns > c.parts)) return TFA_ERR_SHAPE;
+  const bool f32 = ns > 1 || partial;
+  const long long nparts = partial ? c.parts : ns;         // the parts of the workspace: all O parts, then all LSE parts (part0 is 0 unless partial)
+  float* ws_o = workspace ? workspace + (long long)c.part0 * rows * p->D : nullptr;
+  float* ws_l = workspace ? workspace + nparts * rows * p->D + (long long)c.part0 * rows : nullptr;
+  if (f32) {
     // the merge writes contiguous rows: out must be a contiguous (B,H,Nq,D) or (H,total_q,D) tensor; the partial pass writes fp32 O and LSE of every chunk into the workspace
     const int64_t head_rows = vq ? vq->total_q : p->Nq;
     if (p->o_stride[2] != p->D || p->o_stride[1] != head_rows * p->D || (!vq && p->o_stride[0] != (int64_t)p->H * p->Nq * p->D)) return TFA_ERR_STRIDE;
@@ -1085,11 +1095,11 @@ static int kvcache_run(const KvcCall& c, float* workspace, void* stream, tfa::La
   const hipError_t e = tfa::by_dtype_width<64, 128>(p->dtype, p->D, [&](auto k) {
     return tfa::by_kvc_form(q8 != nullptr, packed, layout, c.rider, [&](auto form) {
       using A = typename decltype(form)::Args;
-      return tfa::launch_kvc<typename decltype(k)::T, decltype(k)::W, A>(kvc_typed<A>(ka), causal, ns > 1, nt, s, geom, dry);
+      return tfa::launch_kvc<typename decltype(k)::T, decltype(k)::W, A>(kvc_typed<A>(ka), causal, f32, nt, s, geom, dry);
     });
   });
   if (e != hipSuccess) return (int)e;
-  if (dry || ns == 1) return TFA_OK;
+  if (dry || partial || ns == 1) return TFA_OK;
   return tfa_merge(ws_o, ws_l, ns, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
 }
 
@@ -1273,6 +1283,101 @@ int tfa_fwd_kvcache_tree_suggest_splits(const tfa_kvcache_params* p, const tfa_k
   (void)tree;                                              // the underlying form's rule: the mask removes no tile
   if (!p) return 1;
   return vq ? tfa_fwd_kvcache_varlen_suggest_splits(p, vq, pack_gqa) : kvcache_suggest_splits(p, pack_gqa);
+}
+
+// ---- the cascade form (tfa.h: tfa_fwd_kvcache_cascade): two packed-q calls over one pool — the groups' shared keys, the sequences' own — as partial passes into one
+// workspace, and one merge over all their parts.  Both levels are KvcCalls through kvcache_run; what is new on the device is the merge that skips empty parts
+// (tfa_merge.hip: tfa::merge_skip)
+// level 0 as a packed-q call of its own: the groups as its sequences, non-causal, over the same q, out and pool
+struct KvcCascade {
+  tfa_kvcache_params p0;
+  tfa_kvcache_varlen_q vq0;
+};
+static int kvcache_cascade_levels(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, KvcCascade* lv) {
+  if (!p || !vq || !cs || !cs->prefix_cu_seqlens_q || !cs->prefix_seqlens || !cs->prefix_block_table || !p->block_table) return TFA_ERR_NULL;
+  if (cs->num_groups <= 0 || cs->prefix_max_blocks <= 0 || cs->prefix_max_seqlen_q <= 0 || cs->reserved_ != 0) return TFA_ERR_SHAPE;
+  if (p->page_size <= 0 || (long long)cs->prefix_max_blocks * p->page_size > 0x7fffffffll) return TFA_ERR_SHAPE;
+  if (((uintptr_t)cs->prefix_cu_seqlens_q | (uintptr_t)cs->prefix_seqlens | (uintptr_t)cs->prefix_block_table) & 3) return TFA_ERR_ALIGN;
+  lv->p0 = *p;
+  lv->p0.B = cs->num_groups;
+  lv->p0.cache_seqlens = cs->prefix_seqlens;
+  lv->p0.block_table = cs->prefix_block_table;
+  lv->p0.block_table_stride = cs->prefix_block_table_stride;
+  lv->p0.capacity = cs->prefix_max_blocks * p->page_size;
+  lv->p0.is_causal = 0;
+  lv->vq0 = *vq;
+  lv->vq0.cu_seqlens_q = cs->prefix_cu_seqlens_q;
+  lv->vq0.max_seqlen_q = cs->prefix_max_seqlen_q;
+  return TFA_OK;
+}
+// the two levels as calls: dry runs of both validate everything before anything is launched.  *ns0 / *ns1: the chunk counts each level runs
+static int kvcache_cascade_calls(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack, int splits, int prefix_splits,
+                                 const int32_t* meta, const int32_t* prefix_meta, bool sched, bool prefix_sched, KvcCascade* lv, KvcCall* c0, KvcCall* c1, int* ns0,
+                                 int* ns1) {
+  int st = kvcache_cascade_levels(p, vq, cs, lv);
+  if (st != TFA_OK) return st;
+  if (splits < 1 || prefix_splits < 1) return TFA_ERR_SHAPE;
+  *c0 = kvc_varlen_call(&lv->p0, &lv->vq0, nullptr, pack, prefix_splits, prefix_meta, prefix_sched);
+  *c1 = kvc_varlen_call(p, vq, nullptr, pack, splits, meta, sched);
+  if (p->capacity <= 0) return TFA_ERR_SHAPE;
+  *ns0 = kvcache_chunks(&lv->p0, prefix_splits);
+  *ns1 = kvcache_chunks(p, splits);
+  c0->part0 = 0; c1->part0 = *ns0;
+  c0->parts = c1->parts = *ns0 + *ns1;
+  st = kvcache_run(*c1, nullptr, nullptr, nullptr, true);
+  return st != TFA_OK ? st : kvcache_run(*c0, nullptr, nullptr, nullptr, true);
+}
+
+int tfa_fwd_kvcache_cascade(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits, int prefix_splits,
+                            const int32_t* metadata, const int32_t* prefix_metadata, float* workspace, void* stream) {
+  KvcCascade lv;
+  KvcCall c0, c1;
+  int ns0 = 0, ns1 = 0;
+  int st = kvcache_cascade_calls(p, vq, cs, pack_gqa, splits, prefix_splits, metadata, prefix_metadata, metadata != nullptr, prefix_metadata != nullptr, &lv, &c0, &c1,
+                                 &ns0, &ns1);
+  if (st != TFA_OK) return st;
+  if (!workspace) return TFA_ERR_NULL;
+  if (((uintptr_t)workspace & 15) || (((uintptr_t)metadata | (uintptr_t)prefix_metadata) & 7)) return TFA_ERR_ALIGN;
+  const int parts = ns0 + ns1;
+  const long long rows = kvcache_rows(c1);
+  float* ws_l = workspace + (long long)parts * rows * p->D;
+  // every part starts empty (+inf, 0x7f800000): the rows no group owns, the rows no sequence owns and the blocks without rows are written by no level
+  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ws_l), 0x7f800000, (size_t)((long long)parts * rows), reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return (int)e;
+  st = kvcache_run(c0, workspace, stream, nullptr, false);
+  if (st != TFA_OK) return st;
+  st = kvcache_run(c1, workspace, stream, nullptr, false);
+  if (st != TFA_OK) return st;
+  return tfa::merge_skip(workspace, ws_l, parts, rows, p->D, rows * p->D, rows, p->out, p->dtype, p->lse, stream);
+}
+long long tfa_fwd_kvcache_cascade_workspace(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits,
+                                            int prefix_splits) {
+  KvcCascade lv;
+  KvcCall c0, c1;
+  int ns0 = 0, ns1 = 0;
+  const int st = kvcache_cascade_calls(p, vq, cs, pack_gqa, splits, prefix_splits, nullptr, nullptr, false, false, &lv, &c0, &c1, &ns0, &ns1);
+  if (st != TFA_OK) return st;
+  return (long long)(ns0 + ns1) * kvcache_rows(c1) * (p->D + 1);
+}
+int tfa_fwd_kvcache_cascade_plan(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int splits, int prefix_splits,
+                                 int scheduled, int prefix_scheduled, int level, int* grid, int* block, int* lds_bytes) {
+  KvcCascade lv;
+  KvcCall c0, c1;
+  int ns0 = 0, ns1 = 0;
+  const int st = kvcache_cascade_calls(p, vq, cs, pack_gqa, splits, prefix_splits, nullptr, nullptr, scheduled != 0, prefix_scheduled != 0, &lv, &c0, &c1, &ns0, &ns1);
+  if (st != TFA_OK) return st;
+  if (level != 0 && level != 1) return TFA_ERR_SHAPE;
+  return kvcache_plan(level == 0 ? c0 : c1, grid, block, lds_bytes);
+}
+int tfa_fwd_kvcache_cascade_suggest_splits(const tfa_kvcache_params* p, const tfa_kvcache_varlen_q* vq, const tfa_kvcache_cascade* cs, int pack_gqa, int* splits,
+                                           int* prefix_splits) {
+  KvcCascade lv;
+  if (!splits || !prefix_splits) return TFA_ERR_NULL;
+  const int st = kvcache_cascade_levels(p, vq, cs, &lv);
+  if (st != TFA_OK) return st;
+  *splits = tfa_fwd_kvcache_varlen_suggest_splits(p, vq, pack_gqa);
+  *prefix_splits = tfa_fwd_kvcache_varlen_suggest_splits(&lv.p0, &lv.vq0, pack_gqa);
+  return TFA_OK;
 }
 
 static int kvcache_append_run(const tfa_kvcache_params* p, const tfa_kvcache_fp8* q8, void* stream) {

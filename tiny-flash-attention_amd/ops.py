@@ -1274,6 +1274,141 @@ def _flash_attn_with_kvcache_varlen_q(q, k_cache, v_cache, k, v, cache_seqlens, 
     return (out, lse) if return_softmax_lse else out
 
 
+def flash_attn_with_kvcache_cascade(q, k_cache, v_cache, *, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, prefix_cu_seqlens_q, prefix_max_seqlen_q,
+                                    prefix_seqlens, prefix_block_table, softmax_scale=None, causal=True, num_splits=0, prefix_num_splits=0,
+                                    return_softmax_lse=False, pack_gqa=None, scheduler_metadata=None, prefix_scheduler_metadata=None):
+    """Shared-prefix (cascade) attention over a paged K/V cache (tfa_fwd_kvcache_cascade): the keys a group of sequences shares — one prompt behind n samples, a
+    system prompt behind many requests, the common trunk of a beam — are streamed once per GROUP, each sequence's own keys once per sequence, and the two are
+    merged by LSE in fp32 before the one rounding of ``out``.
+
+    ``q`` is packed (total_q, H, D) exactly as ``flash_attn_with_kvcache(cu_seqlens_q=)`` takes it; ``k_cache`` / ``v_cache`` one paged 16-bit pool
+    (num_pages, page_size, Hk, D) of q's dtype, page_size a multiple of 64, any page / row / head strides; both tables index this pool.
+    Level 1, each sequence's OWN keys — ``cu_seqlens_q`` (B + 1,), ``max_seqlen_q``, ``cache_seqlens`` (B,), ``block_table`` (B, max_blocks): the packed-q call over
+    the non-shared keys only.  Sequence b owns the rows [q0_b, q0_b + nq_b) (clamped as there) and attends its own keys [0, ulen_b),
+    ulen_b = clamp(cache_seqlens[b], 0, max_blocks * page_size), through ``block_table[b]``; ``cache_seqlens`` counts own keys only and includes this step's rows.
+    ``causal``: own key j is visible to row t iff j <= t + (ulen_b - nq_b).
+    Level 0, each group's SHARED keys — ``prefix_cu_seqlens_q`` (Gn + 1,), ``prefix_max_seqlen_q``, ``prefix_seqlens`` (Gn,), ``prefix_block_table``
+    (Gn, prefix_max_blocks): group g owns the packed rows [pcu[g], pcu[g+1]) (clamped by the same rule with ``prefix_max_seqlen_q``; a group is a run of
+    consecutive sequences, so the engine builds this array the way it builds ``cu_seqlens_q``) and EVERY row of it sees EVERY key [0, plen_g),
+    plen_g = clamp(prefix_seqlens[g], 0, prefix_max_blocks * page_size), through ``prefix_block_table[g]`` — the caller's contract: the shared keys precede all of
+    the step's rows.  ``causal`` does not act on level 0; plen_g need not be a multiple of the page size.
+    A row's result is softmax attention over the disjoint union of its group's shared keys and its sequence's visible own keys; ``lse`` is the logsumexp over
+    that union.  A row in no group takes no shared keys, a row in no sequence no own keys; a row that sees no key at all gives out = 0, lse = +inf: every row of
+    ``out`` (total_q, H, D) — a transposed view of the dense (H, total_q, D) buffer the merge writes — and of ``lse`` (H, total_q) is specified.  Overlapping
+    groups, or any other garbage in the six device arrays, give unspecified values in the rows concerned and never an access outside the tensors.
+    Nothing is read on the host (no synchronisation; a captured step replayed after the six arrays were overwritten in place computes with the new values); bytes
+    behind a length read as zeros; ``pack_gqa`` is a scheduling choice only (None / True pack when Hk < H and H / Hk <= 128); everything runs on the current stream.
+    ``num_splits`` / ``prefix_num_splits``: key chunks of level 1 / level 0 (0 = tfa_fwd_kvcache_cascade_suggest_splits, each level's own geometry).
+    ``scheduler_metadata``: the list ``get_scheduler_metadata(cu_seqlens_q, max_seqlen_q, total_q, H, Hk, causal=causal, pack_gqa=pack_gqa)`` built for level 1;
+    ``prefix_scheduler_metadata``: the list the same function builds from ``prefix_cu_seqlens_q`` / ``prefix_max_seqlen_q`` with ``causal=False``.  Results with
+    lists are bit for bit those without.
+    What runs: a fill of the workspace's LSE words, the packed-q kernel once per level writing fp32 partials, one merge that skips empty parts.  Not
+    differentiable.  Refused by name before any launch: a 4-D q, a contiguous cache (``block_table`` None), mismatched B or Gn between a level's three arrays, an
+    index array of the wrong dtype / device / contiguity, a missing or non-positive maximum, negative split counts (ValueError); fp8 pools, a k / v dtype other than
+    q's (TypeError); an input that requires grad (RuntimeError); head dims and fp32 as the packed-q call refuses them."""
+    name = "flash_attn_with_kvcache_cascade"
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        got = tuple(q.shape) if isinstance(q, torch.Tensor) else type(q).__name__
+        raise ValueError(f"{name}: q must be packed (total_q, H, D) (got {got}); the 4-D layout has no cascade form")
+    for n, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be a 4-D paged pool (num_pages, page_size, Hk, D)")
+    for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{n} must be a CUDA tensor")
+    if k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn:
+        raise TypeError(f"{name}: fp8 pools are not implemented (got {k_cache.dtype}, {v_cache.dtype}); k_cache and v_cache must have q's 16-bit dtype")
+    if block_table is None or prefix_block_table is None:
+        raise ValueError(f"{name}: a paged pool only — block_table and prefix_block_table must be given (a contiguous cache has no cascade form)")
+    for n, val in (("max_seqlen_q", max_seqlen_q), ("prefix_max_seqlen_q", prefix_max_seqlen_q)):
+        if val is None or isinstance(val, (bool, torch.Tensor)) or not isinstance(val, int) or val <= 0:
+            raise ValueError(f"{name}: {n} must be a positive host int (it sizes the grid; got {val!r})")
+    for n, t in (("cu_seqlens_q", cu_seqlens_q), ("prefix_cu_seqlens_q", prefix_cu_seqlens_q)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 2:
+            raise ValueError(f"{name}: {n} must be a 1-D int32 tensor of at least two entries")
+        if t.device != q.device or not t.is_contiguous():
+            raise ValueError(f"{name}: {n} must be contiguous and on q's device")
+    total_q, H, D = q.shape
+    B, Gn = cu_seqlens_q.numel() - 1, prefix_cu_seqlens_q.numel() - 1
+    for n, lens, table, rows, what in (("cache_seqlens", cache_seqlens, None, B, "B = cu_seqlens_q.numel() - 1"),
+                                       ("prefix_seqlens", prefix_seqlens, prefix_block_table, Gn, "Gn = prefix_cu_seqlens_q.numel() - 1")):
+        if (not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (rows,) or not lens.is_contiguous()
+                or lens.device != q.device):
+            raise ValueError(f"{name}: {n} must be a contiguous int32 tensor of shape ({rows},) — {what} — on q's device")
+        if table is None:
+            continue                                      # (block_table: _kvcache_checks' own check, below)
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] != rows or table.shape[1] < 1:
+            raise ValueError(f"{name}: prefix_block_table must be an int32 tensor of shape ({rows}, prefix_max_blocks) — {what}")
+        if table.device != q.device or table.stride(1) != 1:
+            raise ValueError(f"{name}: prefix_block_table must be on q's device with unit stride along prefix_max_blocks")
+    prefix_num_splits = int(prefix_num_splits)
+    if prefix_num_splits < 0:
+        raise ValueError(f"{name}: prefix_num_splits must be >= 0 (0 = automatic; got {prefix_num_splits})")
+    _, Hk, capacity, cache_seqlens, num_splits = _kvcache_checks(name, q, k_cache, v_cache, None, None, cache_seqlens, block_table, num_splits, pack_gqa, None,
+                                                                 None, B, H, D, True)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    metas = []
+    for n, md, b, mq, cz in (("scheduler_metadata", scheduler_metadata, B, max_seqlen_q, causal),
+                             ("prefix_scheduler_metadata", prefix_scheduler_metadata, Gn, prefix_max_seqlen_q, False)):
+        if md is None:
+            metas.append(None)
+            continue
+        if not isinstance(md, torch.Tensor):
+            raise TypeError(f"{name}: {n} must be the tensor get_scheduler_metadata returned (got {type(md).__name__})")
+        if md.dtype != torch.int32 or md.device != q.device or not md.is_contiguous():
+            raise ValueError(f"{name}: {n} must be a contiguous int32 tensor on q's device (got {md.dtype} on {md.device})")
+        want = _scheduler_metadata_size(name, b, H, Hk, int(mq), total_q, pack_gqa, cz)
+        if md.numel() != want:
+            raise ValueError(f"{name}: {n} holds {md.numel()} entries, this level's schedule ({b} sequences, max_seqlen_q {mq}, total_q {total_q}, H {H}, Hk {Hk}, "
+                             f"causal {bool(cz)}, pack_gqa {pack_gqa!r}) holds {want}: it was built for another batch")
+        metas.append(C.c_void_p(md.data_ptr()))
+
+    L = _lib.lib()
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device) if return_softmax_lse else None
+    dense = torch.empty((H, total_q, D), dtype=q.dtype, device=q.device)          # what the merge writes
+    p = _lib.TfaKvcacheParams()
+    p.q, p.out = q.data_ptr(), dense.data_ptr()
+    p.lse = lse.data_ptr() if lse is not None else None
+    p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    p.cache_seqlens = cache_seqlens.data_ptr()
+    p.B, p.H, p.Hk, p.Nq, p.D, p.capacity = B, H, Hk, 0, D, capacity
+    p.block_table = block_table.data_ptr()
+    p.block_table_stride = block_table.stride(0)
+    p.page_size, p.num_pages = k_cache.shape[1], k_cache.shape[0]
+    p.q_stride[0], p.q_stride[1], p.q_stride[2] = 0, q.stride(1), q.stride(0)     # {ignored, head, row}
+    p.o_stride[0], p.o_stride[1], p.o_stride[2] = 0, total_q * D, D
+    for sname, t in (("k_stride", k_cache), ("v_stride", v_cache)):
+        arr = getattr(p, sname)
+        arr[0], arr[1], arr[2] = t.stride(0), t.stride(2), t.stride(1)
+    p.softmax_scale = float(softmax_scale)
+    p.is_causal = 1 if causal else 0
+    p.dtype = _DT[q.dtype]
+    vq = _lib.TfaKvcacheVarlenQ()
+    vq.cu_seqlens_q = cu_seqlens_q.data_ptr()
+    vq.max_seqlen_q, vq.total_q = int(max_seqlen_q), total_q
+    cs = _lib.TfaKvcacheCascade()
+    cs.prefix_cu_seqlens_q, cs.prefix_seqlens = prefix_cu_seqlens_q.data_ptr(), prefix_seqlens.data_ptr()
+    cs.prefix_block_table, cs.prefix_block_table_stride = prefix_block_table.data_ptr(), prefix_block_table.stride(0)
+    cs.num_groups, cs.prefix_max_blocks, cs.prefix_max_seqlen_q = Gn, prefix_block_table.shape[1], int(prefix_max_seqlen_q)
+    p, pv, pc = C.byref(p), C.byref(vq), C.byref(cs)
+    pack = _lib.TFA_PACK_GQA_OFF if pack_gqa is False else _lib.TFA_PACK_GQA_ON
+    if num_splits == 0 or prefix_num_splits == 0:
+        s1, s0 = C.c_int(1), C.c_int(1)
+        _lib.check(L.tfa_fwd_kvcache_cascade_suggest_splits(p, pv, pc, pack, C.byref(s1), C.byref(s0)))
+        num_splits = num_splits or max(1, s1.value)
+        prefix_num_splits = prefix_num_splits or max(1, s0.value)
+    need = int(L.tfa_fwd_kvcache_cascade_workspace(p, pv, pc, pack, num_splits, prefix_num_splits))
+    if need < 0:
+        _lib.check(need)
+    ws = torch.empty((need,), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.tfa_fwd_kvcache_cascade(p, pv, pc, pack, num_splits, prefix_num_splits, metas[0], metas[1], ws.data_ptr(), C.c_void_p(stream)))
+    out = dense.transpose(0, 1)
+    return (out, lse) if return_softmax_lse else out
+
+
 def _window_left(sliding_window, capacity):
     """The ``window_left`` of tfa_fwd_kvcache_window for a checked ``sliding_window``, or None where the plain causal entry points run: no window, or one that
     reaches every key a row can see (w - 1 >= capacity — the host knows it)."""
